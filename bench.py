@@ -8,7 +8,13 @@ One "step" = one pass of the hot path over one HBM-resident batch of frames (con
  -> CalcFade on the device (:1317-1341, amtgpu_erase_calc_fades_device)  -> AMTEraseLogo in place (:1248-1261, :1374-1397)
 Inputs are already in HBM when the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` (frames/sec) and `ms_per_step` are those of
+the timed steps.  --dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy (float32, or float64 for
+integer sums), inputs identical from run to run, so that two builds can be compared output for output.  Everything else
+described below -- per-kernel timing and `roofline`, the CPU oracle check (`verified`), `exact_mode`, `in_place_erase_step`,
+the other analysis mode, `strong_scan`, `configs`, `e2e10`, `boundary`, `ingest`, `cpu_baseline` -- runs with --full only.
 
 --gpus N > 1 without a torch.distributed environment re-executes itself under torch.distributed.run (one rank per GPU,
 RCCL); the driver's own `python -m torch.distributed.run ... bench.py --gpus N` is used as it comes.
@@ -107,6 +113,13 @@ def parse_args():
     ap.add_argument("--analysis-mode", choices=("linear", "exact"), default="linear",
                     help="AMTAnalyzeLogo evaluation: linear = all fades from one window evaluation of s and bg, decisions guarded by exact "
                          "re-evaluation (identical fades / erased frames, scores within 1e-4); exact = the reference's fp32 order for every fade")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel timing and roofline, verification against the CPU oracle, the exact-mode and in-place "
+                         "erase steps, the other analysis mode, the strong scan, the other configurations, e2e10, boundary, ingest, CPU baseline "
+                         "(each still subject to its own --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; at most 64 MB, a fixed seeded "
+                         "sample of frames where the whole output is larger)")
     return ap.parse_args()
 
 
@@ -468,8 +481,41 @@ def emit(full):
     return line
 
 
+DUMP_LIMIT = 64 << 20                  # bytes of all dumped arrays together
+DUMP_SEED = 0x5EED0D0D
+DUMP_RECT_FRAMES = 128                 # erased logo rectangles: frames sampled
+DUMP_RECORD_FRAMES = 65536             # per-frame records: all frames up to this many, a sample beyond
+
+
+def dump_sample(n, k):
+    """sorted indices of a fixed, seeded sample of k of n frames (all n where k >= n)"""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(outdir, arrays):
+    """arrays: name -> array (numpy or torch).  Written as outdir/<name>.npy: floating point as float32, integers as float64 (the
+    integer outputs are sums far below 2**53, so the conversion is exact)"""
+    conv = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        exact32 = a.dtype.kind == "f" and a.dtype.itemsize <= 4 or a.dtype.kind in "iub" and a.dtype.itemsize <= 2
+        conv[name] = np.ascontiguousarray(a, np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
+    if args.dump_outputs and args.workload == "e2e10":
+        raise SystemExit("--dump-outputs: available for the headline workload and --scaling strong, not for --workload e2e10")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args)
     import torch
@@ -572,7 +618,7 @@ def main():
     # ================================================================================================================
     # strong scaling: BASELINE configs[3] -- the all-frames LogoFrame scan of a 60-minute stream, frames sharded
     # ================================================================================================================
-    def strong_scan():
+    def strong_scan(dump=None):
         NT = args.strong_frames
         f0, f1 = SH.shard_range(NT, rank, world)
         nloc = f1 - f0
@@ -607,6 +653,11 @@ def main():
         el = max_over_ranks(time.perf_counter() - t0)
         prof = ctx.profile_report()
         ctx.profile(False)
+        if dump and rank == 0:                                        # the last timed step's records (the whole clip's on rank 0) and decision
+            rec = lf.evalResults
+            sel = dump_sample(NT, DUMP_RECORD_FRAMES)
+            dump_outputs(dump, {"scan_records": rec[sel] if len(sel) < NT else rec,
+                                "logo_selection": np.array([lf.getBestLogo(), lf.getLogoRatio()], np.float64)})
         # ---- EVERY record of this rank's shard against the CPU oracle (threaded; only the logo rectangle's rows travel to the host):
         #      LogoScan.hpp:1543-1568.  Flags and frame counts are reduced over the ranks. ----
         vall = None
@@ -665,7 +716,7 @@ def main():
         return out
 
     if args.scaling == "strong":
-        ss = strong_scan()
+        ss = strong_scan(dump=args.dump_outputs)
         if rank == 0:
             line = {"metric": "frames/sec 1440x1080i logo+CM+KFM pass", "value": ss["value"], "unit": "frames/sec", "n_gpus": world,
                     "steps": args.strong_steps, "warmup": 2, "ms_per_step": ss["ms_per_step"], "higher_is_better": True,
@@ -782,15 +833,65 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    profile_on(True)
+    if args.full:                                                    # per-kernel HIP events on the launch stream (the kernel table, roofline)
+        profile_on(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    prof = profile_read()
-    profile_on(False)
+    prof = {}
+    if args.full:
+        prof = profile_read()
+        profile_on(False)
     elapsed = max_over_ranks(elapsed)
+
+    # what the last timed step computed, before anything below runs the step again
+    if args.dump_outputs and rank == 0:
+        rows = dump_sample(N, DUMP_RECORD_FRAMES)
+        outs = {"analysis": d_analysis[torch.from_numpy(rows).to(dev)], "scan_records": lf.evalResults[rows],
+                "frame_metrics": d_stats[torch.from_numpy(rows).to(dev)]}
+        if not args.no_erase:
+            outs["fades"] = d_fades[torch.from_numpy(rows).to(dev)] if args.fades == "device" else last["fades"][rows]
+        if to_copy:                                                  # the erased frames (the writable copy): the logo rectangle of sampled frames
+            sel = torch.from_numpy(dump_sample(N, DUMP_RECT_FRAMES)).to(dev)
+            outs["erased_Y_rect"] = wclip.Y[sel, IMGY:IMGY + LH, IMGX:IMGX + LW]
+            outs["erased_U_rect"] = wclip.U[sel, IMGY // 2:(IMGY + LH) // 2, IMGX // 2:(IMGX + LW) // 2]
+            outs["erased_V_rect"] = wclip.V[sel, IMGY // 2:(IMGY + LH) // 2, IMGX // 2:(IMGX + LW) // 2]
+        dump_outputs(args.dump_outputs, outs)
+
+    fps = N * world * args.steps / elapsed
+    line = {
+        "metric": "frames/sec 1440x1080i logo+CM+KFM pass",
+        "value": fps, "unit": "frames/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        # (`workload` must survive the compact line's 120-character cut: the list of passes, no prose)
+        "config": {"workload": f"configs[1]: {N}x 1440x1080i 8-bit in HBM: AMTAnalyzeLogo, LogoFrame scan x3, CM/KFM metrics, CalcFade, AMTEraseLogo",
+                   "analysis_mode": args.analysis_mode,
+                   # the headline is NOT the drop-in default: the library and the plugin's "AMTAnalyzeLogo" evaluate in exact mode (every record
+                   # bit-identical); the linear-guarded mode is opt-in (amtgpu_analyze_set_mode / AMTAnalyzeLogoFast).  exact_mode.value is
+                   # the same step at the default
+                   "library_default_mode": "exact",
+                   "value_is_in_mode": ("linear-guarded (opt-in; identical fades and erased frames, scores within 1e-4): see exact_mode.value for the library default"
+                                        if args.analysis_mode == "linear" else "exact (the library default)"),
+                   "calc_fade": args.fades,
+                   "erase": ("none" if args.no_erase else "into a resident writable copy (MakeWritable's frame)" if to_copy else
+                             "in place, rectangles put back inside the step"),
+                   "device_partition": ({"metrics_cus": MCU, "logo_cus": NCU - MCU, "how": "two contexts on CU-range streams (amtgpu_stream_create_cu_range): the "
+                                         "frame metrics run beside the analysis + scan; erase waits for both"} if MCU else None),
+                   "frames_per_gpu": N, "logo": f"{LW}x{LH}@({IMGX},{IMGY})", "maskratio": MASKRATIO,
+                   "parallelism": f"frames sharded x{world} (one private batch per rank)" if world > 1 else "single GPU"},
+        "timed_region_s": elapsed, "collectives": rccl,
+    }
+    if not args.full:
+        if rank == 0:
+            emit(line)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     if not args.no_erase and last.get("fades") is None:
         last["fades"] = d_fades.cpu().numpy()
 
@@ -984,7 +1085,6 @@ def main():
             ingest = {"error": f"{type(e).__name__}: {e}"}
 
     if rank == 0:
-        fps = N * world * args.steps / elapsed
         # ---- per-kernel figures (HIP events on the launch stream, inside the timed steps) ----
         an_tab = [logos[0].mask_tables(k, MASKRATIO)["count"] for k in (0, 1, 2)]
         scan_tab = [l.mask_tables(0, MASKRATIO)["count"] for l in logos]
@@ -1071,35 +1171,15 @@ def main():
         cpu = None
         if args.cpu_frames > 0 and world == 1:        # the CPU baseline is reported at N=1 only
             cpu = cpu_baseline(args.cpu_frames, logos_np, alpha, alphaUV, args.cpu_seconds)
-        line = {
-            "metric": "frames/sec 1440x1080i logo+CM+KFM pass",
-            "value": fps, "unit": "frames/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            # (`workload` must survive the compact line's 120-character cut: the list of passes, no prose)
-            "config": {"workload": f"configs[1]: {N}x 1440x1080i 8-bit in HBM: AMTAnalyzeLogo, LogoFrame scan x3, CM/KFM metrics, CalcFade, AMTEraseLogo",
-                       "analysis_mode": args.analysis_mode,
-                       # the headline is NOT the drop-in default: the library and the plugin's "AMTAnalyzeLogo" evaluate in exact mode (every record
-                       # bit-identical); the linear-guarded mode is opt-in (amtgpu_analyze_set_mode / AMTAnalyzeLogoFast).  exact_mode.value is
-                       # the same step at the default
-                       "library_default_mode": "exact",
-                       "value_is_in_mode": ("linear-guarded (opt-in; identical fades and erased frames, scores within 1e-4): see exact_mode.value for the library default"
-                                            if args.analysis_mode == "linear" else "exact (the library default)"),
-                       "calc_fade": args.fades,
-                       "erase": ("none" if args.no_erase else "into a resident writable copy (MakeWritable's frame)" if to_copy else
-                                 "in place, rectangles put back inside the step"),
-                       "device_partition": ({"metrics_cus": MCU, "logo_cus": NCU - MCU, "how": "two contexts on CU-range streams (amtgpu_stream_create_cu_range): the "
-                                             "frame metrics run beside the analysis + scan; erase waits for both"} if MCU else None),
-                       "frames_per_gpu": N, "logo": f"{LW}x{LH}@({IMGX},{IMGY})", "maskratio": MASKRATIO,
-                       "parallelism": f"frames sharded x{world} (one private batch per rank)" if world > 1 else "single GPU"},
-            "timed_region_s": elapsed, "step_phases_ms": phases, "collectives": rccl,
+        line.update({
+            "step_phases_ms": phases,
             "roofline": roofline, "roofline_second": roofline_second, "cpu_baseline": cpu,
             "gpu_over_cpu": (fps / cpu["value"]) if cpu else None,
             "gpu_over_cpu_all_cores": (fps / cpu["all_cores"]["value"]) if cpu else None,
             "exact_mode": exact_mode, "in_place_erase_step": in_place_step,
             "verified": verified, "configs": configs, "e2e10": e2e, "boundary": boundary, "strong_scan": strong, "ingest": ingest,
             "kernels": out_kern,
-        }
+        })
         emit(line)
     if world > 1:
         dist.barrier()

@@ -4,6 +4,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -120,3 +122,52 @@ def test_round6_detail_compacts_to_the_committed_line():
     e2e = line["e2e10"]
     assert e2e["verified_ok"] is True and e2e["verified_whole_stream"] is True and e2e["verified_frames"] == e2e["frames_total"]
     assert line["roofline"]["traffic_source"].startswith("profiles/r06_") and 0 < line["roofline"]["frac"] < 1
+
+
+def test_dump_outputs_types_sample_and_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float32 stays float32, integer sums become float64 exactly, the frame sample is fixed, the size limit holds"""
+    import numpy as np
+    st = np.array([[0, 2 ** 40 + 3], [7, 9]], np.int64)
+    bench.dump_outputs(str(tmp_path / "d"), {"a": np.arange(6, dtype=np.float32).reshape(2, 3), "m": st, "y": np.full((2, 2), 255, np.uint8)})
+    a, m, y = (np.load(tmp_path / "d" / f"{n}.npy") for n in ("a", "m", "y"))
+    assert a.dtype == np.float32 and a.shape == (2, 3) and m.dtype == np.float64 and (m.astype(np.int64) == st).all()
+    assert y.dtype == np.float32 and (y == 255).all()
+    s = bench.dump_sample(10000, 128)
+    assert len(s) == 128 and (np.diff(s) > 0).all() and (s == bench.dump_sample(10000, 128)).all()
+    assert (bench.dump_sample(50, 128) == np.arange(50)).all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 16)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "e"), {"a": np.zeros(8, np.float32)})
+    assert not (tmp_path / "e").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_them(tmp_path):
+    """a plain run: the line's `steps` are the timed steps, `ms_per_step` their mean; nothing beyond the headline (no oracle check, no
+    attached measurements); --dump-outputs writes the last timed step's outputs, the same bytes from run to run"""
+    import subprocess
+    import numpy as np
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "512",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads(r.stdout.strip().splitlines()[-1])
+    line = run(tmp_path / "a")
+    for k in CONTRACT:
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["config"]["frames_per_gpu"] == 512
+    assert abs(line["ms_per_step"] - line["timed_region_s"] * 1e3 / 3) <= 1e-3 * line["ms_per_step"]
+    assert abs(line["value"] - 512 * 3 / line["timed_region_s"]) <= 1e-4 * line["value"]
+    for k in ("verified", "roofline", "cpu_baseline", "exact_mode", "strong_scan", "configs", "e2e10", "ingest"):
+        assert k not in line, k
+    names = {"analysis": (512, 33), "scan_records": (512, 3, 2), "frame_metrics": (512, 8), "fades": (512, 2),
+             "erased_Y_rect": (128, 128, 256), "erased_U_rect": (128, 64, 128), "erased_V_rect": (128, 64, 128)}
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert {n: g.shape for n, g in got.items()} == names
+    assert all(g.dtype in (np.float32, np.float64) for g in got.values()) and sum(g.nbytes for g in got.values()) <= 64 << 20
+    assert np.isfinite(got["analysis"]).all()
+    run(tmp_path / "b")
+    for n, g in got.items():                  # (the linear-guarded analysis is held to its 1e-4 bound, everything else to the byte)
+        b = np.load(tmp_path / "b" / f"{n}.npy")
+        assert (np.abs(b - g).max() <= 1e-4) if n == "analysis" else b.tobytes() == g.tobytes(), n

@@ -190,7 +190,7 @@ def test_bench_multi_rank_control_flow_dry_run():
     if torch.cuda.device_count() < 2:
         env["AMT_BENCH_SHARED_GPU"] = "1"
     common = ["--gpus", "2", "--strong-frames", "4096", "--strong-steps", "2"]
-    for extra, scaling in ((["--steps", "2", "--warmup", "1", "--frames", "512", "--no-ingest", "--cpu-frames", "0", "--no-alt-mode"], "weak"),
+    for extra, scaling in ((["--full", "--steps", "2", "--warmup", "1", "--frames", "512", "--no-ingest", "--cpu-frames", "0", "--no-alt-mode"], "weak"),
                            (["--scaling", "strong"], "strong")):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + extra, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -247,6 +247,6 @@ def test_bench_eight_rank_control_flow_dry_run():
     for e_ in (e8, e1):                                   # every frame of every rank's share against the CPU oracle
         assert e_["e2e10"]["verified"]["whole_stream"] and e_["e2e10"]["verified"]["frames_compared_with_cpu_oracle"] == 1500
     assert e8["e2e10"]["decisions_sha256"] == e1["e2e10"]["decisions_sha256"]
-    weak = run(["--steps", "1", "--warmup", "1", "--frames", "256", "--no-ingest", "--cpu-frames", "0", "--no-alt-mode", "--no-configs", "--no-strong",
+    weak = run(["--full", "--steps", "1", "--warmup", "1", "--frames", "256", "--no-ingest", "--cpu-frames", "0", "--no-alt-mode", "--no-configs", "--no-strong",
                 "--exact-steps", "0"], 8)
     assert weak["n_gpus"] == 8 and weak["scaling"] == "weak" and weak["verified"]["ok"] and weak["collectives"]["world_size_observed"] == 8

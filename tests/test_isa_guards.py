@@ -18,12 +18,13 @@ import hashlib
 import os
 import re
 import subprocess
+import tempfile
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "amatsukaze_amd", "csrc")
-CACHE = os.path.join("/tmp", "amt_isa_cache")
+CACHE = os.path.join(tempfile.gettempdir(), f"amt_isa_cache_{os.getuid()}")      # per user: a shared machine may hold another user's
 
 # file -> (extra flags, {kernel-name substring: max VGPRs})   budgets: 512 VGPRs per SIMD lane / waves per SIMD, rounded to the allocation granule of 8
 FILES = {
@@ -46,7 +47,9 @@ def compile_asm(name):
     os.makedirs(CACHE, exist_ok=True)
     out = os.path.join(CACHE, f"{name}.{h.hexdigest()[:16]}.s")
     if not os.path.exists(out):
-        subprocess.check_call([B.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", out, src], stderr=subprocess.DEVNULL)
+        tmp = f"{out}.{os.getpid()}.tmp"                          # (renamed into place whole: an interrupted compile leaves no half file)
+        subprocess.check_call([B.hipcc()] + flags + ["-S", "--cuda-device-only", "-o", tmp, src], stderr=subprocess.DEVNULL)
+        os.replace(tmp, out)
     return open(out).read()
 
 
