@@ -354,12 +354,14 @@ def logoframe_decide_host(evals, fps_num=30000, fps_den=1001, numCandidates=-1, 
 class AMTAnalyzeLogo:
     """logo::AMTAnalyzeLogo (LogoScan.hpp:1106-1236); GetFrames returns 33 floats per source frame."""
 
-    MODES = {"exact": 0, "linear": 1, "linear_unguarded": 2}
+    MODES = {"exact": 0, "linear": 1, "linear_unguarded": 2, "monitored": 3}
 
-    def __init__(self, ctx: Context, logo, maskratio: float = 0.35, mode: str = "exact"):
+    def __init__(self, ctx: Context, logo, maskratio: float = 0.35, mode: str = "exact", tolerance: float = 1e-4, sentinels: int = 16):
         """mode "exact": records bit-identical to the reference's; "linear": all fades from one evaluation of the source and one
         of the background window per mask pixel (scores within `error_bound` of the reference's, decisions guarded by exact
-        re-evaluation -- include/amt_gpu.h AMTGPU_ANALYZE_LINEAR_GUARDED)."""
+        re-evaluation -- include/amt_gpu.h AMTGPU_ANALYZE_LINEAR_GUARDED); "monitored": "linear", and `sentinels` frames of every batch
+        are evaluated exactly as well and compared on the device: a score off by more than `tolerance` re-evaluates the batch exactly and
+        keeps the analyzer exact from then on (AMTGPU_ANALYZE_LINEAR_MONITORED)."""
         self.ctx = ctx
         if isinstance(logo, Logo):
             self._keep = logo
@@ -367,7 +369,23 @@ class AMTAnalyzeLogo:
         else:
             self.h = ctx.lib.amtgpu_analyze_create(ctx.h, str(logo).encode(), maskratio)
         ctx.check(self.h, "AMTAnalyzeLogo")
-        ctx.check(ctx.lib.amtgpu_analyze_set_mode(self.h, self.MODES[mode]))
+        if mode == "monitored" or (tolerance, sentinels) != (1e-4, 16):
+            self.set_monitor(tolerance, sentinels)
+        self.set_mode(mode)
+
+    def set_mode(self, mode: str):
+        """switches the evaluation mode; "monitored" (also when already set) re-arms the monitor"""
+        self.ctx.check(self.ctx.lib.amtgpu_analyze_set_mode(self.h, self.MODES[mode]))
+
+    def set_monitor(self, tolerance: float = 1e-4, sentinels: int = 16):
+        """the monitored mode's tolerance on |linear - exact| and sentinel frames per batch, from the next batch on"""
+        self.ctx.check(self.ctx.lib.amtgpu_analyze_set_monitor(self.h, float(tolerance), int(sentinels)))
+
+    def monitor_stats(self):
+        """since the monitor was armed: {"max_abs": largest |linear - exact| compared, "frames_checked", "downgraded": bool} (synchronises)"""
+        m, n, d = C.c_float(), C.c_int64(), C.c_int()
+        self.ctx.check(self.ctx.lib.amtgpu_analyze_monitor_stats(self.h, C.byref(m), C.byref(n), C.byref(d)))
+        return {"max_abs": m.value, "frames_checked": n.value, "downgraded": bool(d.value)}
 
     def last_refined(self):
         return self.ctx.lib.amtgpu_analyze_last_refined(self.h)

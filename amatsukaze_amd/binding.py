@@ -104,6 +104,8 @@ SIGNATURES = {
     "amtgpu_analyze_last_refined": (c_i, [c_p]),
     "amtgpu_analyze_set_fixup_queue": (c_i, [c_p, c_i]),
     "amtgpu_analyze_error_bound": (c_f, [c_p, c_i, c_i]),
+    "amtgpu_analyze_set_monitor": (c_i, [c_p, c_f, c_i]),
+    "amtgpu_analyze_monitor_stats": (c_i, [c_p, c_p, c_p, c_p]),
     "amtgpu_erase_create": (c_p, [c_p, c_s, c_s, c_i, c_i]),
     "amtgpu_erase_create_from_logo": (c_p, [c_p, c_p, c_s, c_i, c_i]),
     "amtgpu_erase_destroy": (None, [c_p]),

@@ -6,6 +6,7 @@
 #include <link.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -553,16 +554,71 @@ struct AmtGpuAnalyze {
     int mode = AMTGPU_ANALYZE_EXACT;
     DevBuf<int> dList, dCount;          // decision guard of the linear mode: frames to re-evaluate exactly
     DevBuf<uint8_t> dForce;             // ... and the frames that carry samples above maxv (9..15-bit clips in 16-bit containers)
+    // sentinel monitor (AMTGPU_ANALYZE_LINEAR_MONITORED)
+    float mon_tol = 1e-4f;
+    int mon_sentinels = 16;
+    DevBuf<MonitorState> dMon;          // persistent: max |linear - exact|, tripped, frames compared (the source of truth)
+    DevBuf<int> dGate;                  // [2] per batch: frames of the gated exact pass (0 or nframes), workgroups that tripped
+    DevBuf<int> dIota;                  // identity list of the gated pass
+    DevBuf<float> dSide;                // [sentinels][33] linear records of the sentinels
+    DevBuf<uint8_t> dSideForced;
+    int* hMonFlag = nullptr;            // pinned, device-written: == mon_epoch once a batch of this arming has run downgraded on the device
+    int* dMonFlag = nullptr;            // ... its device view
+    int mon_epoch = 1;                  // bumped by every re-arm: a flag stored by a batch of an earlier arming does not count
+    bool mon_host_downgraded = false;   // the host has seen the flag: later batches go to EvalEngine::run() directly
+    int last_all_exact = 0;             // frames of the latest batch that run() evaluated (monitored mode after a downgrade), else 0
+    ~AmtGpuAnalyze() { if (hMonFlag) (void)hipHostFree(hMonFlag); }
 };
+
+static void monitor_rearm(AmtGpuAnalyze* an)
+{
+    an->ctx->bind();
+    if (an->dMon.size() < 1) an->dMon.alloc(1);
+    AMT_HIP(hipMemsetAsync(an->dMon.get(), 0, sizeof(MonitorState), an->ctx->stream));
+    if (!an->hMonFlag) {
+        AMT_HIP(hipHostMalloc((void**)&an->hMonFlag, sizeof(int), hipHostMallocCoherent));
+        *an->hMonFlag = 0;
+        void* d = nullptr;
+        AMT_HIP(hipHostGetDevicePointer(&d, an->hMonFlag, 0));
+        an->dMonFlag = (int*)d;
+    }
+    ++an->mon_epoch;
+    an->mon_host_downgraded = false;
+    an->last_all_exact = 0;
+}
+
+// the monitor's device state, after the stream has drained (synchronises)
+static MonitorState monitor_read(AmtGpuAnalyze* an)
+{
+    MonitorState m{};
+    if (an->dMon.size() < 1) return m;
+    an->ctx->bind();
+    download_via_pinned(an->ctx, &m, an->dMon.get(), sizeof m);
+    return m;
+}
 
 // one batch in the selected mode.  Linear mode: all fades from one window evaluation of s and of bg, then the decision guard --
 // frames whose argmin over the fades of p, t or b is not safe against the evaluation's error bound are listed on the device and
 // re-evaluated by the exact kernel in the same stream (no host round trip)
+// Monitored mode: the same, and K sentinel frames ride in the guard's listed launch; their linear records (saved by the mark kernel) are
+// compared with the exact ones on the device, and a failed comparison -- in this batch or any earlier one -- re-evaluates the whole batch
+// exactly in a gated launch that reads its frame count from the device.  The host never waits: a downgrade it has seen (the device-written
+// flag) only saves the linear work of later batches.
 static void analyze_run(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride, int pitch, int bits, int nframes, float* dout)
 {
     if (an->mode == AMTGPU_ANALYZE_EXACT) {
         an->engine->run(dY, frame_stride, pitch, bits, nframes, dout);
         return;
+    }
+    const bool monitored = an->mode == AMTGPU_ANALYZE_LINEAR_MONITORED;
+    if (monitored) {
+        if (!an->mon_host_downgraded && *(volatile int*)an->hMonFlag == an->mon_epoch) an->mon_host_downgraded = true;
+        if (an->mon_host_downgraded) {
+            an->engine->run(dY, frame_stride, pitch, bits, nframes, dout);
+            an->last_all_exact = std::max(nframes, 0);
+            return;
+        }
+        an->last_all_exact = 0;
     }
     if (nframes <= 0) return;
     an->ctx->bind();
@@ -587,10 +643,30 @@ static void analyze_run(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride,
     if (!guarded) return;
     float eps[3];
     for (int k = 0; k < 3; ++k) eps[k] = 2.0f * an->engine->linear_error_bound(k, bits);
+    SentinelArgs sent;
+    if (monitored) {
+        sent.nsent = std::min(an->mon_sentinels, nframes);
+        if (an->dSide.size() < (size_t)sent.nsent * AMTGPU_ANALYZE_FLOATS) an->dSide.alloc((size_t)sent.nsent * AMTGPU_ANALYZE_FLOATS);
+        if (an->dSideForced.size() < (size_t)sent.nsent) an->dSideForced.alloc(sent.nsent);
+        if (an->dGate.size() < 2) an->dGate.alloc(2);
+        if (an->dIota.size() < (size_t)nframes) {
+            an->dIota.alloc(nframes);
+            AMT_HIP(launch_analysis_iota(an->ctx->stream, an->dIota.get(), nframes));
+        }
+        sent.side = an->dSide.get(); sent.side_forced = an->dSideForced.get(); sent.gate = an->dGate.get();
+    }
     const int sp = an->ctx->prof_begin("analysis_mark_kernel");
-    AMT_HIP(launch_analysis_mark(an->ctx->stream, dout, AMTGPU_ANALYZE_FLOATS, nframes, 3, AMTGPU_NUM_FADE, eps, an->dList.get(), an->dCount.get(), force));
+    AMT_HIP(launch_analysis_mark(an->ctx->stream, dout, AMTGPU_ANALYZE_FLOATS, nframes, 3, AMTGPU_NUM_FADE, eps, an->dList.get(), an->dCount.get(), force,
+                                 sent));
     an->ctx->prof_end(sp);
     an->engine->run_listed(dY, frame_stride, pitch, bits, nframes, an->dList.get(), an->dCount.get(), dout);
+    if (!monitored) return;
+    const int spc = an->ctx->prof_begin("analysis_sentinel_check_kernel");
+    AMT_HIP(launch_analysis_sentinel_check(an->ctx->stream, dout, AMTGPU_ANALYZE_FLOATS, nframes, sent, an->mon_tol, an->dMon.get(), an->dMonFlag,
+                                           an->mon_epoch));
+    an->ctx->prof_end(spc);
+    // every frame again, exactly, when the check failed (gate[0] = nframes); otherwise a launch whose workgroups find nothing to do
+    an->engine->run_listed(dY, frame_stride, pitch, bits, nframes, an->dIota.get(), an->dGate.get(), dout, an->engine->exact_group_frames(nframes), 0);
 }
 
 static AmtGpuAnalyze* analyze_new(AmtGpuContext* c, LogoPlanes logo, float maskratio)
@@ -649,10 +725,34 @@ int amtgpu_analyze_batch(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride
 int amtgpu_analyze_set_mode(AmtGpuAnalyze* an, int mode)
 {
     return guard(an->ctx, [&] {
-        if (mode != AMTGPU_ANALYZE_EXACT && mode != AMTGPU_ANALYZE_LINEAR_GUARDED && mode != AMTGPU_ANALYZE_LINEAR_UNGUARDED)
+        if (mode != AMTGPU_ANALYZE_EXACT && mode != AMTGPU_ANALYZE_LINEAR_GUARDED && mode != AMTGPU_ANALYZE_LINEAR_UNGUARDED &&
+            mode != AMTGPU_ANALYZE_LINEAR_MONITORED)
             throw std::runtime_error("unknown analysis mode");
         if (mode != AMTGPU_ANALYZE_EXACT) (void)an->engine->linear_error_bound(0, 8);   // builds the tables; throws for logos the kernel does not take (wider than 256)
+        if (mode == AMTGPU_ANALYZE_LINEAR_MONITORED) monitor_rearm(an);
         an->mode = mode;
+    });
+}
+
+int amtgpu_analyze_set_monitor(AmtGpuAnalyze* an, float tolerance, int sentinels)
+{
+    return guard(an->ctx, [&] {
+        if (!std::isfinite(tolerance) || tolerance < 0.0f) throw std::runtime_error("monitor: tolerance must be finite and >= 0");
+        if (sentinels < 1) throw std::runtime_error("monitor: sentinels must be >= 1");
+        an->mon_tol = tolerance;
+        an->mon_sentinels = sentinels;
+    });
+}
+
+int amtgpu_analyze_monitor_stats(AmtGpuAnalyze* an, float* max_abs, int64_t* frames_checked, int* downgraded)
+{
+    return guard(an->ctx, [&] {
+        const MonitorState m = monitor_read(an);
+        float v;
+        std::memcpy(&v, &m.max_abs_bits, sizeof v);
+        if (max_abs) *max_abs = v;
+        if (frames_checked) *frames_checked = (int64_t)m.frames_checked;
+        if (downgraded) *downgraded = m.tripped ? 1 : 0;
     });
 }
 
@@ -668,6 +768,16 @@ int amtgpu_analyze_last_refined(AmtGpuAnalyze* an)
 {
     int n = -1;
     guard(an->ctx, [&] {
+        if (an->mode == AMTGPU_ANALYZE_LINEAR_MONITORED) {
+            // frames whose records came from the exact kernel: the listed ones (guard + sentinels), or all of a gated / downgraded batch
+            if (an->last_all_exact > 0 || an->dCount.size() < 1 || an->dGate.size() < 2) { n = an->last_all_exact; return; }
+            an->ctx->bind();
+            int g[2] = {0, 0};
+            download_via_pinned(an->ctx, g, an->dGate.get(), sizeof g);
+            download_via_pinned(an->ctx, &n, an->dCount.get(), sizeof(int));
+            n = std::max(n, g[0]);
+            return;
+        }
         if (an->mode != AMTGPU_ANALYZE_LINEAR_GUARDED || an->dCount.size() < 1) { n = 0; return; }
         an->ctx->bind();
         download_via_pinned(an->ctx, &n, an->dCount.get(), sizeof(int));
@@ -688,6 +798,7 @@ float amtgpu_analyze_error_bound(AmtGpuAnalyze* an, int group, int bits)
     guard(an->ctx, [&] {
         if (group < 0 || group > 2 || bits < 8 || bits > 16) throw std::runtime_error("bad group / bits");
         e = an->mode == AMTGPU_ANALYZE_EXACT ? 0.0f : an->engine->linear_error_bound(group, bits);
+        if (an->mode == AMTGPU_ANALYZE_LINEAR_MONITORED && monitor_read(an).tripped) e = 0.0f;      // downgraded: every record is exact
     });
     return e;
 }

@@ -188,8 +188,12 @@ public:
     float linear_error_bound(int logo, int bits) const;
     // exact re-evaluation of the frames listed on the device: batch slot j < *dcount reads source frame dlist[j] and its results
     // go to record dlist[j] of dout (scatter).  max_frames bounds *dcount.  async
+    // G = frames per workgroup, fade_chunk = fades per workgroup (0: all): the defaults suit a handful of frames; a whole batch (the
+    // monitored mode's gated re-evaluation) takes run()'s G and fade_chunk 0
     void run_listed(const void* dY, int64_t frame_stride_bytes, int pitch, int bits, int max_frames, const int* dlist, const int* dcount,
-                    float* dout);
+                    float* dout, int G = 1, int fade_chunk = -1);
+    // frames per workgroup run() takes for a batch of nframes
+    int exact_group_frames(int nframes) const;
     int num_fades() const { return (int)fades_.size(); }
     int num_logos() const { return (int)specs_.size(); }
     const EvalLogoSpec& spec(int i) const { return specs_[i]; }
@@ -255,8 +259,34 @@ hipError_t launch_logo_eval_linear(hipStream_t st, int bits, const EvalLogoDev* 
 hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
                                  const void* dY, const int* dframe_map, long long frame_stride_elems, int pitch,
                                  int nframes, int G, float* dout, int out_frame_stride, int take_abs);
+// Sentinel monitor of AMTGPU_ANALYZE_LINEAR_MONITORED: persistent per-analyzer device state.  max_abs_bits: the largest |linear - exact| over
+// every compared score as float bits (non-negative floats order like unsigned ints; NaN counts as +inf); tripped: a comparison failed (sticky
+// until re-armed); frames_checked: sentinel frames compared; batches_tripped: batches in which a comparison failed
+struct MonitorState {
+    unsigned max_abs_bits;
+    int tripped;
+    unsigned long long frames_checked;
+    unsigned batches_tripped;
+    unsigned pad_;
+};
+// Sentinel arguments of the mark kernel (nsent = 0: none, the guarded mode).  The sentinels of a batch of nframes frames are
+// s_j = floor(j (nframes - 1) / (nsent - 1)), j < nsent (nsent = 1: frame 0); nsent <= nframes.  side: [nsent][stride] copy of their
+// linear records; side_forced: [nsent] their force byte; gate: [2] per-batch words the mark kernel zeroes (frames of the gated exact pass,
+// workgroups that tripped) -- analysis_sentinel_check_kernel sets them, later launches read them
+struct SentinelArgs {
+    int nsent = 0;
+    float* side = nullptr;
+    uint8_t* side_forced = nullptr;
+    int* gate = nullptr;
+};
 hipError_t launch_analysis_mark(hipStream_t st, const float* drec, int stride, int nframes, int ngroups, int nfades, const float* eps3,
-                                int* dlist, int* dcount, const uint8_t* dforce = nullptr);
+                                int* dlist, int* dcount, const uint8_t* dforce = nullptr, const SentinelArgs& sent = SentinelArgs());
+// compares the sentinels' exact records (rec, after the listed re-evaluation) with their saved linear copies; a failed comparison or an
+// earlier one (state->tripped) sets gate[0] = nframes and stores `epoch` to the host-mapped word `host_flag` (optional)
+hipError_t launch_analysis_sentinel_check(hipStream_t st, const float* drec, int stride, int nframes, const SentinelArgs& sent, float tol,
+                                          MonitorState* dstate, int* host_flag, int epoch);
+// list[i] = i for i < n (the identity list of the gated whole-batch re-evaluation)
+hipError_t launch_analysis_iota(hipStream_t st, int* dlist, int n);
 hipError_t launch_rect_range_flag(hipStream_t st, const void* dY, long long frame_stride_elems, int pitch, int imgx, int imgy, int w, int h, int bits,
                                   int nframes, uint8_t* dflag);
 

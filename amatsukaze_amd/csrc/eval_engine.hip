@@ -209,7 +209,7 @@ void EvalEngine::run(const void* dY, int64_t frame_stride_bytes, int pitch, int 
     if (frame_stride_bytes % es) throw std::runtime_error("frame stride not a multiple of the sample size");
     // frames per workgroup: amortises the per-band tap loads; keep >= ~2k workgroups per launch
     const int nl = (int)specs_.size();
-    int G = group_frames_ > 0 ? group_frames_ : (int)std::max(1LL, std::min(8LL, (long long)nframes * nl / 2048));
+    int G = exact_group_frames(nframes);
     const int nf_all = (int)fades_.size();
     if (pair_eligible() && pair_addressable(pitch * es)) {
         // fades {0, 1}: the window of s and the window of bg are the two blends themselves
@@ -230,6 +230,12 @@ void EvalEngine::run(const void* dY, int64_t frame_stride_bytes, int pitch, int 
                                        plane_cap_));
         ctx_->prof_end(sp);
     }
+}
+
+int EvalEngine::exact_group_frames(int nframes) const
+{
+    const int nl = (int)specs_.size();
+    return group_frames_ > 0 ? group_frames_ : (int)std::max(1LL, std::min(8LL, (long long)nframes * nl / 2048));
 }
 
 // The pair kernel evaluates fade 0 on s and fade 1 on bg = a*s + b*maxv directly.  That equals the reference's blend
@@ -471,9 +477,10 @@ void EvalEngine::run_linear(const void* dY, int64_t frame_stride_bytes, int pitc
 #define AMT_LISTED_FADE_CHUNK 1      /* fades per workgroup of the listed re-evaluation (0: all of them, round 3's form) */
 #endif
 void EvalEngine::run_listed(const void* dY, int64_t frame_stride_bytes, int pitch, int bits, int max_frames, const int* dlist,
-                            const int* dcount, float* dout)
+                            const int* dcount, float* dout, int G, int fade_chunk)
 {
     if (max_frames <= 0 || specs_.empty()) return;
+    if (fade_chunk < 0) fade_chunk = AMT_LISTED_FADE_CHUNK;
     ctx_->bind();
     const int es = bits <= 8 ? 1 : 2;
     if (frame_stride_bytes % es) throw std::runtime_error("frame stride not a multiple of the sample size");
@@ -481,11 +488,12 @@ void EvalEngine::run_listed(const void* dY, int64_t frame_stride_bytes, int pitc
     const int nf_all = (int)fades_.size();
     for (int f0 = 0; f0 < nf_all; f0 += kEvalMaxFades) {
         const int nf = std::min(kEvalMaxFades, nf_all - f0);
-        const int G = 1;      // a handful of frames is expected: one per workgroup, so that the pass lasts one frame's walk over the bands
-        const int sp = ctx_->prof_begin((prof_name_ + "_refine").c_str());
+        // (by default a handful of frames is expected: one per workgroup, so that the pass lasts one frame's walk over the bands)
+        const int g = std::max(1, std::min(G, kEvalThreads / nf));
+        const int sp = ctx_->prof_begin((prof_name_ + (G > 1 || fade_chunk != AMT_LISTED_FADE_CHUNK ? "_gated" : "_refine")).c_str());
         AMT_HIP(launch_logo_eval_fused(ctx_->stream, bits, d_logos_.get(), nl, d_bands_.get(), d_fades_.get(), nf, f0, dY, dlist,
-                                       frame_stride_bytes / es, pitch, max_frames, G, dout, out_frame_stride_, take_abs_ ? 1 : 0,
-                                       plane_cap_, dcount, 1, AMT_LISTED_FADE_CHUNK));
+                                       frame_stride_bytes / es, pitch, max_frames, g, dout, out_frame_stride_, take_abs_ ? 1 : 0,
+                                       plane_cap_, dcount, 1, fade_chunk));
         ctx_->prof_end(sp);
     }
 }

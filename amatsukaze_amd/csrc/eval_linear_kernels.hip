@@ -745,12 +745,25 @@ hipError_t launch_logo_eval_linear(hipStream_t st, int bits, const EvalLogoDev* 
 // frames where it does not (ties included, NaN included) are listed for exact re-evaluation.
 // rec: [nframes][stride] with the groups of nfades floats at offsets k*nfades; eps_k = guard margin of group k.
 // ------------------------------------------------------------------------------------------------------------------------
+// Sentinel monitor (AMTGPU_ANALYZE_LINEAR_MONITORED).  The sentinels of a batch are s_j = floor(j (N - 1) / (K - 1)), j < K <= N (K = 1:
+// frame 0); they are distinct and increasing, so frame n is one exactly when the smallest j with s_j >= n, ceil(n (K - 1) / (N - 1)), has
+// s_j == n.  Returns that j, or -1.
+__device__ __forceinline__ int sentinel_slot(int n, int K, int N)
+{
+    if (K <= 0) return -1;
+    if (K == 1) return n == 0 ? 0 : -1;
+    const long long d = N - 1, j = ((long long)n * (K - 1) + d - 1) / d;
+    return j < K && j * d / (K - 1) == n ? (int)j : -1;
+}
+
 __global__ __launch_bounds__(256)
 void analysis_mark_kernel(const float* __restrict__ rec, int stride, int nframes, int ngroups, int nfades, float eps0, float eps1, float eps2,
-                          int* __restrict__ list, int* __restrict__ count, const uint8_t* __restrict__ force)
+                          int* __restrict__ list, int* __restrict__ count, const uint8_t* __restrict__ force, int nsent,
+                          float* __restrict__ side, uint8_t* __restrict__ side_forced, int* __restrict__ gate)
 {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= nframes) return;
+    if (gate && n == 0) { gate[0] = 0; gate[1] = 0; }     // (read by the check kernel and the gated pass: later launches)
     bool amb = force != nullptr && force[n] != 0;          // frames the error bound does not cover (out-of-range samples): always exact
     for (int k = 0; k < ngroups; ++k) {
         const float eps = k == 0 ? eps0 : (k == 1 ? eps1 : eps2);
@@ -765,17 +778,96 @@ void analysis_mark_kernel(const float* __restrict__ rec, int stride, int nframes
         }
         amb |= bad || !(lo2 - lo > eps);
     }
+    // a sentinel keeps its linear record (before the listed re-evaluation overwrites it) and is listed with the guard's frames -- once
+    const int j = sentinel_slot(n, nsent, nframes);
+    if (j >= 0) {
+        const float* p = rec + (long long)n * stride;
+        float* q = side + (long long)j * stride;
+        for (int i = 0; i < ngroups * nfades; ++i) q[i] = p[i];
+        side_forced[j] = force != nullptr && force[n] != 0 ? 1 : 0;
+        amb = true;
+    }
     if (amb) list[atomicAdd(count, 1)] = n;
 }
 
 hipError_t launch_analysis_mark(hipStream_t st, const float* drec, int stride, int nframes, int ngroups, int nfades, const float* eps3,
-                                int* dlist, int* dcount, const uint8_t* dforce)
+                                int* dlist, int* dcount, const uint8_t* dforce, const SentinelArgs& sent)
 {
     if (nframes <= 0) return hipSuccess;
+    if (sent.nsent < 0 || sent.nsent > nframes || (sent.nsent > 0 && (!sent.side || !sent.side_forced || !sent.gate))) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(dcount, 0, sizeof(int), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(analysis_mark_kernel, dim3((unsigned)((nframes + 255) / 256)), dim3(256), 0, st, drec, stride, nframes, ngroups, nfades,
-                       eps3[0], eps3[1], eps3[2], dlist, dcount, dforce);
+                       eps3[0], eps3[1], eps3[2], dlist, dcount, dforce, sent.nsent, sent.side, sent.side_forced, sent.gate);
+    return hipGetLastError();
+}
+
+// One thread per sentinel: its 33 scores, now exact in rec, against the linear copy the mark kernel saved.  A score fails when
+// !(|lin - exact| <= tol) (NaN against a number fails; NaN against NaN, and equal infinities, are equal).  Forced frames (the linear kernel
+// did not vouch for them) are not compared.  Per workgroup: one atomicMax of the largest difference's bits, one add of the frames compared;
+// a workgroup that failed, or that finds the analyzer already tripped by an earlier batch, raises gate[0] to nframes -- read only by the
+// launches that follow (the gated re-evaluation), never by another workgroup of this one.
+__global__ __launch_bounds__(256)
+void analysis_sentinel_check_kernel(const float* __restrict__ rec, int stride, int nvals, int nframes, int nsent,
+                                    const float* __restrict__ side, const uint8_t* __restrict__ side_forced, float tol,
+                                    MonitorState* __restrict__ state, int* __restrict__ gate, int* __restrict__ host_flag, int epoch)
+{
+    __shared__ unsigned wg_max;
+    if (threadIdx.x == 0) wg_max = 0u;
+    __syncthreads();
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    bool trip = false, checked = false;
+    float dmax = 0.0f;
+    if (j < nsent && side_forced[j] == 0) {
+        const int n = nsent == 1 ? 0 : (int)((long long)j * (nframes - 1) / (nsent - 1));
+        const float* e = rec + (long long)n * stride;
+        const float* l = side + (long long)j * stride;
+        for (int i = 0; i < nvals; ++i) {
+            const float a = l[i], b = e[i];
+            const float d = (a == b || (a != a && b != b)) ? 0.0f : fabsf(a - b);
+            trip |= !(d <= tol);
+            dmax = fmaxf(dmax, d == d ? d : INFINITY);
+        }
+        checked = true;
+    }
+    if (dmax > 0.0f) atomicMax(&wg_max, __float_as_uint(dmax));
+    const int any_trip = __syncthreads_or(trip);
+    const int nchecked = __syncthreads_count(checked);
+    if (threadIdx.x == 0) {
+        if (wg_max) atomicMax(&state->max_abs_bits, wg_max);
+        if (nchecked) atomicAdd(&state->frames_checked, (unsigned long long)nchecked);
+        if (any_trip) {
+            state->tripped = 1;
+            if (atomicAdd(&gate[1], 1) == 0) atomicAdd(&state->batches_tripped, 1u);
+        }
+        if (any_trip || state->tripped) {
+            atomicMax(&gate[0], nframes);
+            if (host_flag) *(volatile int*)host_flag = epoch;
+        }
+    }
+}
+
+hipError_t launch_analysis_sentinel_check(hipStream_t st, const float* drec, int stride, int nframes, const SentinelArgs& sent, float tol,
+                                          MonitorState* dstate, int* host_flag, int epoch)
+{
+    if (nframes <= 0 || sent.nsent <= 0) return hipSuccess;
+    if (sent.nsent > nframes || !sent.side || !sent.side_forced || !sent.gate || !dstate || stride < 33) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(analysis_sentinel_check_kernel, dim3((unsigned)((sent.nsent + 255) / 256)), dim3(256), 0, st, drec, stride, 33, nframes,
+                       sent.nsent, sent.side, sent.side_forced, tol, dstate, sent.gate, host_flag, epoch);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256)
+void analysis_iota_kernel(int* __restrict__ list, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) list[i] = i;
+}
+
+hipError_t launch_analysis_iota(hipStream_t st, int* dlist, int n)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(analysis_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dlist, n);
     return hipGetLastError();
 }
 

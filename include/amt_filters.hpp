@@ -160,7 +160,8 @@ class AMTAnalyzeLogo : public GenericVideoFilter {
     }
 
 public:
-    /* analysisMode: AMTGPU_ANALYZE_EXACT (the reference's records bit for bit) or AMTGPU_ANALYZE_LINEAR_GUARDED */
+    /* analysisMode: AMTGPU_ANALYZE_EXACT (the reference's records bit for bit), AMTGPU_ANALYZE_LINEAR_GUARDED or
+     * AMTGPU_ANALYZE_LINEAR_MONITORED (the guarded mode with exact sentinel frames compared on the device; monitorStats()) */
     AMTAnalyzeLogo(PClip clip, const std::string& logoPath, float maskratio, IScriptEnvironment* env, PContext ctx = PContext(),
                    int framesPerLaunch = 32, int analysisMode = AMTGPU_ANALYZE_EXACT)
         : GenericVideoFilter(clip), ctx_(ctx ? ctx : std::make_shared<Context>()), srcvi_(vi), block_(std::max(1, framesPerLaunch)),
@@ -182,6 +183,17 @@ public:
         vi.num_frames = nblocks(vi.num_frames, 8);
     }
     ~AMTAnalyzeLogo() override { if (an_) amtgpu_analyze_destroy(an_); }
+
+    /* AMTGPU_ANALYZE_LINEAR_MONITORED: the largest |linear - exact| the monitor compared, sentinel frames compared, whether it has
+     * downgraded to exact evaluation (amtgpu_analyze_monitor_stats; synchronises).  false on error, message on the context */
+    bool monitorStats(float* maxAbs, int64_t* framesChecked, bool* downgraded)
+    {
+        std::lock_guard<std::mutex> lock(mu_);
+        int d = 0;
+        if (!amtgpu_analyze_monitor_stats(an_, maxAbs, framesChecked, &d)) return false;
+        if (downgraded) *downgraded = d != 0;
+        return true;
+    }
 
     PVideoFrame GetFrame(int n, IScriptEnvironment* env) override
     {

@@ -35,7 +35,9 @@ extern "C" {
                                    *    num_candidates > num_logos; additions: amtgpu_logoframe_dump_result, amtgpu_host_set_parallelism
                                    * 5: amtgpu_logoframe_decide_host is back to 1 / 0 like every other entry point (a too-small text buffer
                                    *    is 0 with *text_len > cap: `if (!call) fail;` written against ABI <= 3 is right again); additions:
-                                   *    amtgpu_analyze_set_fixup_queue, amtgpu_erase_batch_dfades_to */
+                                   *    amtgpu_analyze_set_fixup_queue, amtgpu_erase_batch_dfades_to
+                                   * 5 (later additions): AMTGPU_ANALYZE_LINEAR_MONITORED, amtgpu_analyze_set_monitor,
+                                   *    amtgpu_analyze_monitor_stats */
 #define AMTGPU_NUM_FADE 11            /* LogoAnalyzeFrame p/t/b[11]  (LogoScan.hpp:1100-1103) */
 #define AMTGPU_ANALYZE_FLOATS 33      /* floats per source frame in an analysis record */
 
@@ -277,15 +279,33 @@ int  amtgpu_analyze_batch_host(AmtGpuAnalyze* an, const void* dY, int64_t frame_
 #define AMTGPU_ANALYZE_EXACT 0
 #define AMTGPU_ANALYZE_LINEAR_GUARDED 1
 #define AMTGPU_ANALYZE_LINEAR_UNGUARDED 2   /* the linear evaluation alone, without the argmin guard: for accuracy tests and profiling */
+/*   AMTGPU_ANALYZE_LINEAR_MONITORED: the guarded linear mode, and in every batch K sentinel frames are evaluated exactly as well (frames
+ *     floor(j (nframes - 1) / (K' - 1)), j < K' = min(K, nframes); K' = 1: frame 0 -- the first and the last frame of a batch whenever
+ *     K' > 1).  Their 33 linear scores are compared with the exact ones on the device; a score with !(|linear - exact| <= tolerance) trips
+ *     the monitor (NaN against a number trips, NaN against NaN is equal; frames with samples above maxv are exact anyway and not compared).
+ *     A batch that passes hands out the exact records on the sentinels and mode 1's everywhere else; a batch that trips is re-evaluated
+ *     exactly in the same stream (records = the exact mode's), and the analyzer stays exact from then on ("downgraded") until
+ *     amtgpu_analyze_set_mode(an, AMTGPU_ANALYZE_LINEAR_MONITORED) re-arms it.  The monitor SAMPLES: it vouches for every compared frame
+ *     and, once a comparison has failed, for every later record; it proves nothing about frames it did not compare.  async like mode 1. */
+#define AMTGPU_ANALYZE_LINEAR_MONITORED 3
+/* (setting AMTGPU_ANALYZE_LINEAR_MONITORED, also when it is already set, re-arms the monitor: no downgrade, statistics zeroed) */
 int   amtgpu_analyze_set_mode(AmtGpuAnalyze* an, int mode);
-/* frames of the most recent batch that the guard re-evaluated exactly (synchronises); 0 in exact mode, -1 on error */
+/* the monitor's absolute tolerance on the normalised scores (finite, >= 0; 0: any difference trips; default 1e-4) and sentinels per batch
+ * (>= 1; default 16); valid in any mode, used from the next monitored batch on */
+int   amtgpu_analyze_set_monitor(AmtGpuAnalyze* an, float tolerance, int sentinels);
+/* since the monitor was last armed: the largest |linear - exact| of a compared score (+inf for NaN against a number), sentinel frames
+ * compared, whether it has downgraded.  Synchronises; any pointer may be null */
+int   amtgpu_analyze_monitor_stats(AmtGpuAnalyze* an, float* max_abs, int64_t* frames_checked, int* downgraded);
+/* frames of the most recent batch that the guard re-evaluated exactly (synchronises); 0 in exact mode, -1 on error.  Monitored mode: the
+ * frames whose records came from the exact kernel -- the guard's and the sentinels, or all of a batch that tripped or ran downgraded */
 int   amtgpu_analyze_last_refined(AmtGpuAnalyze* an);
 /* Linear modes: (pixel, frame, fade) pairs whose window mean lies within the evaluation's error bound of a bin edge (LogoScan.hpp:304 is
  * discontinuous there) are listed per wave and settled exactly when the workgroup has finished; a workgroup whose list overflows leaves
  * its frames to the exact kernel (they are counted by amtgpu_analyze_last_refined).  entries = pairs a wave can list, 16 .. 640,
  * default 256; fewer frames share a workgroup as the list grows (LDS).  A tuning knob: results do not depend on it. */
 int   amtgpu_analyze_set_fixup_queue(AmtGpuAnalyze* an, int entries);
-/* the linear mode's bound on |score - reference score| for group 0 = p, 1 = t, 2 = b at the given bit depth; 0 in exact mode */
+/* the linear mode's bound on |score - reference score| for group 0 = p, 1 = t, 2 = b at the given bit depth; 0 in exact mode and in a
+ * downgraded monitored mode (which synchronises to find out) */
 float amtgpu_analyze_error_bound(AmtGpuAnalyze* an, int group, int bits);
 
 /* ---- encode-time erase: replaces logo::AMTEraseLogo ("AMTEraseLogo" "ccs[logof]s[mode]i[maxfade]i",
