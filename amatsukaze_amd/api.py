@@ -548,6 +548,123 @@ def ScanLogoFile(ctx: Context, srcpath, serviceid, workfile, dstpath, imgx, imgy
                                              w, h, thy, numMaxFrames, cbf))
 
 
+@dataclass
+class LogoCandidate:
+    """AmtGpuLogoRect: a rectangle for ScanLogo (imgx, imgy, w, h: even, inside the frame) and how strongly it was found"""
+    imgx: int
+    imgy: int
+    w: int
+    h: int
+    score: float
+    coherence: float
+    edge_pixels: int
+
+    @classmethod
+    def _of(cls, r):
+        return cls(r.imgx, r.imgy, r.w, r.h, r.score, r.coherence, r.edge_pixels)
+
+
+def logo_find_params(**params):
+    """AmtGpuLogoFindParams: the library's defaults with the given fields replaced (min_coherence, min_edge, join, margin, min_w,
+    min_h, max_w_frac, max_h_frac)"""
+    p = binding.LogoFindParams()
+    binding.load().amtgpu_logofind_default_params(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(binding.LogoFindParams._fields_):
+            raise TypeError(f"unknown logo-finder parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def logo_candidates_host(sums, width, height, bits, nframes, cap=64, **params):
+    """amtgpu_logofind_candidates_host: ranked candidates from sums in host memory (2*W*H int64: S1 then SM); no device.
+    Returns (candidates, total) or raises ValueError when the library refuses the arguments."""
+    s = np.ascontiguousarray(sums, np.int64)
+    out = (binding.LogoRect * max(1, cap))()
+    n = C.c_int()
+    p = logo_find_params(**params)
+    if not binding.load().amtgpu_logofind_candidates_host(_p(s), width, height, bits, nframes, C.byref(p), out, cap, C.byref(n)):
+        raise ValueError("amtgpu_logofind_candidates_host refused its arguments")
+    return [LogoCandidate._of(out[i]) for i in range(min(cap, n.value))], n.value
+
+
+class LogoFinder:
+    """Automatic logo detection (self-specified): edge-persistence sums over the Y planes of every frame
+    offered, then ranked candidate rectangles for ScanLogo."""
+
+    def __init__(self, ctx: Context, width, height, bits=8):
+        self.ctx, self.width, self.height, self.bits = ctx, width, height, bits
+        self.h = ctx.lib.amtgpu_logofind_create(ctx.h, width, height, bits)
+        ctx.check(self.h, "LogoFinder")
+
+    def add_device(self, Y, nframes=None):
+        """Y: torch tensor (N, H, pitch) of Y planes in HBM (uint8, or int16 / uint16 above 8 bits).  async"""
+        es = 1 if self.bits <= 8 else 2
+        n = int(Y.shape[0]) if nframes is None else nframes
+        self.ctx.check(self.ctx.lib.amtgpu_logofind_add_batch(self.h, _p(Y), int(Y.stride(0)) * es, int(Y.stride(1)), n))
+
+    def add(self, clip: DeviceClip):
+        self.add_device(clip.Y)
+
+    @property
+    def nframes(self):
+        return int(self.ctx.lib.amtgpu_logofind_nframes(self.h))
+
+    def sums(self):
+        """(S1, SM): int64 arrays of shape (H, W)"""
+        s = np.zeros(2 * self.width * self.height, np.int64)
+        self.ctx.check(self.ctx.lib.amtgpu_logofind_get_sums(self.h, _p(s)))
+        s = s.reshape(2, self.height, self.width)
+        return s[0], s[1]
+
+    def set_sums(self, S1, SM, nframes):
+        s = np.ascontiguousarray(np.concatenate([np.ravel(S1), np.ravel(SM)]), np.int64)
+        if s.size != 2 * self.width * self.height:
+            raise ValueError("set_sums: sums of another frame size")
+        self.ctx.check(self.ctx.lib.amtgpu_logofind_set_sums(self.h, _p(s), nframes))
+
+    def allreduce(self, coll):
+        """frame-sharded detection: every rank's sums (and frame count) summed on every rank (sharding.TorchCollectives)"""
+        self.ctx.check(self.ctx.lib.amtgpu_logofind_allreduce(self.h, coll.ref()))
+
+    def candidates(self, cap=64, **params):
+        """ranked LogoCandidate list (at most cap); parameters as in logo_find_params"""
+        out = (binding.LogoRect * max(1, cap))()
+        n = C.c_int()
+        p = logo_find_params(**params)
+        self.ctx.check(self.ctx.lib.amtgpu_logofind_candidates(self.h, C.byref(p), out, cap, C.byref(n)))
+        return [LogoCandidate._of(out[i]) for i in range(min(cap, n.value))]
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.ctx.lib.amtgpu_logofind_destroy(self.h)
+        except Exception:
+            pass
+
+
+def ScanLogoAuto(ctx: Context, clip: DeviceClip, serviceid, dstpath, thy, numMaxFrames, cb=None, **params):
+    """ScanLogo without a rectangle: detection over the whole clip, then ScanLogo on the best candidate.  Returns (ok, LogoCandidate or
+    None); with no candidate ok is False and the context's message is "no logo found"."""
+    cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
+    found = binding.LogoRect()
+    p = logo_find_params(**params)
+    ok = ctx.lib.amtgpu_scanlogo_auto(ctx.h, _p(clip.Y), _p(clip.U), _p(clip.V), clip.strideY, clip.strideUV, clip.pitchY, clip.pitchUV,
+                                      clip.width, clip.height, clip.num_frames, serviceid, str(dstpath).encode() if dstpath else None, thy,
+                                      numMaxFrames, cbf, C.byref(p), C.byref(found))
+    return bool(ok), (LogoCandidate._of(found) if found.w > 0 else None)
+
+
+def ScanLogoFileAuto(ctx: Context, srcpath, serviceid, workfile, dstpath, thy, numMaxFrames, cb=None, **params):
+    """ScanLogoFile without a rectangle (the raw 'AMTR' clip is read twice); returns (ok, LogoCandidate or None)"""
+    cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
+    found = binding.LogoRect()
+    p = logo_find_params(**params)
+    ok = ctx.lib.amtgpu_scanlogo_file_auto(ctx.h, str(srcpath).encode(), serviceid, str(workfile).encode(), str(dstpath).encode(), thy,
+                                           numMaxFrames, cbf, C.byref(p), C.byref(found))
+    return bool(ok), (LogoCandidate._of(found) if found.w > 0 else None)
+
+
 class FrameStats:
     """Self-specified whole-frame field-difference / combing metrics."""
 

@@ -22,6 +22,18 @@ class Scatter(C.Structure):
     _fields_ = [("hdst", c_p), ("dst_stride", c_i64), ("src_offset", c_u64), ("chunk_bytes", c_u64), ("nchunks", c_i)]
 
 
+class LogoFindParams(C.Structure):
+    """AmtGpuLogoFindParams (include/amt_gpu.h)"""
+    _fields_ = [("min_coherence", c_f), ("min_edge", c_f), ("join", c_i), ("margin", c_i), ("min_w", c_i), ("min_h", c_i),
+                ("max_w_frac", c_f), ("max_h_frac", c_f)]
+
+
+class LogoRect(C.Structure):
+    """AmtGpuLogoRect (include/amt_gpu.h)"""
+    _fields_ = [("imgx", c_i), ("imgy", c_i), ("w", c_i), ("h", c_i), ("score", c_f), ("coherence", c_f), ("edge_pixels", c_i),
+                ("reserved", c_i)]
+
+
 class Collectives(C.Structure):
     """AmtGpuCollectives (include/amt_gpu.h)"""
     _fields_ = [("rank", c_i), ("world", c_i), ("allgather", ALLGATHER_CB), ("allreduce_sum_i64", ALLREDUCE_CB), ("user", c_p)]
@@ -141,6 +153,19 @@ SIGNATURES = {
     "amtgpu_kfm_write_durations": (c_i, [c_p, c_p, c_i, c_s, c_p]),
     "amtgpu_kfm_write_timecode": (c_i, [c_p, c_p, c_i, c_i, c_i, c_s, c_p]),
     "amtgpu_cm_write_chapter_exe": (c_i, [c_p, c_i, c_i, c_s]),
+    "amtgpu_logofind_create": (c_p, [c_p, c_i, c_i, c_i]),
+    "amtgpu_logofind_destroy": (None, [c_p]),
+    "amtgpu_logofind_add_batch": (c_i, [c_p, c_p, c_i64, c_i, c_i]),
+    "amtgpu_logofind_nframes": (c_i64, [c_p]),
+    "amtgpu_logofind_get_sums": (c_i, [c_p, c_p]),
+    "amtgpu_logofind_set_sums": (c_i, [c_p, c_p, c_i64]),
+    "amtgpu_logofind_default_params": (None, [c_p]),
+    "amtgpu_logofind_candidates": (c_i, [c_p, c_p, c_p, c_i, c_p]),
+    "amtgpu_logofind_candidates_host": (c_i, [c_p, c_i, c_i, c_i, c_i64, c_p, c_p, c_i, c_p]),
+    "amtgpu_logofind_allreduce": (c_i, [c_p, c_p]),
+    "amtgpu_scanlogo_auto": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_s, c_i, c_i, CB, c_p, c_p]),
+    "amtgpu_scanlogo_auto_sharded": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_s, c_i, c_i, CB, c_p, c_p]),
+    "amtgpu_scanlogo_file_auto": (c_i, [c_p, c_s, c_i, c_s, c_s, c_i, c_i, CB, c_p, c_p]),
 }
 
 _lib = None

@@ -25,11 +25,14 @@ SOURCES = [
     "erase_scan_kernels.hip",
     "stats_kernels.hip",
     "ingest_kernels.hip",
+    "amt_gpu_logofind.hip",
+    "logofind_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",
     "stats_decisions.cpp",
     "amts_file.cpp",
+    "logo_find.cpp",
 ]
 
 # -ffp-contract=off: the reference is built without FMA contraction (MSVC /fp:precise) and its scores

@@ -1,0 +1,256 @@
+// amt_gpu_logofind.hip -- C ABI of the automatic logo finder: the edge-persistence sums on the device (logofind_kernels.hip), their
+// exchange between ranks, and ScanLogo fed with the best candidate (logo_find.cpp ranks them).  Self-specified: DESIGN.md section 6b.
+#include "build_knobs.h"
+#include "../../include/amt_gpu.h"
+
+#include <cstring>
+#include <fstream>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "api_common.hpp"
+
+namespace amt {
+long long logofind_launch_cap(int bits);
+hipError_t launch_logofind(hipStream_t st, int bits, const void* dY, long long frame_stride, int pitch_elems, int W, int H, int nframes,
+                           int num_cus, unsigned long long* dS1, unsigned long long* dSM);
+}
+using namespace amt;
+
+struct AmtGpuLogoFind {
+    AmtGpuContext* ctx;
+    int width, height, bits;
+    int num_cus;
+    int64_t nframes = 0;
+    DevBuf<unsigned long long> dSums;      // S1 [H][W] then SM [H][W]
+};
+
+namespace {
+
+size_t npx(const AmtGpuLogoFind* lf) { return (size_t)lf->width * lf->height; }
+
+AmtGpuLogoFind* logofind_new(AmtGpuContext* c, int width, int height, int bits)
+{
+    if (width < 3 || height < 3 || bits < 8 || bits > 16) throw std::runtime_error("[LogoFind] unsupported frame format (W, H >= 3, bits 8..16)");
+    c->bind();
+    std::unique_ptr<AmtGpuLogoFind> lf(new AmtGpuLogoFind{c, width, height, bits, 0});
+    int dev = 0;
+    AMT_HIP(hipGetDevice(&dev));
+    AMT_HIP(hipDeviceGetAttribute(&lf->num_cus, hipDeviceAttributeMultiprocessorCount, dev));
+    lf->dSums.alloc(2 * npx(lf.get()));
+    AMT_HIP(hipMemsetAsync(lf->dSums.get(), 0, 2 * npx(lf.get()) * sizeof(unsigned long long), c->stream));
+    return lf.release();
+}
+
+void logofind_add(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes)
+{
+    if (nframes < 0) throw std::runtime_error("[LogoFind] negative frame count");
+    if (nframes == 0) return;
+    if (!dY) throw std::runtime_error("[LogoFind] null frame pointer");
+    if (pitch < lf->width || frame_stride < 0) throw std::runtime_error("[LogoFind] pitch below the width or negative frame stride");
+    lf->ctx->bind();
+    const long long cap = logofind_launch_cap(lf->bits);
+    const int sp = lf->ctx->prof_begin("logofind_kernel");
+    for (long long f0 = 0; f0 < nframes; f0 += cap) {
+        const int n = (int)std::min<long long>(cap, nframes - f0);
+        AMT_HIP(launch_logofind(lf->ctx->stream, lf->bits, (const uint8_t*)dY + f0 * frame_stride, frame_stride, pitch, lf->width, lf->height, n,
+                                lf->num_cus, lf->dSums.get(), lf->dSums.get() + npx(lf)));
+    }
+    lf->ctx->prof_end(sp);
+    lf->nframes += nframes;
+}
+
+std::vector<int64_t> logofind_pull(AmtGpuLogoFind* lf)
+{
+    std::vector<int64_t> h(2 * npx(lf));
+    lf->ctx->bind();
+    download_via_pinned(lf->ctx, h.data(), lf->dSums.get(), h.size() * sizeof(int64_t));
+    return h;
+}
+
+void logofind_push(AmtGpuLogoFind* lf, const int64_t* sums, int64_t nframes)
+{
+    lf->ctx->bind();
+    lf->dSums.upload((const unsigned long long*)sums, 2 * npx(lf), lf->ctx->stream);
+    lf->nframes = nframes;
+}
+
+// the best candidate of the current sums, or throws "no logo found"
+AmtGpuLogoRect best_rect(AmtGpuLogoFind* lf, const AmtGpuLogoFindParams* params)
+{
+    const std::vector<int64_t> h = logofind_pull(lf);
+    AmtGpuLogoRect r{};
+    int n = 0;
+    if (!amtgpu_logofind_candidates_host(h.data(), lf->width, lf->height, lf->bits, lf->nframes, params, &r, 1, &n))
+        throw std::runtime_error("[LogoFind] invalid detection parameters");
+    if (n == 0) throw std::runtime_error("no logo found");
+    return r;
+}
+
+// the sums of all ranks on every rank; a rank that failed before the exchange still enters it (with a status word) so that nobody blocks
+void logofind_reduce(AmtGpuLogoFind* lf, const AmtGpuCollectives* coll, std::string local_error)
+{
+    if (!coll || coll->world <= 1) {
+        if (!local_error.empty()) throw std::runtime_error(local_error);
+        return;
+    }
+    if (!coll->allreduce_sum_i64 || coll->rank < 0 || coll->rank >= coll->world) throw std::runtime_error("AmtGpuCollectives incomplete");
+    const size_t n = 2 * npx(lf);
+    std::vector<int64_t> buf(n + 2, 0);
+    if (local_error.empty()) {
+        try {
+            std::vector<int64_t> h = logofind_pull(lf);
+            std::copy(h.begin(), h.end(), buf.begin());
+            buf[n] = lf->nframes;
+        } catch (const std::exception& e) { local_error = e.what(); std::fill(buf.begin(), buf.end(), 0); }
+    }
+    buf[n + 1] = local_error.empty() ? 0 : 1;
+    if (!coll->allreduce_sum_i64(coll->user, buf.data(), (int64_t)buf.size())) throw std::runtime_error("allreduce_sum_i64 failed");
+    if (!local_error.empty()) throw std::runtime_error(local_error);
+    if (buf[n + 1]) throw std::runtime_error("another rank failed; the sharded logo detection was abandoned on every rank");
+    logofind_push(lf, buf.data(), buf[n]);
+}
+
+void zero_found(AmtGpuLogoRect* found) { if (found) std::memset(found, 0, sizeof *found); }
+
+} // namespace
+
+extern "C" {
+
+AmtGpuLogoFind* amtgpu_logofind_create(AmtGpuContext* c, int width, int height, int bits)
+{
+    AmtGpuLogoFind* lf = nullptr;
+    if (!c) return nullptr;
+    guard(c, [&] { lf = logofind_new(c, width, height, bits); });
+    return lf;
+}
+
+void amtgpu_logofind_destroy(AmtGpuLogoFind* lf) { delete lf; }
+
+int amtgpu_logofind_add_batch(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes)
+{
+    if (!lf) return 0;
+    return guard(lf->ctx, [&] { logofind_add(lf, dY, frame_stride, pitch, nframes); });
+}
+
+int64_t amtgpu_logofind_nframes(const AmtGpuLogoFind* lf) { return lf ? lf->nframes : -1; }
+
+int amtgpu_logofind_get_sums(AmtGpuLogoFind* lf, int64_t* sums)
+{
+    if (!lf) return 0;
+    return guard(lf->ctx, [&] {
+        if (!sums) throw std::runtime_error("[LogoFind] null sums pointer");
+        const std::vector<int64_t> h = logofind_pull(lf);
+        std::memcpy(sums, h.data(), h.size() * sizeof(int64_t));
+    });
+}
+
+int amtgpu_logofind_set_sums(AmtGpuLogoFind* lf, const int64_t* sums, int64_t nframes)
+{
+    if (!lf) return 0;
+    return guard(lf->ctx, [&] {
+        if (!sums) throw std::runtime_error("[LogoFind] null sums pointer");
+        if (nframes < 0) throw std::runtime_error("[LogoFind] negative frame count");
+        logofind_push(lf, sums, nframes);
+    });
+}
+
+int amtgpu_logofind_candidates(AmtGpuLogoFind* lf, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* out, int cap, int* ncand)
+{
+    if (!lf) return 0;
+    return guard(lf->ctx, [&] {
+        if (!ncand || cap < 0 || (cap > 0 && !out)) throw std::runtime_error("[LogoFind] bad output arguments");
+        const std::vector<int64_t> h = logofind_pull(lf);
+        if (!amtgpu_logofind_candidates_host(h.data(), lf->width, lf->height, lf->bits, lf->nframes, params, out, cap, ncand))
+            throw std::runtime_error("[LogoFind] invalid detection parameters");
+    });
+}
+
+int amtgpu_logofind_allreduce(AmtGpuLogoFind* lf, const AmtGpuCollectives* coll)
+{
+    if (!lf) return 0;
+    return guard(lf->ctx, [&] {
+        if (!coll) throw std::runtime_error("[LogoFind] null collectives");
+        logofind_reduce(lf, coll, std::string());
+    });
+}
+
+int amtgpu_scanlogo_auto(AmtGpuContext* c, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV, int pitchY,
+                         int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath, int thy, int numMaxFrames,
+                         AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found)
+{
+    if (!c) return 0;
+    zero_found(found);
+    AmtGpuLogoRect r{};
+    const int ok = guard(c, [&] {
+        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, 8));
+        logofind_add(lf.get(), dY, strideY, pitchY, nframes);
+        r = best_rect(lf.get(), params);
+    });
+    if (!ok) return 0;
+    if (found) *found = r;
+    return amtgpu_scanlogo(c, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, nframes, serviceid, dstpath, r.imgx, r.imgy, r.w, r.h,
+                           thy, numMaxFrames, cb);
+}
+
+int amtgpu_scanlogo_auto_sharded(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV, int64_t strideY,
+                                 int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int nframes_local, int serviceid,
+                                 const char* dstpath, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params,
+                                 AmtGpuLogoRect* found)
+{
+    if (!c) return 0;
+    zero_found(found);
+    AmtGpuLogoRect r{};
+    const int ok = guard(c, [&] {
+        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, 8));
+        std::string err;
+        try { logofind_add(lf.get(), dY, strideY, pitchY, nframes_local); } catch (const std::exception& e) { err = e.what(); }
+        logofind_reduce(lf.get(), coll, err);
+        r = best_rect(lf.get(), params);       // identical sums on every rank: the same answer (or the same "no logo found") everywhere
+    });
+    if (!ok) return 0;
+    if (found) *found = r;
+    return amtgpu_scanlogo_sharded(c, coll, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, nframes_local, serviceid, dstpath,
+                                   r.imgx, r.imgy, r.w, r.h, thy, numMaxFrames, cb);
+}
+
+// pass 1 over the raw clip: the Y planes only, chunk by chunk through the pinned upload path; pass 2 is amtgpu_scanlogo_file itself
+int amtgpu_scanlogo_file_auto(AmtGpuContext* c, const char* srcpath, int serviceid, const char* workfile, const char* dstpath, int thy,
+                              int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found)
+{
+    if (!c) return 0;
+    zero_found(found);
+    AmtGpuLogoRect r{};
+    const int ok = guard(c, [&] {
+        if (!srcpath) throw std::runtime_error("null source path");
+        std::ifstream f(srcpath, std::ios::binary);
+        if (!f) throw std::runtime_error(std::string("failed to open file ") + srcpath);
+        int32_t hdr[4];
+        f.read(reinterpret_cast<char*>(hdr), sizeof hdr);
+        if (!f || hdr[0] != 0x52544D41 || hdr[1] <= 0 || hdr[2] <= 0 || hdr[3] < 0 || (hdr[1] & 1) || (hdr[2] & 1))
+            throw std::runtime_error("not a raw AMTR clip (int32 'AMTR', width, height, frames; 8-bit 4:2:0 planes)");
+        const int W = hdr[1], H = hdr[2], N = hdr[3];
+        const size_t ysz = (size_t)W * H, csz = (size_t)(W / 2) * (H / 2), fsz = ysz + 2 * csz;
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>(1024, (256u << 20) / fsz));
+        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, W, H, 8));
+        DevBuf<uint8_t> dChunk(ysz * chunk);
+        std::vector<uint8_t> host(fsz * chunk), planes(ysz * chunk);
+        for (int f0 = 0; f0 < N; f0 += chunk) {
+            const int n = std::min(chunk, N - f0);
+            f.read(reinterpret_cast<char*>(host.data()), (std::streamsize)(fsz * n));
+            if (!f) throw std::runtime_error("raw clip truncated");
+            for (int i = 0; i < n; ++i) std::memcpy(planes.data() + ysz * i, host.data() + fsz * i, ysz);
+            if (!amtgpu_frames_upload(c, dChunk.get(), planes.data(), ysz * n) || !amtgpu_frames_upload_wait(c)) throw std::runtime_error(c->err);
+            logofind_add(lf.get(), dChunk.get(), (int64_t)ysz, W, n);
+            AMT_HIP(hipStreamSynchronize(c->stream));          // the chunk buffer is refilled by the next upload
+            if (cb && !cb(0.f, f0 + n, N, 0)) throw std::runtime_error("Cancel requested");
+        }
+        r = best_rect(lf.get(), params);
+    });
+    if (!ok) return 0;
+    if (found) *found = r;
+    return amtgpu_scanlogo_file(c, srcpath, serviceid, workfile, dstpath, r.imgx, r.imgy, r.w, r.h, thy, numMaxFrames, cb);
+}
+
+} // extern "C"

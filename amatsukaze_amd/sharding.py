@@ -160,3 +160,27 @@ def scan_logo_sharded(ctx, clip_local, serviceid, dstpath, imgx, imgy, w, h, thy
                                          clip_local.num_frames, serviceid, str(dstpath).encode() if dstpath else None, imgx, imgy, w, h,
                                          thy, numMaxFrames, cbf)
     return bool(ok)
+
+
+def find_logo_sharded(ctx, clip_local, coll: TorchCollectives, cap=64, **params):
+    """Automatic logo detection over frame-sharded ranks: each rank adds its own frames, the exact int64 sums (with the frame count)
+    are all-reduced, every rank ranks the same candidates.  Returns (LogoFinder holding the whole clip's sums, candidates)."""
+    from .api import LogoFinder
+    lf = LogoFinder(ctx, clip_local.width, clip_local.height, clip_local.bits)
+    lf.add(clip_local)
+    lf.allreduce(coll)
+    return lf, lf.candidates(cap, **params)
+
+
+def scan_logo_auto_sharded(ctx, clip_local, serviceid, dstpath, thy, numMaxFrames, coll: TorchCollectives, cb=None, **params):
+    """amtgpu_scanlogo_auto_sharded: detection over all ranks' frames, then scan_logo_sharded with the best candidate.  Rank 0 writes
+    dstpath.  Returns (ok, LogoCandidate or None) like api.ScanLogoAuto."""
+    from .api import LogoCandidate, _p, logo_find_params
+    cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
+    found = binding.LogoRect()
+    p = logo_find_params(**params)
+    ok = ctx.lib.amtgpu_scanlogo_auto_sharded(ctx.h, coll.ref(), _p(clip_local.Y), _p(clip_local.U), _p(clip_local.V), clip_local.strideY,
+                                              clip_local.strideUV, clip_local.pitchY, clip_local.pitchUV, clip_local.width, clip_local.height,
+                                              clip_local.num_frames, serviceid, str(dstpath).encode() if dstpath else None, thy, numMaxFrames,
+                                              cbf, C.byref(p), C.byref(found))
+    return bool(ok), (LogoCandidate._of(found) if found.w > 0 else None)

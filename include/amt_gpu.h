@@ -37,7 +37,8 @@ extern "C" {
                                    *    is 0 with *text_len > cap: `if (!call) fail;` written against ABI <= 3 is right again); additions:
                                    *    amtgpu_analyze_set_fixup_queue, amtgpu_erase_batch_dfades_to
                                    * 5 (later additions): AMTGPU_ANALYZE_LINEAR_MONITORED, amtgpu_analyze_set_monitor,
-                                   *    amtgpu_analyze_monitor_stats */
+                                   *    amtgpu_analyze_monitor_stats; automatic logo detection (amtgpu_logofind_*,
+                                   *    amtgpu_scanlogo_auto, _auto_sharded, _file_auto) */
 #define AMTGPU_NUM_FADE 11            /* LogoAnalyzeFrame p/t/b[11]  (LogoScan.hpp:1100-1103) */
 #define AMTGPU_ANALYZE_FLOATS 33      /* floats per source frame in an analysis record */
 
@@ -468,6 +469,67 @@ int  amtgpu_kfm_write_timecode(const uint8_t* cadence, const uint8_t* phase, int
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines; no "mute" lines (audio is out of scope) */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
+
+/* ---- automatic logo detection (self-specified, "parity unpinned": no reference arithmetic).  The reference
+ *      needs a rectangle drawn by hand before ScanLogo (LogoScan.hpp:1083-1098); these entry points find it from the clip.
+ *      Over the Y planes of all frames offered, per pixel: S1 = sum Y, SM = sum (|Y[x+1]-Y[x-1]| + |Y[y+1]-Y[y-1]|) (0 on the outer
+ *      ring), N = frames.  The summed gradient (from S1) against SM gives a coherence in [0, 1] -- static edges such as a logo's add
+ *      up, moving content does not; coherent strong edges are joined into ranked candidate rectangles.  All sums are int64 and
+ *      exact: independent of frame order, batch split and GPU count. ---- */
+typedef struct AmtGpuLogoFind AmtGpuLogoFind;
+typedef struct AmtGpuLogoFindParams {
+    float min_coherence;    /* edge pixel: coherence m / SM at least this (default 0.6) */
+    float min_edge;         /* ... and persistent edge strength m / N at least this, in 8-bit LSB units (default 3) */
+    int   join;             /* dilation radius (pixels, square) that merges the strokes of one logo (default 4) */
+    int   margin;           /* the rectangle is the edge pixels' bounding box grown by this on each side (default 4) */
+    int   min_w, min_h;     /* smallest bounding box kept (default 16 x 16) */
+    float max_w_frac, max_h_frac;   /* largest bounding box kept, as a fraction of the frame (default 0.5 x 0.5) */
+} AmtGpuLogoFindParams;
+/* one candidate: imgx, imgy even, w, h even, inside the frame (the reference's LogoHeader keeps all four even, LogoScan.hpp:69).
+ * score = sum of m / N over its edge pixels (input sample units); coherence = sum m / sum SM over them; ranked by score, descending,
+ * ties by (imgy, imgx) */
+typedef struct AmtGpuLogoRect {
+    int   imgx, imgy, w, h;
+    float score, coherence;
+    int   edge_pixels, reserved;
+} AmtGpuLogoRect;
+/* width, height >= 3, bits 8..16.  NULL on failure (message on the context) */
+AmtGpuLogoFind* amtgpu_logofind_create(AmtGpuContext* ctx, int width, int height, int bits);
+void amtgpu_logofind_destroy(AmtGpuLogoFind* lf);
+/* adds the Y planes of nframes frames (device; frame n at dY + n*frame_stride bytes, pitch in ELEMENTS as everywhere in this header,
+ * uint8 for 8 bits, uint16 containers above) to the sums.  Batches of any length: the driver splits them into launches whose 32-bit
+ * partials cannot overflow.  async */
+int  amtgpu_logofind_add_batch(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes);
+int64_t amtgpu_logofind_nframes(const AmtGpuLogoFind* lf);
+/* sums: 2*W*H int64 (host), S1 then SM, row-major.  get synchronises; set replaces the sums and the frame count (nframes >= 0) */
+int  amtgpu_logofind_get_sums(AmtGpuLogoFind* lf, int64_t* sums);
+int  amtgpu_logofind_set_sums(AmtGpuLogoFind* lf, const int64_t* sums, int64_t nframes);
+void amtgpu_logofind_default_params(AmtGpuLogoFindParams* params);
+/* ranked candidates from the current sums: the best min(cap, total) go to out, *ncand = total.  params NULL = defaults */
+int  amtgpu_logofind_candidates(AmtGpuLogoFind* lf, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* out, int cap, int* ncand);
+/* the same from sums in host memory, no device: sums = 2*W*H int64 as above.  Refuses NULL sums / ncand (out may be NULL only when
+ * cap == 0), W or H below 3, bits outside 8..16, nframes < 0, cap < 0 and parameters out of range.  Returns 0 without a message
+ * (there is no context). */
+int  amtgpu_logofind_candidates_host(const int64_t* sums, int width, int height, int bits, int64_t nframes, const AmtGpuLogoFindParams* params,
+                                     AmtGpuLogoRect* out, int cap, int* ncand);
+/* frame-sharded detection: every rank has added its own frames; one allreduce_sum_i64 over the 2*W*H + 1 values (the frame count rides
+ * along) leaves identical sums on every rank.  Synchronises. */
+int  amtgpu_logofind_allreduce(AmtGpuLogoFind* lf, const AmtGpuCollectives* coll);
+/* ScanLogo without a rectangle: detection over all nframes frames (8-bit, as ScanLogo is), then amtgpu_scanlogo with the best
+ * candidate, which *found receives (may be NULL).  No candidate: returns 0 with "no logo found", *found zeroed, no file written. */
+int  amtgpu_scanlogo_auto(AmtGpuContext* ctx, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
+                          int pitchY, int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath, int thy,
+                          int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found);
+/* the same over frame-sharded ranks: each adds its own frames, the sums are all-reduced (every rank finds the same rectangle), then
+ * amtgpu_scanlogo_sharded.  Rank 0 writes dstpath. */
+int  amtgpu_scanlogo_auto_sharded(AmtGpuContext* ctx, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,
+                                  int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int nframes_local,
+                                  int serviceid, const char* dstpath, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb,
+                                  const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found);
+/* amtgpu_scanlogo_file without a rectangle: the raw 'AMTR' clip is read twice -- detection over the Y planes of every frame (through
+ * the pinned upload path), then amtgpu_scanlogo_file with the best candidate */
+int  amtgpu_scanlogo_file_auto(AmtGpuContext* ctx, const char* srcpath, int serviceid, const char* workfile, const char* dstpath, int thy,
+                               int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found);
 
 #ifdef __cplusplus
 }
