@@ -306,6 +306,9 @@ static int logoscan_add(AmtGpuLogoScan* s, const void* dY, const void* dU, const
     if (known_verdicts) {
         v.assign(known_verdicts, known_verdicts + nframes);
     } else {
+        // the border histogram has 1 << bits bins and holds an accepted plane's samples, which span at most thy (erase_scan_kernels.hip
+        // border_plane); 8-bit samples fit whatever thy is
+        if (bits > 8 && s->thy >= (1 << bits)) throw std::runtime_error("[LogoScan] thy must be below 1 << bits for a clip of more than 8 bits");
         if (s->dVerdict.size() < (size_t)nframes) s->dVerdict.alloc(nframes);
         const int spb = s->ctx->prof_begin("scan_border_kernel");
         AMT_HIP(launch_scan_border(s->ctx->stream, bits, dY, dU, dV, strideY / es, strideUV / es, pitchY, pitchUV, imgx, imgy, cx, cy,

@@ -301,73 +301,120 @@ hipError_t launch_calc_fades(hipStream_t st, const float* danalysis, int analysi
 // reject when max-min > thy, else background = med_average (:414-428) = (int)((sum of the middle half of
 // the sorted samples + nn/2) / nn).  Sorting is replaced by a histogram (exact: the sorted sequence is
 // the histogram read out in order).  One workgroup per frame.
-// out[frame] = {valid, bgY, bgU, bgV}
+// The samples are taken at their real container value, whatever the declared depth (AddFrame is a template over pixel_t and
+// knows no depth): a first pass reduces their true min and max and decides, and only an accepted plane is histogrammed, as
+// value - base.  An accepted plane's samples span at most thy, so they fit the nbins = 1 << bits bins whenever thy < nbins, which
+// the host checks.  The reference keeps the samples in `short`: a 16-bit container value above 32767 enters as its
+// two's-complement wrap there, and so it does here.
+// out[frame] = {valid, bgY, bgU, bgV}; the backgrounds of a rejected frame are 0
 // ------------------------------------------------------------------------------------------------
 constexpr int kBorderThreads = 256;
 
+__device__ __forceinline__ int border_value(uint8_t v) { return (int)v; }
+__device__ __forceinline__ int border_value(uint16_t v) { return (int)(int16_t)v; }      // tmpY is a std::vector<short>
+
+// false: the plane's border spread exceeds thy (the same answer in every thread).  true: bg = its trimmed mean.
 template <typename pix_t>
-__device__ void border_plane(const pix_t* __restrict__ p, int pitch, int w, int h, int nbins, int* hist,
-                             long long* red, int* redi, int& vmin, int& vmax, int& bg)
+__device__ bool border_plane(const pix_t* __restrict__ p, int pitch, int w, int h, int nbins, int thy, int* hist,
+                             long long* red, int* redi, int& bg)
 {
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int kWaves = kBorderThreads / 64;
+    int* wmin = redi;                            // per-wave partial results: kWaves entries each
+    int* wmax = redi + kWaves;
+    int* wcnt = redi + 2 * kWaves;
     for (int i = tid; i < nbins; i += kBorderThreads) hist[i] = 0;
-    __syncthreads();
-    // samples above the declared depth (a 10-bit clip in uint16 containers is not guaranteed to stay below 1 << bits) are
-    // counted in the top bin instead of indexing past the histogram
-    const int top = nbins - 1;
-    for (int x = tid; x < w; x += kBorderThreads) {
-        atomicAdd(&hist[min((int)p[x], top)], 1);
-        atomicAdd(&hist[min((int)p[x + (long long)(h - 1) * pitch], top)], 1);
+    // pass 1: the true min and max of the border samples.  The first trip's samples (all of them, for a rectangle of up to 256 x 258)
+    // stay in registers for pass 2.
+    const bool hasRow = tid < w, hasCol = 1 + tid < h - 1;
+    int ra = 0, rb = 0, ca = 0, cb = 0;
+    int mn = 0x7FFFFFFF, mx = -0x7FFFFFFF - 1;
+    if (hasRow) {
+        ra = border_value(p[tid]); rb = border_value(p[tid + (long long)(h - 1) * pitch]);
+        mn = min(ra, rb); mx = max(ra, rb);
     }
-    for (int y = 1 + tid; y < h - 1; y += kBorderThreads) {
-        atomicAdd(&hist[min((int)p[(long long)y * pitch], top)], 1);
-        atomicAdd(&hist[min((int)p[w - 1 + (long long)y * pitch], top)], 1);
+    if (hasCol) {
+        ca = border_value(p[(long long)(1 + tid) * pitch]); cb = border_value(p[w - 1 + (long long)(1 + tid) * pitch]);
+        mn = min(mn, min(ca, cb)); mx = max(mx, max(ca, cb));
+    }
+    for (int x = tid + kBorderThreads; x < w; x += kBorderThreads) {
+        const int a = border_value(p[x]), b = border_value(p[x + (long long)(h - 1) * pitch]);
+        mn = min(mn, min(a, b));
+        mx = max(mx, max(a, b));
+    }
+    for (int y = 1 + tid + kBorderThreads; y < h - 1; y += kBorderThreads) {
+        const int a = border_value(p[(long long)y * pitch]), b = border_value(p[w - 1 + (long long)y * pitch]);
+        mn = min(mn, min(a, b));
+        mx = max(mx, max(a, b));
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        mn = min(mn, __shfl_xor(mn, s));
+        mx = max(mx, __shfl_xor(mx, s));
+    }
+    if (lane == 0) { wmin[wave] = mn; wmax[wave] = mx; }
+    __syncthreads();                             // (also: the histogram is cleared)
+    mn = wmin[0]; mx = wmax[0];
+#pragma unroll
+    for (int k = 1; k < kWaves; ++k) { mn = min(mn, wmin[k]); mx = max(mx, wmax[k]); }
+    if (mx - mn > thy) return false;             // abs(front - back) > thy (:638-649)
+    // pass 2: histogram of value - base.  A plane inside the declared depth keeps bin == value; otherwise the window
+    // [base, base + nbins) is moved so that it ends at the max (or starts at a negative min): the accepted samples lie in
+    // [max - thy, max] and thy < nbins
+    const int base = mn < 0 ? mn : max(0, mx - (nbins - 1));
+    if (hasRow) { atomicAdd(&hist[ra - base], 1); atomicAdd(&hist[rb - base], 1); }
+    if (hasCol) { atomicAdd(&hist[ca - base], 1); atomicAdd(&hist[cb - base], 1); }
+    for (int x = tid + kBorderThreads; x < w; x += kBorderThreads) {
+        atomicAdd(&hist[border_value(p[x]) - base], 1);
+        atomicAdd(&hist[border_value(p[x + (long long)(h - 1) * pitch]) - base], 1);
+    }
+    for (int y = 1 + tid + kBorderThreads; y < h - 1; y += kBorderThreads) {
+        atomicAdd(&hist[border_value(p[(long long)y * pitch]) - base], 1);
+        atomicAdd(&hist[border_value(p[w - 1 + (long long)y * pitch]) - base], 1);
     }
     __syncthreads();
     const int n = 2 * w + 2 * max(0, h - 2);     // a one-row plane (chroma of a 2-row rectangle) pushes its row twice (:616-635)
     const int lo = n / 4, hi = n - n / 4;
-    // each thread owns nbins/256 consecutive bins; exclusive prefix of the per-thread counts through LDS
+    // each thread owns nbins/256 consecutive bins; exclusive prefix of the per-thread counts: a scan inside the wave, the waves'
+    // totals through LDS
     const int per = (nbins + kBorderThreads - 1) / kBorderThreads;
     const int b0 = tid * per, b1 = min(nbins, b0 + per);
     int cnt = 0;
     for (int b = b0; b < b1; ++b) cnt += hist[b];
-    redi[tid] = cnt;
+    int incl = cnt;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const int v = __shfl_up(incl, s);
+        if (lane >= s) incl += v;
+    }
+    if (lane == 63) wcnt[wave] = incl;
     __syncthreads();
-    int before = 0;
-    for (int t = 0; t < tid; ++t) before += redi[t];
+    int before = incl - cnt;
+    for (int k = 0; k < wave; ++k) before += wcnt[k];
     long long part = 0;
-    int mn = 0x7FFFFFFF, mx = -1;
     int cum = before;
     for (int b = b0; b < b1; ++b) {
         const int c = hist[b];
         if (c) {
-            mn = min(mn, b);
-            mx = max(mx, b);
             const int s = max(cum, lo), e = min(cum + c, hi);
-            if (e > s) part += (long long)(e - s) * b;
+            if (e > s) part += (long long)(e - s) * (b + base);
         }
         cum += c;
     }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) part += __shfl_xor(part, s);
+    if (lane == 0) red[wave] = part;
     __syncthreads();
-    red[tid] = part;
-    redi[tid] = mn;
-    redi[kBorderThreads + tid] = mx;
-    __syncthreads();
-    for (int s = kBorderThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[tid] += red[tid + s];
-            redi[tid] = min(redi[tid], redi[tid + s]);
-            redi[kBorderThreads + tid] = max(redi[kBorderThreads + tid], redi[kBorderThreads + tid + s]);
-        }
-        __syncthreads();
-    }
-    vmin = redi[0];
-    vmax = redi[kBorderThreads];
+    long long sum = red[0];
+#pragma unroll
+    for (int k = 1; k < kWaves; ++k) sum += red[k];
     const int nn = hi - lo;
-    double t = (double)red[0];
+    double t = (double)sum;
     t = (t + nn / 2) / nn;
     bg = (int)t;
-    __syncthreads();
+    // (no barrier here: the next plane writes wmin / wmax, wcnt and red only behind barriers of its own that every thread passes
+    // after these reads, and clears the histogram, last read before the barrier above)
+    return true;
 }
 
 template <typename pix_t>
@@ -381,14 +428,13 @@ void scan_border_kernel(const pix_t* __restrict__ Y, const pix_t* __restrict__ U
     int* redi = hist + nbins;                              // 2*256
     long long* red = (long long*)(redi + 2 * kBorderThreads);   // 256 (8-byte aligned: nbins is a multiple of 2)
     const int frame = blockIdx.x;
-    int mn, mx, bgY, bgU, bgV;
-    bool ok = true;
-    border_plane(Y + (long long)frame * strideY + (long long)imgy * pitchY + imgx, pitchY, w, h, nbins, hist, red, redi, mn, mx, bgY);
-    ok = ok && (abs(mn - mx) <= thy);
-    border_plane(U + (long long)frame * strideUV + (long long)cy * pitchUV + cx, pitchUV, wUV, hUV, nbins, hist, red, redi, mn, mx, bgU);
-    ok = ok && (abs(mn - mx) <= thy);
-    border_plane(V + (long long)frame * strideUV + (long long)cy * pitchUV + cx, pitchUV, wUV, hUV, nbins, hist, red, redi, mn, mx, bgV);
-    ok = ok && (abs(mn - mx) <= thy);
+    int bgY = 0, bgU = 0, bgV = 0;
+    // the reference returns at the first plane that fails; the verdict is the same in every thread, so the rest is skipped whole
+    const bool ok =
+        border_plane(Y + (long long)frame * strideY + (long long)imgy * pitchY + imgx, pitchY, w, h, nbins, thy, hist, red, redi, bgY) &&
+        border_plane(U + (long long)frame * strideUV + (long long)cy * pitchUV + cx, pitchUV, wUV, hUV, nbins, thy, hist, red, redi, bgU) &&
+        border_plane(V + (long long)frame * strideUV + (long long)cy * pitchUV + cx, pitchUV, wUV, hUV, nbins, thy, hist, red, redi, bgV);
+    if (!ok) bgY = bgU = bgV = 0;
     if (threadIdx.x == 0) out[frame] = make_int4(ok ? 1 : 0, bgY, bgU, bgV);
 }
 
@@ -455,7 +501,7 @@ void scan_accumulate_kernel(const pix_t* __restrict__ Y, const pix_t* __restrict
             const int f = base[(long long)a.x * stride + x];
             const int b = pl == 0 ? a.y : (pl == 1 ? a.z : a.w);
             sF += f;
-            sF2 += f * f;
+            sF2 += (unsigned)f * (unsigned)f;          // (a 16-bit container value squared needs all 32 bits)
             sFB += f * b;
         }
         unsigned long long* o = acc + (pix0 + x) * 3;
