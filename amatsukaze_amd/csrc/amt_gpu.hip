@@ -433,37 +433,15 @@ int amtgpu_logoframe_allgather_results(AmtGpuLogoFrame* lf, const AmtGpuCollecti
             return;
         }
         if (!coll->allgather) throw std::runtime_error("AmtGpuCollectives incomplete");
-        // A rank whose own work failed must still enter every collective (the others would block in it for ever): what is wrong
-        // here travels as a status word next to the rank's range, and every rank throws after the exchange.
+        // A rank whose own work failed must still enter the exchange (api_common.hpp allgather_records): it throws there, with all others
         std::string local_error;
         try {
             if (first < 0 || nlocal < 0 || first + nlocal > lf->numFrames) throw std::runtime_error("frame range outside the clip");
             logoframe_sync_results(lf);
         } catch (const std::exception& e) { local_error = e.what(); }
-        const size_t rec = lf->logos.size() * 2;                               // floats per frame
-        // ragged shards: gather {first, nlocal, ok}, then records padded to the largest shard
-        const int64_t mine[3] = {local_error.empty() ? first : 0, local_error.empty() ? nlocal : 0, local_error.empty() ? 1 : 0};
-        std::vector<int64_t> ranges((size_t)coll->world * 3);
-        if (!coll->allgather(coll->user, mine, ranges.data(), sizeof mine)) throw std::runtime_error("allgather failed");
-        int64_t nmax = 0;
-        bool all_ok = true, ranges_ok = true;
-        for (int r = 0; r < coll->world; ++r) {
-            const int64_t f = ranges[3 * r], n = ranges[3 * r + 1];
-            all_ok = all_ok && ranges[3 * r + 2] == 1;
-            ranges_ok = ranges_ok && f >= 0 && n >= 0 && f + n <= lf->numFrames;
-            nmax = std::max(nmax, n);
-        }
-        if (!local_error.empty()) throw std::runtime_error(local_error);
-        if (!all_ok) throw std::runtime_error("another rank failed before the exchange of the scan records");
-        if (!ranges_ok) throw std::runtime_error("a rank reported a frame range outside the clip");
-        if (nmax == 0 || rec == 0) return;
-        std::vector<float> send((size_t)nmax * rec, 0.0f), recv((size_t)nmax * rec * coll->world);
-        std::memcpy(send.data(), lf->results.data() + (size_t)first * rec, (size_t)nlocal * rec * sizeof(float));
-        if (!coll->allgather(coll->user, send.data(), recv.data(), (int64_t)(send.size() * sizeof(float)))) throw std::runtime_error("allgather failed");
-        for (int r = 0; r < coll->world; ++r) {
-            const int64_t f = ranges[3 * r], n = ranges[3 * r + 1];
-            std::memcpy(lf->results.data() + (size_t)f * rec, recv.data() + (size_t)r * nmax * rec, (size_t)n * rec * sizeof(float));
-        }
+        const size_t rec = lf->logos.size() * 2 * sizeof(float);               // bytes per frame
+        const uint8_t* mine = reinterpret_cast<const uint8_t*>(lf->results.data()) + (local_error.empty() ? (size_t)first * rec : 0);
+        if (!allgather_records(coll, mine, first, nlocal, lf->numFrames, rec, lf->results.data(), false, local_error, "the scan records")) return;
         lf->ctx->bind();
         AMT_HIP(hipMemcpyAsync(lf->dResults.get(), lf->results.data(), lf->results.size() * sizeof(float), hipMemcpyHostToDevice, lf->ctx->stream));
         AMT_HIP(hipStreamSynchronize(lf->ctx->stream));

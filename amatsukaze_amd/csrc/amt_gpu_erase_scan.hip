@@ -12,28 +12,15 @@
 #include "api_common.hpp"
 #include "logo_fit.hpp"
 
-namespace amt {
-struct EraseGeom {
-    int w, h, wUV, hUV;
-    int imgx, imgy, cx, cy;
-    int uvparity;
-};
-hipError_t launch_delogo(hipStream_t st, int bits, const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV, long long strideY,
-                         long long strideUV, int pitchY, int pitchUV, const float* dplanes, EraseGeom g, int nframes, const float2* dfades,
-                         int zero_identity);
-hipError_t launch_ingest_rows(hipStream_t st, const void* src, long long src_stride, void* dst, long long dst_stride, unsigned long long chunk,
-                              long long nchunks);
-hipError_t launch_calc_fades(hipStream_t st, const float* danalysis, int analysis_first, int analysis_count, int num_frames, int first,
-                             int nframes, const uint8_t* dstate, int half, float2* dout);
-hipError_t launch_scan_border(hipStream_t st, int bits, const void* dY, const void* dU, const void* dV, long long strideY,
-                              long long strideUV, int pitchY, int pitchUV, int imgx, int imgy, int cx, int cy, int w, int h,
-                              int wUV, int hUV, int thy, int nframes, int4* dout);
-hipError_t launch_scan_accumulate(hipStream_t st, int bits, const void* dY, const void* dU, const void* dV, long long strideY,
-                                  long long strideUV, int pitchY, int pitchUV, int imgx, int imgy, int cx, int cy, int w, int h,
-                                  int wUV, int hUV, const int4* daccepted, int naccepted, unsigned long long* dacc);
-}
-
 using namespace amt;
+
+// The ABI's description of a batch (byte strides) as the kernels take it (strides in samples): the one place that divides.
+static PlaneBatch plane_batch(int bits, const void* Y, const void* U, const void* V, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV)
+{
+    const int es = bits <= 8 ? 1 : 2;
+    if (strideY % es || strideUV % es) throw std::runtime_error("frame stride not a multiple of the sample size");
+    return PlaneBatch{Y, U, V, strideY / es, strideUV / es, pitchY, pitchUV};
+}
 
 // ---------------------------------------------------------------------------------------------
 // AMTEraseLogo
@@ -132,19 +119,20 @@ int amtgpu_erase_calc_fades(AmtGpuErase* er, const float* analysis, int num_fram
     });
 }
 
-// sY / sU / sV: the planes Delogo READS (null = dY / dU / dV: in place)
-static void erase_launch(AmtGpuErase* er, void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV,
-                         int bits, int nframes, const float* fades, bool rect_only, const float* d_fades = nullptr,
-                         const void* sY = nullptr, const void* sU = nullptr, const void* sV = nullptr)
+// what every Delogo entry checks before it looks at the planes; false: an empty batch, nothing to do
+static bool erase_wanted(const AmtGpuErase* er, int bits, int nframes)
 {
-    if (!sY) { sY = dY; sU = dU; sV = dV; }
     if (bits < 8 || bits > 16) throw std::runtime_error("[AMTEraseLogo] Unsupported pixel format");
     if (er->mode != 0) throw std::runtime_error("[AMTEraseLogo] only mode 0 is supported (debug overlay modes are out of scope)");
-    if (nframes <= 0) return;
+    return nframes > 0;
+}
+
+// Delogo of a batch that has passed erase_wanted: reads src, writes dst (the same planes for the in-place calls)
+static void erase_launch(AmtGpuErase* er, const PlaneBatch& src, const PlanesOut& dst, int bits, int nframes, const float* fades, bool rect_only,
+                         const float* d_fades = nullptr)
+{
     const LogoPlanes& P = er->logo;
-    const int es = bits <= 8 ? 1 : 2;
-    if (strideY % es || strideUV % es) throw std::runtime_error("frame stride not a multiple of the sample size");
-    if (rect_only && (pitchY < P.w || pitchUV < P.wUV())) throw std::runtime_error("[AMTEraseLogo] rectangle pitch smaller than the logo width");
+    if (rect_only && (src.pitchY < P.w || src.pitchUV < P.wUV())) throw std::runtime_error("[AMTEraseLogo] rectangle pitch smaller than the logo width");
     er->ctx->bind();
     const float2* dfades = reinterpret_cast<const float2*>(d_fades);
     if (!dfades) {
@@ -177,21 +165,26 @@ static void erase_launch(AmtGpuErase* er, void* dY, void* dU, void* dV, int64_t 
     // 12-bit clip's out-of-range container values.  At 8 and 16 bits every container value is in range: only there are fade-0
     // frames skipped.
     const bool skip_fade0 = er->zeroIdentity && (bits == 8 || bits == 16);
-    AMT_HIP(launch_delogo(er->ctx->stream, bits, sY, sU, sV, dY, dU, dV, strideY / es, strideUV / es, pitchY, pitchUV, er->dPlanes.get(), g,
-                          nframes, dfades, skip_fade0 ? 1 : 0));
+    AMT_HIP(launch_delogo(er->ctx->stream, bits, src, dst, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
     er->ctx->prof_end(sp);
 }
 
 int amtgpu_erase_batch(AmtGpuErase* er, void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY,
                        int pitchUV, int bits, int nframes, const float* fades)
 {
-    return guard(er->ctx, [&] { erase_launch(er, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, fades, false); });
+    return guard(er->ctx, [&] {
+        if (erase_wanted(er, bits, nframes))
+            erase_launch(er, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, fades, false);
+    });
 }
 
 int amtgpu_erase_rect_batch(AmtGpuErase* er, void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY,
                             int pitchUV, int bits, int nframes, const float* fades)
 {
-    return guard(er->ctx, [&] { erase_launch(er, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, fades, true); });
+    return guard(er->ctx, [&] {
+        if (erase_wanted(er, bits, nframes))
+            erase_launch(er, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, fades, true);
+    });
 }
 
 int amtgpu_erase_batch_dfades(AmtGpuErase* er, void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY,
@@ -199,7 +192,8 @@ int amtgpu_erase_batch_dfades(AmtGpuErase* er, void* dY, void* dU, void* dV, int
 {
     return guard(er->ctx, [&] {
         if (!d_fades && nframes > 0) throw std::runtime_error("[AMTEraseLogo] null device fades");
-        erase_launch(er, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, nullptr, false, d_fades);
+        if (erase_wanted(er, bits, nframes))
+            erase_launch(er, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, nullptr, false, d_fades);
     });
 }
 
@@ -208,7 +202,8 @@ int amtgpu_erase_rect_batch_dfades(AmtGpuErase* er, void* dY, void* dU, void* dV
 {
     return guard(er->ctx, [&] {
         if (!d_fades && nframes > 0) throw std::runtime_error("[AMTEraseLogo] null device fades");
-        erase_launch(er, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, nullptr, true, d_fades);
+        if (erase_wanted(er, bits, nframes))
+            erase_launch(er, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, nullptr, true, d_fades);
     });
 }
 
@@ -218,7 +213,8 @@ int amtgpu_erase_batch_dfades_to(AmtGpuErase* er, const void* sY, const void* sU
     return guard(er->ctx, [&] {
         if (!d_fades && nframes > 0) throw std::runtime_error("[AMTEraseLogo] null device fades");
         if (nframes > 0 && (!sY || !sU || !sV || !dY || !dU || !dV)) throw std::runtime_error("[AMTEraseLogo] null plane");
-        erase_launch(er, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, nullptr, false, d_fades, sY, sU, sV);
+        if (erase_wanted(er, bits, nframes))
+            erase_launch(er, plane_batch(bits, sY, sU, sV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, nullptr, false, d_fades);
     });
 }
 
@@ -289,18 +285,13 @@ static void logoscan_pull(AmtGpuLogoScan* s)
     s->accDirty = false;
 }
 
-// border verdicts for a batch, then accumulate the accepted subset; returns accepted count
-static int logoscan_add(AmtGpuLogoScan* s, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
-                        int pitchY, int pitchUV, int bits, int imgx, int imgy, int nframes, int max_valid, const uint8_t* use_mask,
-                        uint8_t* valid_out, const int* frame_ids /* optional: batch slot -> frame index in dY */,
+// border verdicts for a batch (8..12 bits) of the scan's rectangle at r's origin, then accumulate the accepted subset; returns accepted count
+static int logoscan_add(AmtGpuLogoScan* s, const PlaneBatch& b, const ScanRect& r, int bits, int nframes, int max_valid, const uint8_t* use_mask,
+                        uint8_t* valid_out, const int* frame_ids /* optional: batch slot -> frame index in b */,
                         const int4* known_verdicts /* optional: skip the border kernel */)
 {
-    if (bits < 8 || bits > 12) throw std::runtime_error("[LogoScan] 8..12 bit only");
-    const int es = bits <= 8 ? 1 : 2;
-    if (strideY % es || strideUV % es) throw std::runtime_error("frame stride not a multiple of the sample size");
     ScanSums& S = s->sums;
-    const int wUV = S.w >> S.logUVx, hUV = S.h >> S.logUVy;
-    const int cx = imgx >> S.logUVx, cy = imgy >> S.logUVy;
+    if (r.w != S.w || r.h != S.h) throw std::runtime_error("scan size mismatch");       // (the accumulators are sized for S)
     s->ctx->bind();
     std::vector<int4>& v = s->lastVerdicts;
     if (known_verdicts) {
@@ -311,8 +302,7 @@ static int logoscan_add(AmtGpuLogoScan* s, const void* dY, const void* dU, const
         if (bits > 8 && s->thy >= (1 << bits)) throw std::runtime_error("[LogoScan] thy must be below 1 << bits for a clip of more than 8 bits");
         if (s->dVerdict.size() < (size_t)nframes) s->dVerdict.alloc(nframes);
         const int spb = s->ctx->prof_begin("scan_border_kernel");
-        AMT_HIP(launch_scan_border(s->ctx->stream, bits, dY, dU, dV, strideY / es, strideUV / es, pitchY, pitchUV, imgx, imgy, cx, cy,
-                                   S.w, S.h, wUV, hUV, s->thy, nframes, s->dVerdict.get()));
+        AMT_HIP(launch_scan_border(s->ctx->stream, bits, b, r, s->thy, nframes, s->dVerdict.get()));
         s->ctx->prof_end(spb);
         v.resize(nframes);
         download_via_pinned(s->ctx, v.data(), s->dVerdict.get(), (size_t)nframes * sizeof(int4));
@@ -337,8 +327,7 @@ static int logoscan_add(AmtGpuLogoScan* s, const void* dY, const void* dU, const
         AMT_HIP(hipMemcpyAsync(s->dAccepted.get(), acc.data(), acc.size() * sizeof(int4), hipMemcpyHostToDevice, s->ctx->stream));
         AMT_HIP(hipEventRecord(s->accUploaded, s->ctx->stream));
         const int spa = s->ctx->prof_begin("scan_accumulate_kernel");
-        AMT_HIP(launch_scan_accumulate(s->ctx->stream, bits, dY, dU, dV, strideY / es, strideUV / es, pitchY, pitchUV, imgx, imgy, cx, cy,
-                                       S.w, S.h, wUV, hUV, s->dAccepted.get(), (int)acc.size(), s->dAcc.get()));
+        AMT_HIP(launch_scan_accumulate(s->ctx->stream, bits, b, r, s->dAccepted.get(), (int)acc.size(), s->dAcc.get()));
         s->ctx->prof_end(spa);
         s->accDirty = true;
         S.nframes += (int)acc.size();
@@ -377,8 +366,9 @@ int amtgpu_logoscan_add_batch(AmtGpuLogoScan* s, const void* dY, const void* dU,
                               const uint8_t* use_mask, uint8_t* valid_out, int* naccepted)
 {
     return guard(s->ctx, [&] {
-        const int n = logoscan_add(s, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, imgx, imgy, nframes, max_valid, use_mask,
-                                   valid_out, nullptr, nullptr);
+        if (bits < 8 || bits > 12) throw std::runtime_error("[LogoScan] 8..12 bit only");
+        const int n = logoscan_add(s, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), scan_rect(imgx, imgy, s->sums.w, s->sums.h),
+                                   bits, nframes, max_valid, use_mask, valid_out, nullptr, nullptr);
         if (naccepted) *naccepted = n;
     });
 }
@@ -477,15 +467,14 @@ void reduce_scan(AmtGpuLogoScan* s, ShardGuard& sg, size_t npx)
     if (!amtgpu_logoscan_set_sums(s, buf.data(), buf.data() + npx, (int)buf[npx + 6])) throw std::runtime_error(s->ctx->err);
 }
 
-// ReMakeLogo twice (LogoScan.hpp:923-1036, 1065-1071) over a device-resident clip: `kept` lists the frames round 0 accepted (indices into
-// the clip), whose rectangle sits at (cx, cy); the finished logo's header gets (himgw, himgh, himgx, himgy).
+// ReMakeLogo twice (LogoScan.hpp:923-1036, 1065-1071) over a device-resident 8-bit clip: `kept` lists the frames round 0 accepted (indices
+// into the clip), whose rectangle is r; the finished logo's header gets (himgw, himgh, himgx, himgy).
 template <typename Progress>
-std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtGpuLogoScan* scan0, const void* dY, const void* dU,
-                                          const void* dV, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int cx, int cy, int w, int h,
-                                          int thy, const std::vector<int>& kept, const std::vector<int4>& keptVerdict, int himgw, int himgh,
-                                          int himgx, int himgy, Progress&& progress)
+std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtGpuLogoScan* scan0, const PlaneBatch& clip, const ScanRect& r, int thy,
+                                          const std::vector<int>& kept, const std::vector<int4>& keptVerdict, int himgw, int himgh, int himgx,
+                                          int himgy, Progress&& progress)
 {
-    const size_t npx = (size_t)3 * ((size_t)w * h + 2 * (size_t)(w / 2) * (h / 2));
+    const size_t npx = (size_t)3 * ((size_t)r.w * r.h + 2 * (size_t)r.wUV * r.hUV);
     const int bits = 8;
     const int numFrames = (int)kept.size();
     std::unique_ptr<AmtGpuLogo> logo(amtgpu_logoscan_get_logo(scan0, 255, 0, himgw, himgh, himgx, himgy));
@@ -503,13 +492,13 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
             EvalLogoSpec S;
             S.planes = deinterlaced_logo(logo->planes);
             S.tables = build_mask_tables(S.planes, 0.1f);
-            S.imgx = cx; S.imgy = cy; S.row0 = 0; S.row_step = 1; S.deint = 1; S.out_off = 0;
+            S.imgx = r.imgx; S.imgy = r.imgy; S.row0 = 0; S.row_step = 1; S.deint = 1; S.out_off = 0;
             std::vector<EvalLogoSpec> specs;
             specs.push_back(std::move(S));
             EvalEngine eng(c, std::move(specs), fades, true, 20, "logo_eval_fused_kernel.remake");
             std::vector<uint8_t> use(numFrames, 0);
             if (numFrames) {
-                eng.run(dY, strideY, pitchY, bits, numFrames, dEval.get(), dMap.get());
+                eng.run(clip.Y, clip.strideY, clip.pitchY, bits, numFrames, dEval.get(), dMap.get());       // (8 bits: a sample is a byte)
                 download_via_pinned(c, hEval.data(), dEval.get(), hEval.size() * sizeof(float));
             }
             for (int i = 0; i < numFrames; ++i) {
@@ -520,10 +509,8 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
                 use[i] = bestIdx > 8;                       // logo clearly present in this frame
             }
             progress(50.0f + 25.0f * round + 12.5f, numFrames, numFrames, numFrames);
-            rescan.reset(logoscan_new(c, w, h, 1, 1, thy));
-            if (numFrames)
-                logoscan_add(rescan.get(), dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, cx, cy, numFrames, numFrames, use.data(), nullptr,
-                             kept.data(), keptVerdict.data());
+            rescan.reset(logoscan_new(c, r.w, r.h, 1, 1, thy));
+            if (numFrames) logoscan_add(rescan.get(), clip, r, bits, numFrames, numFrames, use.data(), nullptr, kept.data(), keptVerdict.data());
         });
         reduce_scan(rescan.get(), sg, npx);
         logo.reset(amtgpu_logoscan_get_logo(rescan.get(), 255, 1, himgw, himgh, himgx, himgy));
@@ -532,9 +519,8 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
     return logo;
 }
 
-int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV, int64_t strideY,
-                  int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath,
-                  int imgx, int imgy, int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
+int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const PlaneBatch& clip, int imgw, int imgh, int nframes, int serviceid,
+                  const char* dstpath, const ScanRect& r, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
 {
     return guard(c, [&] {
         const bool sharded = coll && coll->world > 1;
@@ -548,62 +534,47 @@ int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* d
                 sg.cancel = 1;                                  // the other ranks learn about it with the next exchange
             }
         };
-        const int bits = 8;                                   // the reference's scan path is 8-bit only (:813)
-        const size_t npx = (size_t)3 * ((size_t)std::max(0, w) * std::max(0, h) + 2 * (size_t)(std::max(0, w) / 2) * (std::max(0, h) / 2));
+        const int bits = 8, es = 1;                           // the reference's scan path is 8-bit only (:813)
+        const size_t npx = (size_t)3 * ((size_t)std::max(0, r.w) * std::max(0, r.h) + 2 * (size_t)(std::max(0, r.w) / 2) * (std::max(0, r.h) / 2));
         std::unique_ptr<AmtGpuLogoScan> scan;
         std::vector<int> kept;              // frame index (within this rank's frames) of every kept frame
         std::vector<int4> keptVerdict;      // its {1,bgY,bgU,bgV}
         const int chunk = 4096;
-        auto at = [&](const void* base, int64_t stride, int f0) { return (const void*)((const uint8_t*)base + (int64_t)f0 * stride); };
-        if (!sharded) {
-            if (imgx < 0 || imgy < 0 || imgx + w > imgw || imgy + h > imgh) throw std::runtime_error("scan rectangle outside the frame");
-            scan.reset(logoscan_new(c, w, h, 1, 1, thy));
-            // round 0: every frame in stream order until numMaxFrames are kept
-            for (int f0 = 0; f0 < nframes && (int)kept.size() < numMaxFrames; f0 += chunk) {
+        // round 0: the border verdicts of every frame in stream order.  One rank accepts frames as it goes and stops once numMaxFrames are
+        // kept; a shard accepts nothing yet (quota 0) and keeps every valid frame: which of them count is decided below
+        auto wanted = [&] { return sharded || (int)kept.size() < numMaxFrames; };
+        sg.attempt([&] {
+            if (r.imgx < 0 || r.imgy < 0 || r.imgx + r.w > imgw || r.imgy + r.h > imgh) throw std::runtime_error("scan rectangle outside the frame");
+            scan.reset(logoscan_new(c, r.w, r.h, 1, 1, thy));
+            for (int f0 = 0; f0 < nframes && wanted(); f0 += chunk) {
                 const int n = std::min(chunk, nframes - f0);
-                std::vector<uint8_t> valid(n);
-                logoscan_add(scan.get(), at(dY, strideY, f0), at(dU, strideUV, f0), at(dV, strideUV, f0), strideY, strideUV, pitchY, pitchUV,
-                             bits, imgx, imgy, n, numMaxFrames - (int)kept.size(), nullptr, valid.data(), nullptr, nullptr);
+                logoscan_add(scan.get(), plane_batch_from(clip, f0, es), r, bits, n, sharded ? 0 : numMaxFrames - (int)kept.size(), nullptr, nullptr,
+                             nullptr, nullptr);
                 for (int i = 0; i < n; ++i)
-                    if (valid[i]) { kept.push_back(f0 + i); keptVerdict.push_back(scan->lastVerdicts[i]); }
+                    if (scan->lastVerdicts[i].x && wanted()) { kept.push_back(f0 + i); keptVerdict.push_back(scan->lastVerdicts[i]); }
                 progress(50.0f * (f0 + n) / std::max(1, nframes), f0 + n, 0, (int)kept.size());
             }
-        } else {
-            // round 0, sharded: border verdicts of every local frame (nothing accepted yet: max_valid = 0) ...
-            sg.attempt([&] {
-                if (imgx < 0 || imgy < 0 || imgx + w > imgw || imgy + h > imgh) throw std::runtime_error("scan rectangle outside the frame");
-                scan.reset(logoscan_new(c, w, h, 1, 1, thy));
-                for (int f0 = 0; f0 < nframes; f0 += chunk) {
-                    const int n = std::min(chunk, nframes - f0);
-                    logoscan_add(scan.get(), at(dY, strideY, f0), at(dU, strideUV, f0), at(dV, strideUV, f0), strideY, strideUV, pitchY, pitchUV,
-                                 bits, imgx, imgy, n, 0, nullptr, nullptr, nullptr, nullptr);
-                    for (int i = 0; i < n; ++i)
-                        if (scan->lastVerdicts[i].x) { kept.push_back(f0 + i); keptVerdict.push_back(scan->lastVerdicts[i]); }
-                    progress(50.0f * (f0 + n) / std::max(1, nframes), f0 + n, 0, (int)kept.size());
-                }
-            });
-            // ... this rank's share of "the first numMaxFrames valid frames of the stream" (and how every rank is doing) ...
+        });
+        if (sharded) {
+            // this rank's share of "the first numMaxFrames valid frames of the stream" (and how every rank is doing) ...
             std::vector<int64_t> counts((size_t)coll->world * 2, 0);
             const int64_t mine[2] = {sg.error.empty() ? (int64_t)kept.size() : 0, sg.status()};
             if (!coll->allgather(coll->user, mine, counts.data(), sizeof mine)) throw std::runtime_error("allgather failed");
             int64_t before = 0, summed = 0;
-            for (int r = 0; r < coll->world; ++r) summed += counts[2 * r + 1];
-            for (int r = 0; r < coll->rank; ++r) before += counts[2 * r];
+            for (int k = 0; k < coll->world; ++k) summed += counts[2 * k + 1];
+            for (int k = 0; k < coll->rank; ++k) before += counts[2 * k];
             sg.agree(summed);
             const int quota = (int)std::max<int64_t>(0, std::min<int64_t>(mine[0], (int64_t)numMaxFrames - before));
             kept.resize(quota);
             keptVerdict.resize(quota);
             // ... accumulated locally, summed over ranks
             sg.attempt([&] {
-                if (quota)
-                    logoscan_add(scan.get(), dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, imgx, imgy, quota, quota, nullptr, nullptr,
-                                 kept.data(), keptVerdict.data());
+                if (quota) logoscan_add(scan.get(), clip, r, bits, quota, quota, nullptr, nullptr, kept.data(), keptVerdict.data());
             });
             reduce_scan(scan.get(), sg, npx);
         }
         const int numFrames = (int)kept.size();
-        std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, scan.get(), dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgx, imgy, w, h,
-                                                         thy, kept, keptVerdict, imgw, imgh, imgx, imgy, progress);
+        std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, scan.get(), clip, r, thy, kept, keptVerdict, imgw, imgh, r.imgx, r.imgy, progress);
         progress(1, numFrames, numFrames, numFrames);
         if (dstpath && (!sharded || coll->rank == 0)) save_lgd(logo->planes, dstpath, "No Name", serviceid);
     });
@@ -617,8 +588,8 @@ int amtgpu_scanlogo(AmtGpuContext* c, const void* dY, const void* dU, const void
                     int pitchY, int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath, int imgx,
                     int imgy, int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
 {
-    return scanlogo_impl(c, nullptr, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, nframes, serviceid, dstpath, imgx, imgy,
-                         w, h, thy, numMaxFrames, cb);
+    return scanlogo_impl(c, nullptr, plane_batch(8, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), imgw, imgh, nframes, serviceid, dstpath,
+                         scan_rect(imgx, imgy, w, h), thy, numMaxFrames, cb);
 }
 
 // The reference's exported ScanLogo, argument for argument (LogoScan.hpp:1083-1098; C# P/Invoke AmatsukazeNatives.cs:391-393), over a
@@ -668,16 +639,15 @@ int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, c
             if (!amtgpu_frames_upload(c, dChunk.get(), planar.data(), fsz * n) || !amtgpu_frames_upload_wait(c)) throw std::runtime_error(c->err);
             const uint8_t *dY = dChunk.get(), *dU = dY + ysz * n, *dV = dU + csz * n;
             std::vector<uint8_t> valid(n);
-            logoscan_add(scan.get(), dY, dU, dV, (int64_t)ysz, (int64_t)csz, W, W / 2, 8, imgx, imgy, n, numMaxFrames - nkept, nullptr, valid.data(),
-                         nullptr, nullptr);
+            logoscan_add(scan.get(), PlaneBatch{dY, dU, dV, (long long)ysz, (long long)csz, W, W / 2}, scan_rect(imgx, imgy, w, h), 8, n,
+                         numMaxFrames - nkept, nullptr, valid.data(), nullptr, nullptr);
             for (int i = 0; i < n; ++i) {
                 if (!valid[i]) continue;
                 // (the library's own row kernel, not the runtime's 2-D copy: amt_gpu_upload.hip)
-                AMT_HIP(launch_ingest_rows(c->stream, dY + ysz * i + (size_t)imgy * W + imgx, W, cropY.get() + (size_t)nkept * w * h, w, (unsigned long long)w, h));
-                AMT_HIP(launch_ingest_rows(c->stream, dU + csz * i + (size_t)(imgy / 2) * (W / 2) + imgx / 2, W / 2, cropU.get() + (size_t)nkept * wUV * hUV, wUV,
-                                           (unsigned long long)wUV, hUV));
-                AMT_HIP(launch_ingest_rows(c->stream, dV + csz * i + (size_t)(imgy / 2) * (W / 2) + imgx / 2, W / 2, cropV.get() + (size_t)nkept * wUV * hUV, wUV,
-                                           (unsigned long long)wUV, hUV));
+                auto crop = [&](const uint8_t* src, int pitch, uint8_t* dst, int cw, int ch) { AMT_HIP(launch_ingest_rows(c->stream, src, pitch, dst, cw, (unsigned long long)cw, ch)); };
+                crop(dY + ysz * i + (size_t)imgy * W + imgx, W, cropY.get() + (size_t)nkept * w * h, w, h);
+                crop(dU + csz * i + (size_t)(imgy / 2) * (W / 2) + imgx / 2, W / 2, cropU.get() + (size_t)nkept * wUV * hUV, wUV, hUV);
+                crop(dV + csz * i + (size_t)(imgy / 2) * (W / 2) + imgx / 2, W / 2, cropV.get() + (size_t)nkept * wUV * hUV, wUV, hUV);
                 keptVerdict.push_back(scan->lastVerdicts[i]);
                 ++nkept;
             }
@@ -687,8 +657,9 @@ int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, c
         std::vector<int> kept(nkept);
         for (int i = 0; i < nkept; ++i) kept[i] = i;
         ShardGuard unsharded;
-        std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, unsharded, scan.get(), cropY.get(), cropU.get(), cropV.get(), (int64_t)w * h,
-                                                         (int64_t)wUV * hUV, w, wUV, 0, 0, w, h, thy, kept, keptVerdict, W, H, imgx, imgy, progress);
+        const PlaneBatch crops{cropY.get(), cropU.get(), cropV.get(), (long long)w * h, (long long)wUV * hUV, w, wUV};
+        std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, unsharded, scan.get(), crops, scan_rect(0, 0, w, h), thy, kept, keptVerdict, W, H, imgx, imgy,
+                                                         progress);
         progress(1, nkept, nkept, nkept);
         save_lgd(logo->planes, dstpath, "No Name", serviceid);
     });
@@ -706,8 +677,8 @@ int amtgpu_scanlogo_sharded(AmtGpuContext* c, const AmtGpuCollectives* coll, con
                             int serviceid, const char* dstpath, int imgx, int imgy, int w, int h, int thy, int numMaxFrames,
                             AMTGPU_LOGO_ANALYZE_CB cb)
 {
-    return scanlogo_impl(c, coll, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, nframes_local, serviceid, dstpath, imgx,
-                         imgy, w, h, thy, numMaxFrames, cb);
+    return scanlogo_impl(c, coll, plane_batch(8, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), imgw, imgh, nframes_local, serviceid, dstpath,
+                         scan_rect(imgx, imgy, w, h), thy, numMaxFrames, cb);
 }
 
 } // extern "C"

@@ -6,20 +6,6 @@
 
 #include "api_common.hpp"
 
-namespace amt {
-struct WeaveArgs {
-    const uint8_t* srcY; const uint8_t* srcU; const uint8_t* srcV;
-    long long src_strideY, src_strideUV;
-    int src_pitchY, src_pitchUV;
-    uint8_t* dstY; uint8_t* dstU; uint8_t* dstV;
-    long long dst_strideY, dst_strideUV;
-    int dst_pitchY, dst_pitchUV;
-    int rowY, rowUV;
-    int H, HUV;
-    int nv12, es, vec;
-};
-hipError_t launch_weave_fields(hipStream_t st, const WeaveArgs& a, const int* dtop_index, const int* dbottom_index, int nframes);
-}
 using namespace amt;
 
 extern "C" {

@@ -11,11 +11,6 @@
 
 #include "api_common.hpp"
 
-namespace amt {
-long long logofind_launch_cap(int bits);
-hipError_t launch_logofind(hipStream_t st, int bits, const void* dY, long long frame_stride, int pitch_elems, int W, int H, int nframes,
-                           int num_cus, unsigned long long* dS1, unsigned long long* dSM);
-}
 using namespace amt;
 
 struct AmtGpuLogoFind {

@@ -10,10 +10,6 @@
 #include "api_common.hpp"
 #include "stats_decisions.hpp"
 
-namespace amt {
-hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W,
-                              int H, const void* dprevY, int nframes, unsigned long long* dout);
-}
 using namespace amt;
 
 struct AmtGpuFrameStats {
@@ -23,8 +19,7 @@ struct AmtGpuFrameStats {
 };
 
 namespace {
-// the exchange of amtgpu_framestats_allgather.  A rank whose own part failed (local_error) still enters every collective with
-// neutral data -- the others would block in it for ever -- and all ranks throw together once the status is known.
+// the exchange of amtgpu_framestats_allgather (api_common.hpp allgather_records); local_error: what this rank's own part failed with
 void gather_frame_metrics(const AmtGpuCollectives* coll, const uint64_t* local, int first, int nlocal, int num_frames,
                           uint64_t* out, std::string local_error)
 {
@@ -41,32 +36,7 @@ void gather_frame_metrics(const AmtGpuCollectives* coll, const uint64_t* local, 
         return;
     }
     if (!coll->allgather || coll->rank < 0 || coll->rank >= coll->world) throw std::runtime_error("AmtGpuCollectives incomplete");
-    const bool ok = local_error.empty();
-    const int64_t mine[3] = {ok ? first : 0, ok ? nlocal : 0, ok ? 1 : 0};
-    std::vector<int64_t> ranges((size_t)coll->world * 3);
-    if (!coll->allgather(coll->user, mine, ranges.data(), sizeof mine)) throw std::runtime_error("allgather failed");
-    bool all_ok = true;
-    int64_t nmax = 0, next = 0;
-    bool tiles = true;                          // ranks hold contiguous ranges in rank order that tile [0, num_frames)
-    for (int r = 0; r < coll->world; ++r) {
-        const int64_t f = ranges[3 * r], n = ranges[3 * r + 1];
-        all_ok = all_ok && ranges[3 * r + 2] == 1;
-        tiles = tiles && f == next && n >= 0;
-        next = f + n;
-        nmax = std::max(nmax, n);
-    }
-    tiles = tiles && next == num_frames;
-    if (!ok) throw std::runtime_error(local_error);
-    if (!all_ok) throw std::runtime_error("another rank failed before the exchange of the frame metrics");
-    if (!tiles) throw std::runtime_error("the ranks' frame ranges do not tile the clip in rank order");
-    if (nmax == 0) return;
-    std::vector<uint64_t> send((size_t)nmax * rec, 0), recv((size_t)nmax * rec * coll->world);
-    if (nlocal) std::memcpy(send.data(), local, (size_t)nlocal * rec * sizeof(uint64_t));
-    if (!coll->allgather(coll->user, send.data(), recv.data(), (int64_t)(send.size() * sizeof(uint64_t)))) throw std::runtime_error("allgather failed");
-    for (int r = 0; r < coll->world; ++r) {
-        const int64_t f = ranges[3 * r], n = ranges[3 * r + 1];
-        if (n) std::memcpy(out + (size_t)f * rec, recv.data() + (size_t)r * nmax * rec, (size_t)n * rec * sizeof(uint64_t));
-    }
+    allgather_records(coll, local, first, nlocal, num_frames, rec * sizeof(uint64_t), out, true, local_error, "the frame metrics");
 }
 } // namespace
 

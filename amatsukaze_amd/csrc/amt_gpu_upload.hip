@@ -25,10 +25,6 @@
 
 #include "api_common.hpp"
 
-namespace amt {
-hipError_t launch_ingest_rows(hipStream_t st, const void* src_host_mapped, long long src_stride, void* dst, long long dst_stride,
-                              unsigned long long chunk, long long nchunks);
-}
 using namespace amt;
 
 namespace {

@@ -3,10 +3,13 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <exception>
 #include <mutex>
 #include <string>
+#include <vector>
 
+#include "../../include/amt_gpu.h"
 #include "decisions.hpp"
 #include "engine.hpp"
 #include "logo_model.hpp"
@@ -63,4 +66,43 @@ template <typename F> inline int guard(AmtGpuContext* c, F&& f, const char* call
         if (c) c->err = "unknown error";
     }
     return 0;
+}
+
+// The exchange of per-frame records between the ranks of a sharded run (world > 1, coll->allgather present): this rank holds records
+// [first, first + nlocal) of num_frames, rec_bytes each, at `local`; afterwards every rank's are in place in `out` (the whole clip's).
+// Ragged shards: {first, nlocal, ok} is gathered first, then the records padded to the largest shard.  A rank whose own part failed
+// (local_error) still enters every collective -- the others would block in it for ever -- and all ranks throw together once the status
+// is known.  tiling: the ranges must tile the clip in rank order; otherwise any range inside the clip is taken.  false: no records.
+inline bool allgather_records(const AmtGpuCollectives* coll, const void* local, int first, int nlocal, int64_t num_frames, size_t rec_bytes,
+                              void* out, bool tiling, const std::string& local_error, const char* what)
+{
+    const bool ok = local_error.empty();
+    const int64_t mine[3] = {ok ? first : 0, ok ? nlocal : 0, ok ? 1 : 0};
+    std::vector<int64_t> ranges((size_t)coll->world * 3);
+    if (!coll->allgather(coll->user, mine, ranges.data(), sizeof mine)) throw std::runtime_error("allgather failed");
+    bool all_ok = true, inside = true, tiles = true;
+    int64_t nmax = 0, next = 0;
+    for (int r = 0; r < coll->world; ++r) {
+        const int64_t f = ranges[3 * r], n = ranges[3 * r + 1];
+        all_ok = all_ok && ranges[3 * r + 2] == 1;
+        inside = inside && f >= 0 && n >= 0 && f + n <= num_frames;
+        tiles = tiles && f == next && n >= 0;
+        next = f + n;
+        nmax = std::max(nmax, n);
+    }
+    tiles = tiles && next == num_frames;
+    if (!ok) throw std::runtime_error(local_error);
+    if (!all_ok) throw std::runtime_error(std::string("another rank failed before the exchange of ") + what);
+    if (tiling && !tiles) throw std::runtime_error("the ranks' frame ranges do not tile the clip in rank order");
+    if (!tiling && !inside) throw std::runtime_error("a rank reported a frame range outside the clip");
+    if (nmax == 0 || rec_bytes == 0) return false;
+    const size_t shard = (size_t)nmax * rec_bytes;
+    std::vector<uint8_t> send(shard, 0), recv(shard * coll->world);
+    if (nlocal) std::memcpy(send.data(), local, (size_t)nlocal * rec_bytes);
+    if (!coll->allgather(coll->user, send.data(), recv.data(), (int64_t)shard)) throw std::runtime_error("allgather failed");
+    for (int r = 0; r < coll->world; ++r) {
+        const int64_t f = ranges[3 * r], n = ranges[3 * r + 1];
+        if (n) std::memcpy((uint8_t*)out + (size_t)f * rec_bytes, recv.data() + (size_t)r * shard, (size_t)n * rec_bytes);
+    }
+    return true;
 }

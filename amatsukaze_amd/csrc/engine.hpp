@@ -12,6 +12,7 @@
 
 #include "eval_plan.h"
 #include "eval_tiles.hpp"
+#include "kernels.hpp"
 #include "logo_model.hpp"
 
 #define AMT_HIP(expr)                                                                              \
@@ -138,24 +139,6 @@ public:
     size_t size() const { return n_; }
 };
 
-// tile plan of one evaluation logo resident in HBM (eval_tiles.hpp; eval_pair_kernels.hip).  slot = (band * kTileWaves + wave) * 64 + lane
-struct TileLogoDev {
-    const float2* kp;            // [13][nslots]  taps of the slot's mask pixel as pairs {k[2j], k[2j+1]} (k[25] = 0), pair-major
-    const float2* sc;            // [32][nslots]  bin-major {scale, scale2} of the slot's mask pixel (the exact scan kernel)
-    const float2* pq;            // [nslots]      {P, Q}: the pixel's response on flat level c is |P + Q c| (the linear analysis kernel: no gathers)
-    const uint32_t* sinfo;       // [nslots]      tile_slot_info
-    const uint32_t* pos;         // [nslots]      (y << 16) | x of the slot's mask pixel in the evaluation logo (the linear kernel's exact bin check)
-    const TileDesc* tiles;       // [nbands * 8]
-    const TileBandDesc* bands;   // [nbands]
-    const int* tlist;            // [ntlist]  indices of the tiles that hold pixels (kernels that need no band order walk these)
-    int nbands, nslots, ntlist;
-    float floorResp;             // limitCorr of the logo (LogoScan.hpp:203)
-    // the linear kernel's copy of everything it loads per tile, in ONE allocation (one scalar base instead of five: its loop is short of
-    // scalar registers): kp at 0, then pq, sinfo, the evaluation logo's a and b planes at these byte offsets
-    const char* lin;
-    unsigned lin_pq, lin_sinfo, lin_a, lin_b;
-};
-
 // one evaluation logo + where its source pixels come from
 struct EvalLogoSpec {
     LogoPlanes planes;       // evaluation logo (deinterlaced, or one field)
@@ -241,53 +224,5 @@ private:
     std::vector<double> lin_err_formula_;              // ... and what evaluating |P + Q c| instead of looking the scale up adds (absolute)
     bool lin_formula_ok_ = true;                       // every logo's responses fit the formula's preconditions (finite, floorResp > 0)
 };
-
-// kernel launcher (eval_fused_kernels.hip).  dnframes (device, optional): the number of frames actually present (<= nframes,
-// which then only sizes the grid); scatter != 0: frame i's results go to record dframe_map[i] of dout; fade_chunk > 0 (with dnframes):
-// a workgroup evaluates fade_chunk of the fades, the chunks of a (logo, frame group) run side by side -- a handful of listed frames
-// is a latency problem (one workgroup walking every band for all fades), not a throughput one
-hipError_t launch_logo_eval_fused(hipStream_t st, int bits, const EvalLogoDev* dlogos, int nlogos, const EvalBand* dbands,
-                                  const float* dfades, int nfades, int fade0, const void* dY, const int* dframe_map,
-                                  long long frame_stride_elems, int pitch, int nframes, int G, float* dout, int out_frame_stride,
-                                  int take_abs, int plane_cap, const int* dnframes = nullptr, int scatter = 0, int fade_chunk = 0);
-// eval_linear_kernels.hip
-hipError_t launch_logo_eval_linear(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
-                                   const float* dfades, int nfades, int fade0, const void* dY, const int* dframe_map,
-                                   long long frame_stride_elems, int pitch, int nframes, int G, float* dout, int out_frame_stride,
-                                   int take_abs, float bin_eps, int qlog2, int qcap, uint8_t* dforce);
-// eval_pair_kernels.hip: fades {0, 1} of every logo, bit-exact
-hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
-                                 const void* dY, const int* dframe_map, long long frame_stride_elems, int pitch,
-                                 int nframes, int G, float* dout, int out_frame_stride, int take_abs);
-// Sentinel monitor of AMTGPU_ANALYZE_LINEAR_MONITORED: persistent per-analyzer device state.  max_abs_bits: the largest |linear - exact| over
-// every compared score as float bits (non-negative floats order like unsigned ints; NaN counts as +inf); tripped: a comparison failed (sticky
-// until re-armed); frames_checked: sentinel frames compared; batches_tripped: batches in which a comparison failed
-struct MonitorState {
-    unsigned max_abs_bits;
-    int tripped;
-    unsigned long long frames_checked;
-    unsigned batches_tripped;
-    unsigned pad_;
-};
-// Sentinel arguments of the mark kernel (nsent = 0: none, the guarded mode).  The sentinels of a batch of nframes frames are
-// s_j = floor(j (nframes - 1) / (nsent - 1)), j < nsent (nsent = 1: frame 0); nsent <= nframes.  side: [nsent][stride] copy of their
-// linear records; side_forced: [nsent] their force byte; gate: [2] per-batch words the mark kernel zeroes (frames of the gated exact pass,
-// workgroups that tripped) -- analysis_sentinel_check_kernel sets them, later launches read them
-struct SentinelArgs {
-    int nsent = 0;
-    float* side = nullptr;
-    uint8_t* side_forced = nullptr;
-    int* gate = nullptr;
-};
-hipError_t launch_analysis_mark(hipStream_t st, const float* drec, int stride, int nframes, int ngroups, int nfades, const float* eps3,
-                                int* dlist, int* dcount, const uint8_t* dforce = nullptr, const SentinelArgs& sent = SentinelArgs());
-// compares the sentinels' exact records (rec, after the listed re-evaluation) with their saved linear copies; a failed comparison or an
-// earlier one (state->tripped) sets gate[0] = nframes and stores `epoch` to the host-mapped word `host_flag` (optional)
-hipError_t launch_analysis_sentinel_check(hipStream_t st, const float* drec, int stride, int nframes, const SentinelArgs& sent, float tol,
-                                          MonitorState* dstate, int* host_flag, int epoch);
-// list[i] = i for i < n (the identity list of the gated whole-batch re-evaluation)
-hipError_t launch_analysis_iota(hipStream_t st, int* dlist, int n);
-hipError_t launch_rect_range_flag(hipStream_t st, const void* dY, long long frame_stride_elems, int pitch, int imgx, int imgy, int w, int h, int bits,
-                                  int nframes, uint8_t* dflag);
 
 } // namespace amt

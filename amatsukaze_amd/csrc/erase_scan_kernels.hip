@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "exact_math.h"
+#include "kernels.hpp"
 
 namespace amt {
 
@@ -17,11 +18,6 @@ namespace amt {
 // frame mode when fadeT == fadeB, otherwise per field with chroma row parity (imgy/2)%2.  In field mode
 // the reference processes hUV/2 chroma rows per field, so an odd last chroma row is left untouched.
 // ------------------------------------------------------------------------------------------------
-struct EraseGeom {
-    int w, h, wUV, hUV;
-    int imgx, imgy, cx, cy;       // rectangle origin in luma / chroma planes
-    int uvparity;
-};
 
 // One workgroup = kDelogoRows consecutive rectangle rows (luma rows first, then U, then V) of one frame; a
 // thread owns PAIRS of horizontally adjacent samples (the rectangle origin and width are even, LogoScan.hpp:69,
@@ -183,9 +179,8 @@ void delogo_kernel(const pix_t* sY, const pix_t* sU, const pix_t* sV, pix_t* Y, 
     }
 }
 
-hipError_t launch_delogo(hipStream_t st, int bits, const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV, long long strideY,
-                         long long strideUV, int pitchY, int pitchUV, const float* dplanes, EraseGeom g, int nframes, const float2* dfades,
-                         int zero_identity)
+hipError_t launch_delogo(hipStream_t st, int bits, const PlaneBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g, int nframes,
+                         const float2* dfades, int zero_identity)
 {
     if (nframes <= 0) return hipSuccess;
     const int rows = g.h + 2 * g.hUV;
@@ -195,18 +190,19 @@ hipError_t launch_delogo(hipStream_t st, int bits, const void* sY, const void* s
     auto even = [](long long v) { return (v & 1) == 0; };
     // a pair access needs 2*es alignment of every row start and an even width (plane bases come from hipMalloc /
     // AviSynth's 64-byte aligned planes; a caller handing odd byte offsets falls back to single samples)
-    const int pairY = even(g.w) && even(g.imgx) && even(pitchY) && even(strideY) && ((uintptr_t)dY % (2 * es) == 0) && ((uintptr_t)sY % (2 * es) == 0);
-    const int pairUV = even(g.wUV) && even(g.cx) && even(pitchUV) && even(strideUV) && ((uintptr_t)dU % (2 * es) == 0) &&
-                       ((uintptr_t)dV % (2 * es) == 0) && ((uintptr_t)sU % (2 * es) == 0) && ((uintptr_t)sV % (2 * es) == 0);
+    auto aligned = [&](const void* p) { return (uintptr_t)p % (2 * es) == 0; };
+    const int pairY = even(g.w) && even(g.imgx) && even(src.pitchY) && even(src.strideY) && aligned(dst.Y) && aligned(src.Y);
+    const int pairUV = even(g.wUV) && even(g.cx) && even(src.pitchUV) && even(src.strideUV) && aligned(dst.U) && aligned(dst.V) && aligned(src.U) &&
+                       aligned(src.V);
     // four samples per lane where a row is a multiple of 4 wide (coefficient rows are then 16-byte aligned float4s)
     const int quadY = pairY && g.w % 4 == 0;
     const int quadUV = pairUV && g.wUV % 4 == 0;
-    if (bits <= 8)
-        hipLaunchKernelGGL(delogo_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)sY, (const uint8_t*)sU, (const uint8_t*)sV, (uint8_t*)dY, (uint8_t*)dU, (uint8_t*)dV, strideY,
-                           strideUV, pitchY, pitchUV, dplanes, g, maxv, dfades, pairY, pairUV, nframes, quadY, quadUV, zero_identity);
-    else
-        hipLaunchKernelGGL(delogo_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)sY, (const uint16_t*)sU, (const uint16_t*)sV, (uint16_t*)dY, (uint16_t*)dU, (uint16_t*)dV, strideY,
-                           strideUV, pitchY, pitchUV, dplanes, g, maxv, dfades, pairY, pairUV, nframes, quadY, quadUV, zero_identity);
+    with_sample_type(bits, [&](auto px) {
+        typedef decltype(px) pix_t;
+        hipLaunchKernelGGL(delogo_kernel<pix_t>, grid, block, 0, st, (const pix_t*)src.Y, (const pix_t*)src.U, (const pix_t*)src.V, (pix_t*)dst.Y,
+                           (pix_t*)dst.U, (pix_t*)dst.V, src.strideY, src.strideUV, src.pitchY, src.pitchUV, dplanes, g, maxv, dfades, pairY, pairUV,
+                           nframes, quadY, quadUV, zero_identity);
+    });
     return hipGetLastError();
 }
 
@@ -438,20 +434,17 @@ void scan_border_kernel(const pix_t* __restrict__ Y, const pix_t* __restrict__ U
     if (threadIdx.x == 0) out[frame] = make_int4(ok ? 1 : 0, bgY, bgU, bgV);
 }
 
-hipError_t launch_scan_border(hipStream_t st, int bits, const void* dY, const void* dU, const void* dV, long long strideY,
-                              long long strideUV, int pitchY, int pitchUV, int imgx, int imgy, int cx, int cy, int w, int h,
-                              int wUV, int hUV, int thy, int nframes, int4* dout)
+hipError_t launch_scan_border(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, int thy, int nframes, int4* dout)
 {
     if (nframes <= 0) return hipSuccess;
     const int nbins = 1 << bits;
     const size_t lds = (size_t)nbins * 4 + 2 * kBorderThreads * 4 + kBorderThreads * 8;
     dim3 grid((unsigned)nframes), block(kBorderThreads);
-    if (bits <= 8)
-        hipLaunchKernelGGL(scan_border_kernel<uint8_t>, grid, block, lds, st, (const uint8_t*)dY, (const uint8_t*)dU,
-                           (const uint8_t*)dV, strideY, strideUV, pitchY, pitchUV, imgx, imgy, cx, cy, w, h, wUV, hUV, nbins, thy, dout);
-    else
-        hipLaunchKernelGGL(scan_border_kernel<uint16_t>, grid, block, lds, st, (const uint16_t*)dY, (const uint16_t*)dU,
-                           (const uint16_t*)dV, strideY, strideUV, pitchY, pitchUV, imgx, imgy, cx, cy, w, h, wUV, hUV, nbins, thy, dout);
+    with_sample_type(bits, [&](auto px) {
+        typedef decltype(px) pix_t;
+        hipLaunchKernelGGL(scan_border_kernel<pix_t>, grid, block, lds, st, (const pix_t*)b.Y, (const pix_t*)b.U, (const pix_t*)b.V, b.strideY,
+                           b.strideUV, b.pitchY, b.pitchUV, r.imgx, r.imgy, r.cx, r.cy, r.w, r.h, r.wUV, r.hUV, nbins, thy, dout);
+    });
     return hipGetLastError();
 }
 
@@ -511,9 +504,8 @@ void scan_accumulate_kernel(const pix_t* __restrict__ Y, const pix_t* __restrict
     }
 }
 
-hipError_t launch_scan_accumulate(hipStream_t st, int bits, const void* dY, const void* dU, const void* dV, long long strideY,
-                                  long long strideUV, int pitchY, int pitchUV, int imgx, int imgy, int cx, int cy, int w, int h,
-                                  int wUV, int hUV, const int4* daccepted, int naccepted, unsigned long long* dacc)
+hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, const int4* daccepted, int naccepted,
+                                  unsigned long long* dacc)
 {
     if (naccepted <= 0) return hipSuccess;
 #ifdef AMT_SCAN_ACC_FIXED32        // instrumented build: round 1's fixed 32 frames per workgroup
@@ -521,13 +513,12 @@ hipError_t launch_scan_accumulate(hipStream_t st, int bits, const void* dY, cons
 #else
     const int per = std::max(kAccMinFramesPerBlock, (naccepted + kAccFrameChunks - 1) / kAccFrameChunks);
 #endif
-    dim3 grid((unsigned)(h + 2 * hUV), (unsigned)((naccepted + per - 1) / per)), block(256);
-    if (bits <= 8)
-        hipLaunchKernelGGL(scan_accumulate_kernel<uint8_t>, grid, block, 0, st, (const uint8_t*)dY, (const uint8_t*)dU,
-                           (const uint8_t*)dV, strideY, strideUV, pitchY, pitchUV, imgx, imgy, cx, cy, w, h, wUV, hUV, daccepted, naccepted, per, dacc);
-    else
-        hipLaunchKernelGGL(scan_accumulate_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)dY, (const uint16_t*)dU,
-                           (const uint16_t*)dV, strideY, strideUV, pitchY, pitchUV, imgx, imgy, cx, cy, w, h, wUV, hUV, daccepted, naccepted, per, dacc);
+    dim3 grid((unsigned)(r.h + 2 * r.hUV), (unsigned)((naccepted + per - 1) / per)), block(256);
+    with_sample_type(bits, [&](auto px) {
+        typedef decltype(px) pix_t;
+        hipLaunchKernelGGL(scan_accumulate_kernel<pix_t>, grid, block, 0, st, (const pix_t*)b.Y, (const pix_t*)b.U, (const pix_t*)b.V, b.strideY,
+                           b.strideUV, b.pitchY, b.pitchUV, r.imgx, r.imgy, r.cx, r.cy, r.w, r.h, r.wUV, r.hUV, daccepted, naccepted, per, dacc);
+    });
     return hipGetLastError();
 }
 

@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "eval_plan.h"
+#include "kernels.hpp"
 #include "exact_math.h"
 #include "eval_ordered_sum.h"
 

@@ -11,19 +11,9 @@
 #include <algorithm>
 #include <cstdint>
 
-namespace amt {
+#include "kernels.hpp"
 
-struct WeaveArgs {
-    const uint8_t* srcY; const uint8_t* srcU; const uint8_t* srcV;   // decoded pictures (srcV unused for NV12)
-    long long src_strideY, src_strideUV;                             // bytes between pictures
-    int src_pitchY, src_pitchUV;                                     // bytes per source row
-    uint8_t* dstY; uint8_t* dstU; uint8_t* dstV;
-    long long dst_strideY, dst_strideUV;
-    int dst_pitchY, dst_pitchUV;                                     // bytes
-    int rowY, rowUV;                                                 // bytes per output row (width * es, widthUV * es)
-    int H, HUV;
-    int nv12, es, vec;                                               // vec: all rows 16-byte aligned
-};
+namespace amt {
 
 constexpr int kWeaveRows = 8;      // rows per workgroup (one wave per row, two rounds)
 
@@ -88,24 +78,23 @@ void ingest_rows_kernel(const uint8_t* __restrict__ src, long long src_stride, u
     }
 }
 
-hipError_t launch_ingest_rows(hipStream_t st, const void* src_host_mapped, long long src_stride, void* dst, long long dst_stride,
-                              unsigned long long chunk, long long nchunks)
+hipError_t launch_ingest_rows(hipStream_t st, const void* src, long long src_stride, void* dst, long long dst_stride, unsigned long long chunk,
+                              long long nchunks)
 {
     if (!chunk || nchunks <= 0) return hipSuccess;
-    const uintptr_t a = (uintptr_t)src_host_mapped | (uintptr_t)dst | (uintptr_t)src_stride | (uintptr_t)dst_stride | (uintptr_t)chunk;
+    const uintptr_t a = (uintptr_t)src | (uintptr_t)dst | (uintptr_t)src_stride | (uintptr_t)dst_stride | (uintptr_t)chunk;
     const int vb = (a % 16 == 0) ? 16 : (a % 4 == 0) ? 4 : 1;
     const long long total = (long long)(chunk / vb) * nchunks;
     // enough lanes in flight to cover the PCIe round trip (a few microseconds) at the link's rate, never more than the work
     const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 2048);
-    if (vb == 16)
-        hipLaunchKernelGGL(ingest_rows_kernel<uint4>, dim3(grid), dim3(256), 0, st, (const uint8_t*)src_host_mapped, src_stride, (uint8_t*)dst, dst_stride,
-                           (int)(chunk / 16), total);
-    else if (vb == 4)
-        hipLaunchKernelGGL(ingest_rows_kernel<uint32_t>, dim3(grid), dim3(256), 0, st, (const uint8_t*)src_host_mapped, src_stride, (uint8_t*)dst, dst_stride,
-                           (int)(chunk / 4), total);
-    else
-        hipLaunchKernelGGL(ingest_rows_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, (const uint8_t*)src_host_mapped, src_stride, (uint8_t*)dst, dst_stride,
-                           (int)chunk, total);
+    auto launch = [&](auto vec) {
+        typedef decltype(vec) V;
+        hipLaunchKernelGGL(ingest_rows_kernel<V>, dim3(grid), dim3(256), 0, st, (const uint8_t*)src, src_stride, (uint8_t*)dst, dst_stride,
+                           (int)(chunk / sizeof(V)), total);
+    };
+    if (vb == 16) launch(uint4());
+    else if (vb == 4) launch(uint32_t());
+    else launch(uint8_t());
     return hipGetLastError();
 }
 

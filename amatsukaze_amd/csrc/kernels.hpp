@@ -1,0 +1,143 @@
+// kernels.hpp -- the interface between the kernel files (*_kernels.hip) and the host code that launches them: every launcher is declared
+// here and nowhere else (default arguments too), and so is every struct both sides see.  Each kernel file includes it, so a definition
+// that has drifted from its declaration, or a second definition of a struct passed by value into a kernel, does not compile.
+// Kept light on purpose (no <vector>, <string>, <mutex>): it goes into translation units that are all device code.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "eval_plan.h"
+
+namespace amt {
+
+struct TileDesc; struct TileBandDesc;     // eval_tiles.hpp
+
+// ---- descriptors ----
+// A batch of planar 4:2:0 frames in HBM.  Strides (between frames) and pitches (between rows) are in SAMPLES: the host divides the
+// ABI's byte strides by the sample size once, where it builds the descriptor.
+struct PlaneBatch { const void *Y, *U, *V; long long strideY, strideUV; int pitchY, pitchUV; };
+// the same batch from frame `frames` on (es: bytes per sample)
+inline PlaneBatch plane_batch_from(const PlaneBatch& b, long long frames, int es)
+{
+    auto at = [&](const void* p, long long stride) { return (const void*)((const uint8_t*)p + frames * stride * es); };
+    return PlaneBatch{at(b.Y, b.strideY), at(b.U, b.strideUV), at(b.V, b.strideUV), b.strideY, b.strideUV, b.pitchY, b.pitchUV};
+}
+// the planes Delogo writes: laid out like the PlaneBatch it reads (the same planes for the in-place call)
+struct PlanesOut { void *Y, *U, *V; };
+// a 4:2:0 rectangle of a frame: origin and size in the luma plane, and in the chroma planes
+struct ScanRect { int imgx, imgy, cx, cy, w, h, wUV, hUV; };
+inline ScanRect scan_rect(int imgx, int imgy, int w, int h) { return ScanRect{imgx, imgy, imgx >> 1, imgy >> 1, w, h, w >> 1, h >> 1}; }
+
+// f(pix_t()) with the sample type of a clip `bits` deep: a launcher writes its kernel's argument list once, in a generic lambda
+template <typename F> inline void with_sample_type(int bits, F&& f) { bits <= 8 ? f(uint8_t()) : f(uint16_t()); }
+
+// ---- erase_scan_kernels.hip ----
+struct EraseGeom {
+    int w, h, wUV, hUV;
+    int imgx, imgy, cx, cy;       // rectangle origin in luma / chroma planes
+    int uvparity;
+};
+hipError_t launch_delogo(hipStream_t st, int bits, const PlaneBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g, int nframes,
+                         const float2* dfades, int zero_identity);
+hipError_t launch_calc_fades(hipStream_t st, const float* danalysis, int analysis_first, int analysis_count, int num_frames, int first,
+                             int nframes, const uint8_t* dstate, int half, float2* dout);
+// dout[frame] = {valid, bgY, bgU, bgV}
+hipError_t launch_scan_border(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, int thy, int nframes, int4* dout);
+// daccepted[i] = {frame, bgY, bgU, bgV}; dacc: 3 int64 per sample of the rectangle, added to
+hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, const int4* daccepted, int naccepted,
+                                  unsigned long long* dacc);
+
+// ---- ingest_kernels.hip ----
+struct WeaveArgs {
+    const uint8_t* srcY; const uint8_t* srcU; const uint8_t* srcV;   // decoded pictures (srcV unused for NV12)
+    long long src_strideY, src_strideUV;                             // bytes between pictures
+    int src_pitchY, src_pitchUV;                                     // bytes per source row
+    uint8_t* dstY; uint8_t* dstU; uint8_t* dstV;
+    long long dst_strideY, dst_strideUV;
+    int dst_pitchY, dst_pitchUV;                                     // bytes
+    int rowY, rowUV;                                                 // bytes per output row (width * es, widthUV * es)
+    int H, HUV;
+    int nv12, es, vec;                                               // vec: all rows 16-byte aligned
+};
+hipError_t launch_weave_fields(hipStream_t st, const WeaveArgs& a, const int* dtop_index, const int* dbottom_index, int nframes);
+// `nchunks` pieces of `chunk` bytes, src_stride apart at src (HBM, or page-locked host memory at its device address), dst_stride apart at dst
+hipError_t launch_ingest_rows(hipStream_t st, const void* src, long long src_stride, void* dst, long long dst_stride, unsigned long long chunk,
+                              long long nchunks);
+
+// ---- stats_kernels.hip, logofind_kernels.hip ----
+hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,
+                              const void* dprevY, int nframes, unsigned long long* dout);
+// Largest frame count of one launch_logofind: its uint32 partials hold at most 2 * maxv per frame (SM) below 2^31.
+long long logofind_launch_cap(int bits);
+// nframes <= logofind_launch_cap(bits) (the caller splits); dS1 / dSM: W*H int64 each, added to
+hipError_t launch_logofind(hipStream_t st, int bits, const void* dY, long long frame_stride, int pitch_elems, int W, int H, int nframes,
+                           int num_cus, unsigned long long* dS1, unsigned long long* dSM);
+
+// ---- eval_fused_kernels.hip, eval_pair_kernels.hip, eval_linear_kernels.hip ----
+// tile plan of one evaluation logo resident in HBM (eval_tiles.hpp; eval_pair_kernels.hip).  slot = (band * kTileWaves + wave) * 64 + lane
+struct TileLogoDev {
+    const float2* kp;            // [13][nslots]  taps of the slot's mask pixel as pairs {k[2j], k[2j+1]} (k[25] = 0), pair-major
+    const float2* sc;            // [32][nslots]  bin-major {scale, scale2} of the slot's mask pixel (the exact scan kernel)
+    const float2* pq;            // [nslots]      {P, Q}: the pixel's response on flat level c is |P + Q c| (the linear analysis kernel: no gathers)
+    const uint32_t* sinfo;       // [nslots]      tile_slot_info
+    const uint32_t* pos;         // [nslots]      (y << 16) | x of the slot's mask pixel in the evaluation logo (the linear kernel's exact bin check)
+    const TileDesc* tiles;       // [nbands * 8]
+    const TileBandDesc* bands;   // [nbands]
+    const int* tlist;            // [ntlist]  indices of the tiles that hold pixels (kernels that need no band order walk these)
+    int nbands, nslots, ntlist;
+    float floorResp;             // limitCorr of the logo (LogoScan.hpp:203)
+    // the linear kernel's copy of everything it loads per tile, in ONE allocation (one scalar base instead of five: its loop is short of
+    // scalar registers): kp at 0, then pq, sinfo, the evaluation logo's a and b planes at these byte offsets
+    const char* lin;
+    unsigned lin_pq, lin_sinfo, lin_a, lin_b;
+};
+// eval_fused_kernels.hip.  dnframes (device, optional): the number of frames actually present (<= nframes,
+// which then only sizes the grid); scatter != 0: frame i's results go to record dframe_map[i] of dout; fade_chunk > 0 (with dnframes):
+// a workgroup evaluates fade_chunk of the fades, the chunks of a (logo, frame group) run side by side -- a handful of listed frames
+// is a latency problem (one workgroup walking every band for all fades), not a throughput one
+hipError_t launch_logo_eval_fused(hipStream_t st, int bits, const EvalLogoDev* dlogos, int nlogos, const EvalBand* dbands,
+                                  const float* dfades, int nfades, int fade0, const void* dY, const int* dframe_map,
+                                  long long frame_stride_elems, int pitch, int nframes, int G, float* dout, int out_frame_stride,
+                                  int take_abs, int plane_cap, const int* dnframes = nullptr, int scatter = 0, int fade_chunk = 0);
+// eval_linear_kernels.hip
+hipError_t launch_logo_eval_linear(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
+                                   const float* dfades, int nfades, int fade0, const void* dY, const int* dframe_map,
+                                   long long frame_stride_elems, int pitch, int nframes, int G, float* dout, int out_frame_stride,
+                                   int take_abs, float bin_eps, int qlog2, int qcap, uint8_t* dforce);
+// eval_pair_kernels.hip: fades {0, 1} of every logo, bit-exact
+hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
+                                 const void* dY, const int* dframe_map, long long frame_stride_elems, int pitch,
+                                 int nframes, int G, float* dout, int out_frame_stride, int take_abs);
+// Sentinel monitor of AMTGPU_ANALYZE_LINEAR_MONITORED: persistent per-analyzer device state.  max_abs_bits: the largest |linear - exact| over
+// every compared score as float bits (non-negative floats order like unsigned ints; NaN counts as +inf); tripped: a comparison failed (sticky
+// until re-armed); frames_checked: sentinel frames compared; batches_tripped: batches in which a comparison failed
+struct MonitorState {
+    unsigned max_abs_bits;
+    int tripped;
+    unsigned long long frames_checked;
+    unsigned batches_tripped;
+    unsigned pad_;
+};
+// Sentinel arguments of the mark kernel (nsent = 0: none, the guarded mode).  The sentinels of a batch of nframes frames are
+// s_j = floor(j (nframes - 1) / (nsent - 1)), j < nsent (nsent = 1: frame 0); nsent <= nframes.  side: [nsent][stride] copy of their
+// linear records; side_forced: [nsent] their force byte; gate: [2] per-batch words the mark kernel zeroes (frames of the gated exact pass,
+// workgroups that tripped) -- analysis_sentinel_check_kernel sets them, later launches read them
+struct SentinelArgs {
+    int nsent = 0;
+    float* side = nullptr;
+    uint8_t* side_forced = nullptr;
+    int* gate = nullptr;
+};
+hipError_t launch_analysis_mark(hipStream_t st, const float* drec, int stride, int nframes, int ngroups, int nfades, const float* eps3,
+                                int* dlist, int* dcount, const uint8_t* dforce = nullptr, const SentinelArgs& sent = SentinelArgs());
+// compares the sentinels' exact records (rec, after the listed re-evaluation) with their saved linear copies; a failed comparison or an
+// earlier one (state->tripped) sets gate[0] = nframes and stores `epoch` to the host-mapped word `host_flag` (optional)
+hipError_t launch_analysis_sentinel_check(hipStream_t st, const float* drec, int stride, int nframes, const SentinelArgs& sent, float tol,
+                                          MonitorState* dstate, int* host_flag, int epoch);
+// list[i] = i for i < n (the identity list of the gated whole-batch re-evaluation)
+hipError_t launch_analysis_iota(hipStream_t st, int* dlist, int n);
+hipError_t launch_rect_range_flag(hipStream_t st, const void* dY, long long frame_stride_elems, int pitch, int imgx, int imgy, int w, int h, int bits,
+                                  int nframes, uint8_t* dflag);
+
+} // namespace amt

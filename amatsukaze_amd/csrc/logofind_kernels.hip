@@ -23,6 +23,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "kernels.hpp"
+
 namespace amt {
 
 constexpr int kLfRows = 8;              // rows of a tile (R); a lane loads R + 2
@@ -166,10 +168,8 @@ void logofind_kernel(const uint8_t* __restrict__ Y, long long frame_stride, int 
     }
 }
 
-// Largest frame count of one launch: uint32 partials hold at most 2 * maxv per frame (SM) below 2^31.
 long long logofind_launch_cap(int bits) { return (long long)((2147483647LL) / (2LL * ((1LL << bits) - 1))); }
 
-// nframes <= logofind_launch_cap(bits) (the caller splits); dS1 / dSM: W*H int64 each, added to
 hipError_t launch_logofind(hipStream_t st, int bits, const void* dY, long long frame_stride, int pitch_elems, int W, int H, int nframes,
                            int num_cus, unsigned long long* dS1, unsigned long long* dSM)
 {

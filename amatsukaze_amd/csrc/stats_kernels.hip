@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "kernels.hpp"
+
 namespace amt {
 
 // (tried and closed, profiles/r04_notes.md: waves of a workgroup stacked on vertically adjacent tiles -- the halo re-reads already hit
