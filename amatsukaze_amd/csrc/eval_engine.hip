@@ -288,7 +288,9 @@ void EvalEngine::ensure_tiles()
     for (int i = 0; i < nl; ++i) {
         const EvalLogoSpec& S = specs_[i];
         const MaskTables& T = S.tables;
-        const TilePlan P = build_tile_plan(T.pos, T.count, S.planes.w, S.planes.h);
+        // (the scan -- fades {0, 1}: the pair kernel, raster-order sums -- takes the cut with the lower modelled critical path; every
+        //  other engine keeps the coarse cut: the linear kernel's summation order follows the tiles)
+        const TilePlan P = build_tile_plan(T.pos, T.count, S.planes.w, S.planes.h, fades_.size() == 2 ? kTileCutBest : kTileCutCoarse);
         const size_t ns = (size_t)P.nslots();
         std::vector<float2> kp(13 * ns, float2{0.0f, 0.0f}), sc((size_t)kNumBins * ns, float2{0.0f, 0.0f}), pq(ns, float2{0.0f, 0.0f});
         std::vector<uint32_t> spos(ns, 0u);

@@ -146,7 +146,8 @@ void logo_eval_pair_kernel(const PairLaunch A)
     }
 
     // ---------------- evaluation waves ----------------
-    const gptr_t gSc = (gptr_t)Xp->sc;
+    typedef const __attribute__((address_space(4))) TileLogoDev* tlogo_ptr;          // (wave-uniform table bases: scalar loads, once)
+    const gptr_t gSc = (gptr_t)Xp->sc, gK = (gptr_t)((tlogo_ptr)Xp)->kp, gInfo = (gptr_t)((tlogo_ptr)Xp)->sinfo;
     const unsigned nslots8 = (unsigned)Xp->nslots * 8u;
     const const_tile_ptr tiles = (const_tile_ptr)(Xp->tiles + wave);
     f2* const myplane = planes + wave * kTileCap;
@@ -163,7 +164,8 @@ void logo_eval_pair_kernel(const PairLaunch A)
     //  compiler places at the loop head for them is the merge of this path and the back edge -- with the raw loads sunk below the 14
     //  pixel / tap loads it became vmcnt(0) in every iteration, which also waits for the scale gathers issued just before)
     asm volatile("" ::: "memory");
-    px.load(Xp, (unsigned)wave * 64u + (unsigned)lane, T, plane_base);
+    px.load(gK, gInfo, nslots8, (unsigned)wave * 64u + (unsigned)lane, T, plane_base);
+    st.coefs_landed();
 
     // the terms of an evaluation are formed one iteration later, when its two scale gathers have long arrived
     f2 pR = {0.0f, 0.0f}, psc0 = pR, psc1 = pR;
@@ -238,9 +240,14 @@ void logo_eval_pair_kernel(const PairLaunch A)
         if (band_end) {
             flush_terms();                                           // the band's rows are complete before the waves meet
             pact = false;
-            // the band's last evaluation is done: the next band's pixel and taps travel across the barrier
+            // the band's last evaluation is done.  Its terms have just waited for their scale gathers and, as vector-memory loads return in
+            // order, for the next tile's logo coefficients (requested in step 2, a whole evaluation ago): b * maxv is formed here
+            // without a wait of its own.  Then the next band's pixel and taps travel across the barrier
             ++b; g = 0;
-            if (b < nbands) px.load(Xp, (unsigned)(b * kTileWaves + wave) * 64u + (unsigned)lane, T, plane_base);
+            if (b < nbands) {
+                st.coefs_landed();
+                px.load(gK, gInfo, nslots8, (unsigned)(b * kTileWaves + wave) * 64u + (unsigned)lane, T, plane_base);
+            }
             AMT_PTICK(4);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             AMT_PTICK(5);

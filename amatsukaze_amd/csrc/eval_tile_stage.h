@@ -265,7 +265,7 @@ template <typename pix_t, bool AB_LDS = false, bool SLIM = false, bool BLEND = t
     int ulds[kTileUnits];            // pair offset in the tile plane
     int ug[kTileUnits][3];           // byte offsets in a frame of the rows above / at / below the unit
     unsigned ubias[kTileUnits];
-    f4 ua[kTileUnits], ubmv[kTileUnits];                        // the unit's logo coefficients: a, b * maxv
+    f4 ua[kTileUnits], ubmv[kTileUnits];                        // the unit's logo coefficients: a, b * maxv (b until coefs_landed())
     Quad<pix_t> raw[kTileUnits][3];
 
     __device__ __forceinline__ void init(const EvalLogoDev* Lp, int pitch, float maxv_, f2* plane_, f2* abplane_ = nullptr)
@@ -293,14 +293,25 @@ template <typename pix_t, bool AB_LDS = false, bool SLIM = false, bool BLEND = t
             }
             typedef f4 __attribute__((aligned(8))) f4a8;
             const f4 av = gld<f4a8>(gA, (unsigned)(U.y * w + U.xs) * 4u);
-            const f4 bmv = gld<f4a8>(gB, (unsigned)(U.y * w + U.xs) * 4u) * maxv;     // rounded once, exactly as in a*s + b*maxv
+            f4 bmv = gld<f4a8>(gB, (unsigned)(U.y * w + U.xs) * 4u);
             if (AB_LDS) {
+                bmv = bmv * maxv;                                              // rounded once, exactly as in a*s + b*maxv
                 f4* d = reinterpret_cast<f4*>(abplane + U.lds);
                 d[0] = f4{av[0], bmv[0], av[1], bmv[1]};
                 d[1] = f4{av[2], bmv[2], av[3], bmv[3]};
             } else {
                 ua[k] = av; ubmv[k] = bmv;
             }
+        }
+    }
+    // b -> b * maxv, rounded once, exactly as in a*s + b*maxv: called once between setup_units() and the next convert(), at a point where
+    // the coefficient loads have had time to land.  Formed in setup_units() itself the product waits for the loads right behind their
+    // issue -- in front of the raw request and of the whole evaluation that could have covered them.
+    __device__ __forceinline__ void coefs_landed()
+    {
+        if (!AB_LDS) {
+#pragma unroll
+            for (int k = 0; k < kTileUnits; ++k) ubmv[k] = ubmv[k] * maxv;
         }
     }
     // frame = buffer descriptor of the source frame (whole plane: 32-bit byte offsets, checked on the host)
@@ -367,10 +378,10 @@ struct TilePixel {
     bool act;
     unsigned slot8;
     unsigned slotbase8;              // (wave-uniform) slot8 of lane 0: slot8 == slotbase8 + 8 * lane, for kernels short of registers
-    __device__ __forceinline__ void load(const TileLogoDev* Xp, unsigned slot, const TileDesc& T, unsigned plane_base)
+    // gK, gInfo, nslots8: TileLogoDev::kp / sinfo / 8 * nslots, fetched ONCE by the caller -- read here, at every band's end, they are vector
+    // loads of their own that the taps' addresses wait for: a second memory round trip in front of the one that matters
+    __device__ __forceinline__ void load(gptr_t gK, gptr_t gInfo, unsigned nslots8, unsigned slot, const TileDesc& T, unsigned plane_base)
     {
-        const gptr_t gK = (gptr_t)Xp->kp, gInfo = (gptr_t)Xp->sinfo;
-        const unsigned nslots8 = (unsigned)Xp->nslots * 8u;
         const unsigned si = gld<unsigned>(gInfo, slot * 4u);
         w0 = plane_base + (si & 0xFFFu) * 8u;                     // idle lanes: the tile's first window (zero taps, never written out)
         tp8 = (unsigned)T.tp * 8u;

@@ -94,8 +94,15 @@ struct TilePlan {
     std::vector<TileDesc> tiles;          // bands.size() * kTileWaves
     std::vector<uint32_t> sinfo;          // per slot: window offset in the tile (pairs, bits 0-11), index in the band's score row (bits 12-23), valid (bit 31)
     std::vector<int> slot_pixel;          // per slot: mask pixel m, -1 for an idle lane
+    long long model_cost = 0;             // modelled critical path: per band the busiest SIMD's sum of its tiles' 131 + 31 * passes
     int nslots() const { return (int)sinfo.size(); }
 };
+// How the bands are cut.  Coarse: an over-full band (more than kTileWaves tiles) loses an eighth of its pixels at a time.  Fine: four
+// at a time -- the largest band on that grid that fits -- and a last band of less than one tile's pixels joins the one before it
+// where that still fits.  Best: whichever of the two has the lower modelled critical path (the coarse one when they tie).
+// A kernel that adds its terms in raster order (the scan's) computes the same records under every cut; the linear analysis kernel's
+// summation order follows the tiles, so it keeps the coarse cut its records were established with.
+enum TileCut { kTileCutCoarse, kTileCutFine, kTileCutBest };
 
 namespace tiles_detail {
 
@@ -160,31 +167,57 @@ inline bool fits(const Geometry& G) { return G.nrows * G.ncol4 * 4 <= kTileCap &
 
 } // namespace tiles_detail
 
+namespace tiles_detail {
+
+// the band's pixels [m, m + n) by column, then row, dealt 64 at a time: a wave's pixels cover few columns and all of the band's rows
+inline std::vector<std::vector<Px>> deal_band(const std::vector<uint32_t>& pos, int m, int n)
+{
+    std::vector<Px> px(n);
+    for (int i = 0; i < n; ++i) px[i] = Px{(int)(pos[m + i] & 0xFFFFu), (int)(pos[m + i] >> 16), m + i};
+    std::stable_sort(px.begin(), px.end(), [](const Px& a, const Px& b) { return a.x < b.x; });
+    std::vector<std::vector<Px>> groups;
+    for (size_t a = 0; a < px.size();) {
+        size_t b = a + 1;
+        while (b < px.size() && b - a < (size_t)kTileLanes && fits(bbox(px, a, b + 1))) ++b;
+        groups.emplace_back(px.begin() + a, px.begin() + b);
+        a = b;
+    }
+    return groups;
+}
+// pixels per band
+inline std::vector<int> cut_bands(const std::vector<uint32_t>& pos, int count, bool fine)
+{
+    std::vector<int> cuts;
+    for (int m = 0; m < count;) {
+        int n = std::min(kTileBandPix, count - m);
+        while ((int)deal_band(pos, m, n).size() > kTileWaves)          // sparse stretch: a shorter band
+            n = fine ? std::max(1, n - 4) : std::max(1, n - std::max(1, n / 8));
+        cuts.push_back(n);
+        m += n;
+    }
+    if (fine && cuts.size() >= 2 && cuts.back() < kTileLanes) {
+        const int n = cuts[cuts.size() - 2] + cuts.back();
+        if (n <= kTileBandPix && (int)deal_band(pos, count - n, n).size() <= kTileWaves) { cuts.pop_back(); cuts.back() = n; }
+    }
+    return cuts;
+}
+
+} // namespace tiles_detail
+
 // pos[m] = (y << 16) | x of mask pixel m in raster order (MaskTables::pos); every pixel has 2 <= x < w-2, 2 <= y < h-2, w >= 5
-inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int w, int h)
+inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int w, int h, TileCut cut = kTileCutCoarse)
 {
     using namespace tiles_detail;
     (void)h;
     if (w < 5) throw std::runtime_error("logo too narrow for the tile kernel");
+    if (cut == kTileCutBest) {
+        TilePlan coarse = build_tile_plan(pos, count, w, h, kTileCutCoarse), fine = build_tile_plan(pos, count, w, h, kTileCutFine);
+        return fine.model_cost < coarse.model_cost ? fine : coarse;
+    }
     TilePlan P;
-    for (int m = 0; m < count;) {
-        int n = std::min(kTileBandPix, count - m);
-        std::vector<std::vector<Px>> groups;
-        for (;;) {
-            // the band's pixels by column, then row: a wave's 64 pixels cover few columns and all of the band's rows
-            std::vector<Px> px(n);
-            for (int i = 0; i < n; ++i) px[i] = Px{(int)(pos[m + i] & 0xFFFFu), (int)(pos[m + i] >> 16), m + i};
-            std::stable_sort(px.begin(), px.end(), [](const Px& a, const Px& b) { return a.x < b.x; });
-            groups.clear();
-            for (size_t a = 0; a < px.size();) {
-                size_t b = a + 1;
-                while (b < px.size() && b - a < (size_t)kTileLanes && fits(bbox(px, a, b + 1))) ++b;
-                groups.emplace_back(px.begin() + a, px.begin() + b);
-                a = b;
-            }
-            if ((int)groups.size() <= kTileWaves) break;
-            n = std::max(1, n - std::max(1, n / 8));       // sparse stretch: a shorter band
-        }
+    int m = 0;
+    for (const int n : cut_bands(pos, count, cut == kTileCutFine)) {
+        std::vector<std::vector<Px>> groups = deal_band(pos, m, n);
         // Which wave takes which tile is free.  Waves are dealt to the CU's four SIMDs round-robin (wave w on SIMD w % 4: with eleven
         // evaluation waves three each on SIMDs 0-2, two and the summing wave on SIMD 3), a SIMD issues for one wave at a time, and a
         // tile with more than 64 staging units costs a second staging pass: the tiles go heaviest first to the SIMD with the least
@@ -204,6 +237,7 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
                 placed[best + 4 * used[best]] = groups[i];
                 load[best] += cost(i); ++used[best];
             }
+            P.model_cost += *std::max_element(load, load + 4);
             groups.swap(placed);                                  // (a wave without a tile keeps an empty group: npix 0, it idles through the band)
         }
         const int band = (int)P.bands.size();
