@@ -19,10 +19,9 @@
 #error "an instrumentation macro (AMT_*_TIMING / AMT_TRACE_* / AMT_EXPERIMENT / AMT_SAME_STREAM) is defined outside an instrumented build (amatsukaze_amd/build.py build_variant)"
 #endif
 #if defined(AMT_LIN_G) || defined(AMT_LIN_G16) || defined(AMT_LIN_OCC) || defined(AMT_LIN_OCC16) || defined(AMT_LIN_WAVES) || defined(AMT_LIN_WGS_MIN16) || \
-    defined(AMT_TILE_WAVES) || defined(AMT_TILE_G) || defined(AMT_PAIR_OCC) || defined(AMT_FUSED_OCC) || defined(AMT_FUSED_BG_LDS) || defined(AMT_LISTED_FADE_CHUNK) || \
-    defined(AMT_STATS_ROWS) || defined(AMT_STATS_ROWS8) || defined(AMT_STATS_RUN) || defined(AMT_STATS_COLB) || defined(AMT_STATS_LEAN) || defined(AMT_STATS_PINGPONG) || \
-    defined(AMT_STATS_DEAL) || defined(AMT_STATS_NT) || defined(AMT_STATS_OCC) || defined(AMT_STATS_WAVES) || defined(AMT_STATS_LDS_BYTES) || \
-    defined(AMT_DELOGO_ROWS) || defined(AMT_DELOGO_FRAMES) || defined(AMT_SCAN_ACC_FIXED32) || defined(AMT_WG_PLAIN_MAP)
+    defined(AMT_TILE_WAVES) || defined(AMT_TILE_G) || defined(AMT_PAIR_OCC) || defined(AMT_FUSED_OCC) || defined(AMT_LISTED_FADE_CHUNK) || \
+    defined(AMT_STATS_ROWS) || defined(AMT_STATS_ROWS8) || defined(AMT_STATS_RUN) || defined(AMT_STATS_NT) || defined(AMT_STATS_OCC) || defined(AMT_STATS_WAVES) || \
+    defined(AMT_DELOGO_ROWS) || defined(AMT_DELOGO_FRAMES)
 #error "a shape / tuning macro of the kernels is defined on the command line: the release library is built with the defaults in the sources (instrumented variants: amatsukaze_amd/build.py build_variant)"
 #endif
 #endif

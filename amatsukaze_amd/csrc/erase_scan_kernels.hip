@@ -508,11 +508,7 @@ hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b,
                                   unsigned long long* dacc)
 {
     if (naccepted <= 0) return hipSuccess;
-#ifdef AMT_SCAN_ACC_FIXED32        // instrumented build: round 1's fixed 32 frames per workgroup
-    const int per = kAccMinFramesPerBlock;
-#else
     const int per = std::max(kAccMinFramesPerBlock, (naccepted + kAccFrameChunks - 1) / kAccFrameChunks);
-#endif
     dim3 grid((unsigned)(r.h + 2 * r.hUV), (unsigned)((naccepted + per - 1) / per)), block(256);
     with_sample_type(bits, [&](auto px) {
         typedef decltype(px) pix_t;

@@ -33,37 +33,12 @@
 #include "eval_plan.h"
 #include "kernels.hpp"
 #include "exact_math.h"
+#include "eval_lds_stage.h"
 #include "eval_ordered_sum.h"
 
 namespace amt {
 
-typedef const __attribute__((address_space(1))) char* gptr_t;
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef f4 __attribute__((aligned(4))) f4u;
-template <typename T> __device__ __forceinline__ T gld(gptr_t base, unsigned byteoff)
-{
-    return *reinterpret_cast<const __attribute__((address_space(1))) T*>(base + byteoff);
-}
-__device__ __forceinline__ f2 bc_lo(f2 v) { return __builtin_shufflevector(v, v, 0, 0); }
-__device__ __forceinline__ f2 bc_hi(f2 v) { return __builtin_shufflevector(v, v, 1, 1); }
-// exact_math.h score_bin in 5 instructions: clamping to [0,255] BEFORE the truncation gives the same bin as cvttss2si + clamp
-// for everything below 2^31 (negative and NaN -> 0: v_med3_f32 returns the minimum when an input is NaN); at and above 2^31
-// cvttss2si yields INT_MIN, i.e. bin 0, not 31
-__device__ __forceinline__ int score_bin_dev(float mean)
-{
-    const int bin = (int)__builtin_amdgcn_fmed3f(mean, 0.0f, 255.0f) >> 3;
-    return mean >= 2147483648.0f ? 0 : bin;
-}
-// x / 25 for both halves (exact_math.h div25, packed)
-__device__ __forceinline__ f2 div25_pk(f2 x)
-{
-    const f2 z = {0.04f, 0.04f};
-    const f2 q = x * z;
-    const f2 r = __builtin_elementwise_fma(f2{-25.0f, -25.0f}, q, x);
-    return __builtin_elementwise_fma(r, z, q);
-}
+using namespace lin;
 
 // four adjacent samples of a frame row in one load
 template <typename pix_t> struct Raw4;
@@ -89,12 +64,6 @@ __device__ __forceinline__ void Raw4<uint16_t>::load(gptr_t base, unsigned byteo
     v = *reinterpret_cast<const __attribute__((address_space(1))) ua_t*>(base + byteoff);
 }
 
-// AMT_FUSED_BG_LDS: the background-estimate window is NOT kept in registers across the fade loop; every fade reads it from the LDS
-// plane straight into the registers its blend is formed in (15 two-dword reads).  30 VGPRs less -> three waves per SIMD instead of
-// two; the price is LDS traffic inside the loop.
-#ifndef AMT_FUSED_BG_LDS
-#define AMT_FUSED_BG_LDS 0
-#endif
 constexpr int kFusedWaves = kEvalThreads / 64;
 constexpr int kStageRows = 4;         // rows a staging wave handles per trip
 
@@ -272,16 +241,9 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
             for (int fr = 0; fr < FPI; ++fr) {
             if (fr >= nfr) break;
             // ---- 4. windows -> registers: per row the column pairs (1,2) (3,4) (0,5) ----
-            f2 S[15];
-#if !AMT_FUSED_BG_LDS
-            f2 BG[15];
-#endif
+            f2 S[15], BG[15];
             const float* const planeS = planes + fr * 2 * plane_cap;
             const float* const planeB = planeS + plane_cap;
-            unsigned bgrow[5];                                   // LDS byte addresses of the five rows of the bg window
-#pragma unroll
-            for (int r = 0; r < 5; ++r)
-                bgrow[r] = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)(planeB + woff + r * lp);
             if (act) {
 #pragma unroll
                 for (int r = 0; r < 5; ++r) {
@@ -289,12 +251,10 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
                     S[3 * r + 0] = f2{ps[1], ps[2]};
                     S[3 * r + 1] = f2{ps[3], ps[4]};
                     S[3 * r + 2] = f2{ps[0], ps[5]};
-#if !AMT_FUSED_BG_LDS
                     const float* pb = planeB + woff + r * lp;
                     BG[3 * r + 0] = f2{pb[1], pb[2]};
                     BG[3 * r + 1] = f2{pb[3], pb[4]};
                     BG[3 * r + 2] = f2{pb[0], pb[5]};
-#endif
                 }
             }
 #ifdef AMT_FUSED_TIMING
@@ -308,22 +268,8 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
                     const float fade = __builtin_bit_cast(float, __builtin_amdgcn_readlane(fade_bits, f));   // no memory op in the loop
                     const float omf = 1 - fade;
                     f2 W[15];
-#if AMT_FUSED_BG_LDS
-                    // the bg window lands in the registers its blend is formed in: column pairs (1,2) (3,4) (0,5) of every row
-#pragma unroll
-                    for (int r = 0; r < 5; ++r)
-                        asm volatile("ds_read2_b32 %0, %3 offset0:1 offset1:2\n\tds_read2_b32 %1, %3 offset0:3 offset1:4\n\t"
-                                     "ds_read2_b32 %2, %3 offset1:5"
-                                     : "=&v"(W[3 * r]), "=&v"(W[3 * r + 1]), "=&v"(W[3 * r + 2]) : "v"(bgrow[r]) : "memory");
-                    asm volatile("s_waitcnt lgkmcnt(0)"
-                                 : "+v"(W[0]), "+v"(W[1]), "+v"(W[2]), "+v"(W[3]), "+v"(W[4]), "+v"(W[5]), "+v"(W[6]), "+v"(W[7]), "+v"(W[8]), "+v"(W[9]),
-                                   "+v"(W[10]), "+v"(W[11]), "+v"(W[12]), "+v"(W[13]), "+v"(W[14]) : : "memory");
-#pragma unroll
-                    for (int i = 0; i < 15; ++i) W[i] = W[i] * fade + S[i] * omf;       // fade*bg + (1-fade)*s
-#else
 #pragma unroll
                     for (int i = 0; i < 15; ++i) W[i] = BG[i] * fade + S[i] * omf;      // fade*bg + (1-fade)*s
-#endif
                     // column sums ((r0+r1)+(r2+r3))+r4 for the column pairs
                     const f2 CA = ((W[0] + W[3]) + (W[6] + W[9])) + W[12];               // cols 1,2
                     const f2 CB = ((W[1] + W[4]) + (W[7] + W[10])) + W[13];              // cols 3,4
@@ -413,11 +359,7 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
 // <= 256 VGPRs: two waves per SIMD, nothing spilled (the fade loop alone holds ~200 live registers: taps 50, the two
 // windows 60, their blend 30, two alternating result/gather sets).  Three waves per SIMD (<= 168) spills taps to
 // scratch inside the fade loop and measured 2.6x slower.
-#if AMT_FUSED_BG_LDS
-#define AMT_FUSED_OCC 3
-#else
 #define AMT_FUSED_OCC 2
-#endif
 template <typename pix_t, int FPI>
 __global__ __launch_bounds__(kEvalThreads) __attribute__((amdgpu_waves_per_eu(AMT_FUSED_OCC, AMT_FUSED_OCC)))
 void logo_eval_fused_kernel(const EvalLogoDev* __restrict__ logos, const EvalBand* __restrict__ bands, const float* __restrict__ fades,

@@ -190,8 +190,10 @@ __device__ __forceinline__ f2 pk_fma_hi_lo_v(f2 a, f2 v)
     return r;
 }
 
-// One wave's staging state (eval_tile_stage.h TileStager, SLIM form) with the loads above.  BLEND = false: a field logo, whose rows are
-// the source rows themselves (CopyY): one row load per unit instead of three, no [1 2 1] sums.
+// One wave's staging state, as eval_tile_stage.h's TileStager but with the loads above and fewer registers: only the unit's own row
+// offset is kept -- the rows above / below are re-derived at every request -- and "this row is blended" rides in the sign bit of the
+// unit's LDS offset.  BLEND = false: a field logo, whose rows are the source rows themselves (CopyY): one row load per unit instead of
+// three, no [1 2 1] sums.
 template <typename pix_t, bool BLEND> struct LinStager {
     static constexpr int ES = (int)sizeof(pix_t);
     static constexpr int kRowsPerUnit = BLEND ? 3 : 1;

@@ -34,7 +34,6 @@ struct EvalLogoDev {
     int lp;                  // LDS row pitch in floats: ((w+31)&~31)+8
 };
 
-constexpr int kLinMaxFades = 12;    // fades the linear kernel's source is written for (11 for AMTAnalyzeLogo, the instantiated case)
 // Most frames a workgroup of the linear kernel takes; how many it does take follows from the LDS its list of bin checks leaves
 // (EvalEngine::run_linear: FOUR workgroups of four waves share a CU's 160 KB).
 #ifndef AMT_LIN_G

@@ -48,15 +48,9 @@ __device__ __forceinline__ void window_rows_ready(f2 (&W)[25])
 }
 // window reads + {mean(s), mean(bg)} in the reference's order: the column sums ((r0+r1)+(r2+r3))+r4 (ComputeKernel.cpp:88-94) start
 // as the rows arrive, then hsum256_ps' order and /25 (ComputeKernel.cpp:54-74,98)
-__device__ __forceinline__ f2 window_means_as_rows_land(f2 (&W)[25]);
 __device__ __forceinline__ f2 window_load_means(const unsigned (&wrow)[5], f2 (&W)[25])
 {
     window_reads(wrow, W);
-    return window_means_as_rows_land(W);
-}
-// ... the second half on its own, for callers that issue window_reads() earlier (and nothing but vector-memory requests in between)
-__device__ __forceinline__ f2 window_means_as_rows_land(f2 (&W)[25])
-{
     f2 c01[5], c[5];
     window_rows_ready<15, 0, 2>(W);
 #pragma unroll
@@ -247,19 +241,15 @@ __device__ __forceinline__ void fetch_tile(TileDesc& D, const_tile_ptr t)
 // last unit repeat it (same loads, same values stored to the same place).  No branch DEFINES these registers: a value that is only
 // conditionally loaded gets copied at the join, and the copy waits for the load right behind its issue -- the prefetch distance
 // would be gone.  Only the conversion of the units beyond the first 64 is skipped for small tiles.
-// AB_LDS: the units' logo coefficients live in a second LDS plane of the wave ({a, b*maxv} at the unit's tile offset) instead of in
-// 16 registers -- for kernels that are short of registers.
-// SLIM: the byte offsets of the rows above / below a unit are re-derived at every request (4 more instructions) instead of kept (4
-// registers), and "this row is blended" rides in the sign bit of the unit's LDS offset instead of in a register of its own.
-// BLEND = false: a logo whose rows are never blended (field logos: CopyY) -- one row load per unit instead of three, no [1 2 1] sums.
-template <typename pix_t, bool AB_LDS = false, bool SLIM = false, bool BLEND = true> struct TileStager {
+// Everything a unit needs is kept in registers: its three row offsets, its bias and its logo coefficients (a, b * maxv).  Every unit
+// loads three rows and goes through the [1 2 1] sum; a row that is not blended loads the same row three times with bias 0 (Quad).
+template <typename pix_t> struct TileStager {
     static constexpr int ES = (int)sizeof(pix_t);
     // (wave-uniform)
     int w, h, deint, srow0, srow_step, scol0, pitchB;
     float maxv;
     gptr_t gA, gB;
     f2* plane;
-    f2* abplane;                     // AB_LDS only
     bool second_pass;                // the tile has more than 64 units
     // (per lane)
     int ulds[kTileUnits];            // pair offset in the tile plane
@@ -268,9 +258,8 @@ template <typename pix_t, bool AB_LDS = false, bool SLIM = false, bool BLEND = t
     f4 ua[kTileUnits], ubmv[kTileUnits];                        // the unit's logo coefficients: a, b * maxv (b until coefs_landed())
     Quad<pix_t> raw[kTileUnits][3];
 
-    __device__ __forceinline__ void init(const EvalLogoDev* Lp, int pitch, float maxv_, f2* plane_, f2* abplane_ = nullptr)
+    __device__ __forceinline__ void init(const EvalLogoDev* Lp, int pitch, float maxv_, f2* plane_)
     {
-        abplane = abplane_;
         w = Lp->w; h = Lp->h; deint = Lp->deint;
         srow0 = Lp->imgy + Lp->row0; srow_step = Lp->row_step; scol0 = Lp->imgx;
         gA = (gptr_t)Lp->a; gB = (gptr_t)Lp->b;
@@ -283,25 +272,15 @@ template <typename pix_t, bool AB_LDS = false, bool SLIM = false, bool BLEND = t
 #pragma unroll
         for (int k = 0; k < kTileUnits; ++k) {
             const TileUnit U = tile_unit(T, lane + 64 * k, w);
-            const bool blend = BLEND && deint && U.y > 0 && U.y < h - 1;       // DeintY copies the first and the last row (LogoScan.hpp:763-780)
-            ulds[k] = SLIM ? (U.lds | (blend ? (int)0x80000000 : 0)) : U.lds;
-            if (!SLIM) ubias[k] = blend ? Quad<pix_t>::kBias : 0u;
+            const bool blend = deint && U.y > 0 && U.y < h - 1;       // DeintY copies the first and the last row (LogoScan.hpp:763-780)
+            ulds[k] = U.lds;
+            ubias[k] = blend ? Quad<pix_t>::kBias : 0u;
             ug[k][1] = (srow0 + U.y * srow_step) * pitchB + (scol0 + U.xs) * ES;
-            if (!SLIM) {
-                ug[k][0] = blend ? ug[k][1] - pitchB : ug[k][1];
-                ug[k][2] = blend ? ug[k][1] + pitchB : ug[k][1];
-            }
+            ug[k][0] = blend ? ug[k][1] - pitchB : ug[k][1];
+            ug[k][2] = blend ? ug[k][1] + pitchB : ug[k][1];
             typedef f4 __attribute__((aligned(8))) f4a8;
-            const f4 av = gld<f4a8>(gA, (unsigned)(U.y * w + U.xs) * 4u);
-            f4 bmv = gld<f4a8>(gB, (unsigned)(U.y * w + U.xs) * 4u);
-            if (AB_LDS) {
-                bmv = bmv * maxv;                                              // rounded once, exactly as in a*s + b*maxv
-                f4* d = reinterpret_cast<f4*>(abplane + U.lds);
-                d[0] = f4{av[0], bmv[0], av[1], bmv[1]};
-                d[1] = f4{av[2], bmv[2], av[3], bmv[3]};
-            } else {
-                ua[k] = av; ubmv[k] = bmv;
-            }
+            ua[k] = gld<f4a8>(gA, (unsigned)(U.y * w + U.xs) * 4u);
+            ubmv[k] = gld<f4a8>(gB, (unsigned)(U.y * w + U.xs) * 4u);
         }
     }
     // b -> b * maxv, rounded once, exactly as in a*s + b*maxv: called once between setup_units() and the next convert(), at a point where
@@ -309,47 +288,26 @@ template <typename pix_t, bool AB_LDS = false, bool SLIM = false, bool BLEND = t
     // issue -- in front of the raw request and of the whole evaluation that could have covered them.
     __device__ __forceinline__ void coefs_landed()
     {
-        if (!AB_LDS) {
 #pragma unroll
-            for (int k = 0; k < kTileUnits; ++k) ubmv[k] = ubmv[k] * maxv;
-        }
+        for (int k = 0; k < kTileUnits; ++k) ubmv[k] = ubmv[k] * maxv;
     }
     // frame = buffer descriptor of the source frame (whole plane: 32-bit byte offsets, checked on the host)
     __device__ __forceinline__ void request(const __amdgpu_buffer_rsrc_t frame)
     {
 #pragma unroll
         for (int k = 0; k < kTileUnits; ++k) {
-            if (!BLEND) {
-                raw[k][1].load(frame, ug[k][1]);
-            } else if (SLIM) {
-                const int d = (ulds[k] >> 31) & pitchB;           // a blended row: the rows above and below; otherwise the row itself
-                raw[k][0].load(frame, ug[k][1] - d);
-                raw[k][1].load(frame, ug[k][1]);
-                raw[k][2].load(frame, ug[k][1] + d);
-            } else {
 #pragma unroll
-                for (int j = 0; j < 3; ++j) raw[k][j].load(frame, ug[k][j]);
-            }
+            for (int j = 0; j < 3; ++j) raw[k][j].load(frame, ug[k][j]);
         }
     }
     // raw samples -> {s, bg = a*s + b*maxv} pairs (LogoScan.hpp:247)
     __device__ __forceinline__ void convert_unit(int k)
     {
         float sv[4];
-        const unsigned bias = SLIM ? ((unsigned)(ulds[k] >> 31) & Quad<pix_t>::kBias) : ubias[k];
-        const int lds = SLIM ? (ulds[k] & 0x7FFFFFFF) : ulds[k];
-        if (BLEND) Quad<pix_t>::blend(raw[k][0], raw[k][1], raw[k][2], bias, sv);
-        else Quad<pix_t>::copy(raw[k][1], sv);
-        f2* dst = plane + lds;
-        if (AB_LDS) {
-            const f4* c = reinterpret_cast<const f4*>(abplane + lds);
-            const f4 c0 = c[0], c1 = c[1];
-            reinterpret_cast<f4*>(dst)[0] = f4{sv[0], c0[0] * sv[0] + c0[1], sv[1], c0[2] * sv[1] + c0[3]};
-            reinterpret_cast<f4*>(dst)[1] = f4{sv[2], c1[0] * sv[2] + c1[1], sv[3], c1[2] * sv[3] + c1[3]};
-        } else {
-            reinterpret_cast<f4*>(dst)[0] = f4{sv[0], ua[k][0] * sv[0] + ubmv[k][0], sv[1], ua[k][1] * sv[1] + ubmv[k][1]};
-            reinterpret_cast<f4*>(dst)[1] = f4{sv[2], ua[k][2] * sv[2] + ubmv[k][2], sv[3], ua[k][3] * sv[3] + ubmv[k][3]};
-        }
+        Quad<pix_t>::blend(raw[k][0], raw[k][1], raw[k][2], ubias[k], sv);
+        f2* dst = plane + ulds[k];
+        reinterpret_cast<f4*>(dst)[0] = f4{sv[0], ua[k][0] * sv[0] + ubmv[k][0], sv[1], ua[k][1] * sv[1] + ubmv[k][1]};
+        reinterpret_cast<f4*>(dst)[1] = f4{sv[2], ua[k][2] * sv[2] + ubmv[k][2], sv[3], ua[k][3] * sv[3] + ubmv[k][3]};
     }
     __device__ __forceinline__ void convert()
     {
@@ -377,7 +335,6 @@ struct TilePixel {
     int ridx;
     bool act;
     unsigned slot8;
-    unsigned slotbase8;              // (wave-uniform) slot8 of lane 0: slot8 == slotbase8 + 8 * lane, for kernels short of registers
     // gK, gInfo, nslots8: TileLogoDev::kp / sinfo / 8 * nslots, fetched ONCE by the caller -- read here, at every band's end, they are vector
     // loads of their own that the taps' addresses wait for: a second memory round trip in front of the one that matters
     __device__ __forceinline__ void load(gptr_t gK, gptr_t gInfo, unsigned nslots8, unsigned slot, const TileDesc& T, unsigned plane_base)
@@ -388,7 +345,6 @@ struct TilePixel {
         ridx = (int)((si >> 12) & 0xFFFu);
         act = (si >> 31) != 0;
         slot8 = slot * 8u;
-        slotbase8 = __builtin_amdgcn_readfirstlane(slot8);
 #pragma unroll
         for (int j = 0; j < 13; ++j) Kp[j] = gld<f2>(gK, (unsigned)j * nslots8 + slot8);
     }

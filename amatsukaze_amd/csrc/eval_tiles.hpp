@@ -75,10 +75,6 @@ constexpr int kXcds = 8;
 struct WgMap { int logo, grp; };
 AMT_TILE_HD WgMap wg_map_shared_rows(int bid, int nlogos, int ngroups)
 {
-#ifdef AMT_WG_PLAIN_MAP             /* (the A/B of the map: logo-major ids) */
-    if (bid >= nlogos * ngroups) return WgMap{0, ngroups};
-    return WgMap{bid / ngroups, bid % ngroups};
-#endif
     (void)ngroups;
     const int x = bid & (kXcds - 1), r = bid >> 3;
     const int blk = r / nlogos;

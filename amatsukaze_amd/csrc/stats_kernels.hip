@@ -9,10 +9,9 @@
 // What bounds it (profiles/r04_notes.md): with the whole device the kernel moves 6.1 TB/s of actual traffic (1.15x its algorithmic
 // bytes: 128-byte lines against a 1472-byte pitch, halo rows, the frame before a run) -- HBM.  Given a PART of the device
 // (hipExtStreamCreateWithCUMask, to run beside the VALU-bound logo kernels) its rate scales with the CUs it owns: per CU it is bound
-// by the vector ALU (~780 instructions per wave and frame in round 3's form, 4.5 cycles each) and by the bytes a CU keeps in flight.
-// Hence the lean form below: raw buffer loads (one VGPR of address for the whole tile, rows outside the frame come back as zeros from
-// the bounds check -- no 64-bit address arithmetic, no selects), the even-row vertical detail of the previous frame carried over
-// instead of recomputed, the duplicate of the odd rows' term dropped, wave sums on DPP instead of LDS permutes.
+// by the vector ALU and by the bytes a CU keeps in flight.  Hence the form below: raw buffer loads (one VGPR of address for the whole
+// tile, rows outside the frame come back as zeros from the bounds check -- no 64-bit address arithmetic, no selects), the even-row
+// vertical detail of the previous frame carried over instead of recomputed, wave sums on DPP instead of LDS permutes.
 //
 // Per frame n (prev = frame n-1; rows 1..H-2 for the vertical metrics), all sums of absolute values:
 //   0 DIFF_TOP   sum_{y even} |Y_n[y] - Y_prev[y]|          3 COMB       sum |Y_n[y] - avg(Y_n[y-1], Y_n[y+1])|
@@ -37,18 +36,6 @@ constexpr int kStatThreads = 128;
 #ifndef AMT_STATS_RUN
 #define AMT_STATS_RUN 32
 #endif
-#ifndef AMT_STATS_COLB
-#define AMT_STATS_COLB 16
-#endif
-#ifndef AMT_STATS_LEAN
-#define AMT_STATS_LEAN 1
-#endif
-#ifndef AMT_STATS_PINGPONG
-#define AMT_STATS_PINGPONG 1
-#endif
-#ifndef AMT_STATS_DEAL
-#define AMT_STATS_DEAL 0       /* 0: (tile, column) pairs dealt densely over the threads; 1: wave-segment dealing (see the kernel) */
-#endif
 #ifndef AMT_STATS_NT
 #define AMT_STATS_NT 2         /* cache-policy bits of the loads of rows no other tile reads: 2 = nt (non-temporal) */
 #endif
@@ -64,7 +51,7 @@ template <int ES, bool BUF = true> constexpr int stat_tile_rows() { return !BUF 
 constexpr int kStatRun = AMT_STATS_RUN;          // frames a workgroup walks through (the frame before a run is its one re-read: 1/32)
 constexpr int kStatXcds = 8;          // MI355X: 8 XCDs, workgroups are dealt to them round-robin by linear workgroup id
 constexpr int kStatWords = 8;
-constexpr int kStatColBytes = AMT_STATS_COLB;      // bytes of a row one lane owns: 16 (one dwordx4 load) or 8 (dwordx2: half the registers per row)
+constexpr int kStatColBytes = 16;     // bytes of a row one lane owns: one dwordx4 load
 constexpr int kStatColWords = kStatColBytes / 4;
 
 template <int ES> struct Px;
@@ -139,7 +126,7 @@ __device__ __forceinline__ unsigned wave_sum_to_lane63(unsigned v)
 #endif
 // RAGGED: the row is not a whole number of lane columns (the last column's tail bytes are masked); the common widths -- multiples of 16
 // bytes -- take the version without the masks
-// BUF: rows come in through raw buffer loads whose bounds check supplies the zeros (the lean form below).  It needs every 16-byte
+// BUF: rows come in through raw buffer loads whose bounds check supplies the zeros.  It needs every 16-byte
 // column of a row to end inside the row's pitch -- a ragged row in an unpadded pitch (W = 362, pitch = 362) would have its last column
 // of the bottom row straddle the end of the buffer and lose its valid bytes; such geometries take the plain loads (BUF = false).
 template <int ES, bool RAGGED, bool BUF>
@@ -159,34 +146,9 @@ void frame_stats_kernel(const uint8_t* __restrict__ Y, long long frame_stride /*
     // (each XCD has a private L2; adjacent blockIdx.x would put every halo on a different one).
     const int per = gridDim.x / kStatXcds;
     const int wg = (blockIdx.x % kStatXcds) * per + blockIdx.x / kStatXcds;
-    int tile, xb;
-    if (AMT_STATS_DEAL == 1) {
-        // wave-segment dealing: a row is cut into wpt = ceil(cols / 64) equal segments, one wave each; consecutive waves take the segments
-        // of one tile, so (wpt = 2, two waves per workgroup) the waves that share a 128-byte line -- the segment boundary, and a row's tail
-        // with the next row's head when the pitch is not a multiple of the line -- sit in ONE workgroup and ask for it at the same time
-        const int wpt = (cols + 63) >> 6, cpw = (cols + wpt - 1) / wpt;
-        const int wave = wg * (kStatThreads / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-        tile = wave / wpt;
-        const int col = (wave - tile * wpt) * cpw + lane;
-        xb = (lane < cpw && col < cols) ? col * kStatColBytes : row_bytes;          // (row_bytes: no valid bytes -> an idle lane)
-    } else if (AMT_STATS_DEAL == 2) {
-        // grouped dealing: every wave's span starts on a multiple of 64 columns (1 KiB) of its tile's rows, so a span boundary never cuts a
-        // 128-byte line of a line-aligned row.  The full 64-column groups of a tile take a wave each; the remainders (r = cols % 64
-        // columns) of P = 64 / r consecutive tiles share one wave.  1440 bytes = 90 columns: waves {tile 2b: 0-63}, {tile 2b+1: 0-63},
-        // {26 + 26 remainder columns of both} -- 94 % of the lanes busy, against dense dealing's arbitrary boundaries (a line cut by a
-        // boundary is fetched by both waves, and the L2 does not merge the two misses: profiles/r05_notes.md)
-        const int G = cols >> 6, r = cols & 63, P = r ? 64 / r : 1, wpb = P * G + (r ? 1 : 0);      // waves per block of P tiles
-        const int wave = wg * (kStatThreads / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-        const int b = wave / wpb, i = wave - b * wpb;
-        int col;
-        if (i < P * G) { tile = b * P + i / G; col = (i % G) * 64 + lane; }
-        else { const int sub = lane / r; tile = b * P + sub; col = sub < P ? G * 64 + (lane - sub * r) : cols; }
-        xb = col < cols ? col * kStatColBytes : row_bytes;
-    } else {
-        const int gid = wg * kStatThreads + threadIdx.x;
-        tile = gid / cols;
-        xb = (gid - tile * cols) * kStatColBytes;                 // byte column of this thread
-    }
+    const int gid = wg * kStatThreads + threadIdx.x;
+    const int tile = gid / cols;
+    const int xb = (gid - tile * cols) * kStatColBytes;           // byte column of this thread
     const int y0 = tile * TR;
     const int nvalid = y0 < H ? min(kStatColBytes, row_bytes - xb) : 0;      // <= 0: thread has no pixels
     const int n0 = blockIdx.y * kStatRun;
@@ -222,19 +184,12 @@ void frame_stats_kernel(const uint8_t* __restrict__ Y, long long frame_stride /*
             // non-temporal, so that the rows two tiles DO share stay in the XCD's L2 until the neighbour asks for them
             constexpr int kNt = AMT_STATS_NT;
             const bool shared_row = r <= 1 || r >= R - 2;
-            if (kStatColBytes == 16) {
-                typedef unsigned u4 __attribute__((ext_vector_type(4)));
-                const u4 v = (kNt && !shared_row) ? __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, 0, kNt)
-                                                  : __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, 0, 0);
+            static_assert(kStatColBytes == 16, "one dwordx4 load per row");
+            typedef unsigned u4 __attribute__((ext_vector_type(4)));
+            const u4 v = (kNt && !shared_row) ? __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, 0, kNt)
+                                              : __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, 0, 0);
 #pragma unroll
-                for (int i = 0; i < kStatColWords; ++i) rows[r].w[i] = RAGGED ? (v[i] & bmask[i]) : v[i];
-            } else {
-                typedef unsigned u2 __attribute__((ext_vector_type(2)));
-                const u2 v = (kNt && !shared_row) ? __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)off, 0, kNt)
-                                                  : __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)off, 0, 0);
-#pragma unroll
-                for (int i = 0; i < kStatColWords; ++i) rows[r].w[i] = RAGGED ? (v[i] & bmask[i]) : v[i];
-            }
+            for (int i = 0; i < kStatColWords; ++i) rows[r].w[i] = RAGGED ? (v[i] & bmask[i]) : v[i];
         }
     };
 
@@ -278,17 +233,8 @@ void frame_stats_kernel(const uint8_t* __restrict__ Y, long long frame_stride /*
         acc[2] = ve + vo;                // VERT of the frame
         acc[6] = vo + ve_prev;           // VERT of the weave: odd rows look at this frame's neighbours, even rows at the previous frame's
 #pragma unroll
-        for (int k = 0; k < 7; ++k) {
-#if AMT_STATS_LEAN
-            acc[k] = wave_sum_to_lane63(acc[k]);
-#else
-            unsigned v = acc[k];
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
-            acc[k] = v;
-#endif
-        }
-        if ((threadIdx.x & 63) == (AMT_STATS_LEAN ? 63 : 0)) {
+        for (int k = 0; k < 7; ++k) acc[k] = wave_sum_to_lane63(acc[k]);
+        if ((threadIdx.x & 63) == 63) {
 #pragma unroll
             for (int k = 0; k < 7; ++k)
                 if (acc[k]) atomicAdd(&out[(long long)n * kStatWords + k], (unsigned long long)acc[k]);
@@ -302,7 +248,7 @@ void frame_stats_kernel(const uint8_t* __restrict__ Y, long long frame_stride /*
     load_rows(before, A);
     unsigned ve = vert_even(A);
     // (ragged rows keep the copying form: with the byte masks the doubled body needs more than 256 registers at 8 bits)
-    if constexpr (AMT_STATS_PINGPONG && !RAGGED) {
+    if constexpr (!RAGGED) {
         for (int n = n0; n < n1; n += 2) {
             load_rows(Y + (long long)n * frame_stride, B);
             ve = compute(B, A, n, ve);
@@ -327,26 +273,19 @@ hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long lon
     const int es = bits <= 8 ? 1 : 2;
     const int row_bytes = W * es;
     const int col_groups = (row_bytes + kStatColBytes - 1) / kStatColBytes;     // lane columns per row
-    const bool buf = AMT_STATS_LEAN && (long long)col_groups * kStatColBytes <= (long long)pitch_elems * es;   // see the kernel's BUF
+    const bool buf = (long long)col_groups * kStatColBytes <= (long long)pitch_elems * es;   // see the kernel's BUF
     const int tile_rows = !buf ? kStatTileRowsPlain : es == 1 ? kStatTileRows8 : kStatTileRows;
     const int tiles = (H + tile_rows - 1) / tile_rows;
-    // (the lean form addresses a frame with 32-bit byte offsets below 2^31)
+    // (the kernel addresses a frame with 32-bit byte offsets below 2^31)
     if ((long long)H * pitch_elems * es >= (1LL << 31)) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(dout, 0, (size_t)nframes * kStatWords * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
-    const int wpt = (col_groups + 63) / 64;
-    const int dG = col_groups / 64, dR = col_groups % 64, dP = dR ? 64 / dR : 1, dWpb = dP * dG + (dR ? 1 : 0);
-    const int wgs = AMT_STATS_DEAL == 2 ? ((tiles + dP - 1) / dP * dWpb + kStatThreads / 64 - 1) / (kStatThreads / 64)
-                  : AMT_STATS_DEAL == 1 ? (tiles * wpt + kStatThreads / 64 - 1) / (kStatThreads / 64)
-                  : (tiles * col_groups + kStatThreads - 1) / kStatThreads;
+    const int wgs = (tiles * col_groups + kStatThreads - 1) / kStatThreads;
     dim3 grid((unsigned)((wgs + kStatXcds - 1) / kStatXcds * kStatXcds), (unsigned)((nframes + kStatRun - 1) / kStatRun)),
         block(kStatThreads);                                      // surplus workgroups of the round-up find nvalid <= 0
     const bool ragged = row_bytes % kStatColBytes != 0;
-#ifndef AMT_STATS_LDS_BYTES
-#define AMT_STATS_LDS_BYTES 0      /* experiments: an LDS reservation the kernel never touches caps its workgroups per CU */
-#endif
 #define AMT_STATS_LAUNCH(E, RG, BF)                                                                                                          \
-    hipLaunchKernelGGL((frame_stats_kernel<E, RG, BF>), grid, block, AMT_STATS_LDS_BYTES, st, (const uint8_t*)dY, frame_stride_bytes, pitch_elems * es, row_bytes, H, \
+    hipLaunchKernelGGL((frame_stats_kernel<E, RG, BF>), grid, block, 0, st, (const uint8_t*)dY, frame_stride_bytes, pitch_elems * es, row_bytes, H, \
                        (const uint8_t*)dprevY, nframes, col_groups, dout)
     if (es == 1) { if (!buf) AMT_STATS_LAUNCH(1, true, false); else if (ragged) AMT_STATS_LAUNCH(1, true, true); else AMT_STATS_LAUNCH(1, false, true); }
     else { if (!buf) AMT_STATS_LAUNCH(2, true, false); else if (ragged) AMT_STATS_LAUNCH(2, true, true); else AMT_STATS_LAUNCH(2, false, true); }

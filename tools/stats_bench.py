@@ -1,21 +1,16 @@
-"""frame_stats_kernel variants (amatsukaze_amd/build.py build_variant: -DAMT_STATS_VG / _ROWS / _RUN) on the bench's shapes: time per
+"""frame_stats_kernel variants (amatsukaze_amd/build.py build_variant: -DAMT_STATS_ROWS / _RUN / _NT / _WAVES) on the bench's shapes: time per
 10 000-frame launch and equality of every record with the default build's.  Build where hipcc is (`--build`), run on the GPU box:
     python tools/stats_bench.py > gpurun_out/stats_bench.json"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-VARIANTS = {"r03_form": ["AMT_STATS_LEAN=0"], "lean_no_nt": ["AMT_STATS_NT=0"], "lean_nt3": ["AMT_STATS_NT=3"], "lean_vg4": ["AMT_STATS_VG=4"],
-            "lean_8B_columns": ["AMT_STATS_COLB=8"], "lean_8B_prefetch": ["AMT_STATS_COLB=8", "AMT_STATS_PREFETCH=1"],
-            "lean_8rows_prefetch": ["AMT_STATS_ROWS=8", "AMT_STATS_PREFETCH=1"], "lean_run64": ["AMT_STATS_RUN=64"],
+VARIANTS = {"lean_no_nt": ["AMT_STATS_NT=0"], "lean_nt3": ["AMT_STATS_NT=3"], "lean_run64": ["AMT_STATS_RUN=64"],
             # taller tiles: the halo rows are 2 / ROWS of the traffic
-            "rows24": ["AMT_STATS_ROWS=24"], "rows24_8B": ["AMT_STATS_ROWS=24", "AMT_STATS_COLB=8"], "rows32_8B": ["AMT_STATS_ROWS=32", "AMT_STATS_COLB=8"],
-            "rows32_8B_run64": ["AMT_STATS_ROWS=32", "AMT_STATS_COLB=8", "AMT_STATS_RUN=64"],
+            "rows24": ["AMT_STATS_ROWS=24"],
             "w3_r16_r12": ["AMT_STATS_WAVES=3", "AMT_STATS_ROWS8=16", "AMT_STATS_ROWS=12"], "w3_r12_r12": ["AMT_STATS_WAVES=3", "AMT_STATS_ROWS8=12", "AMT_STATS_ROWS=12"],
             "w3_r16_r8": ["AMT_STATS_WAVES=3", "AMT_STATS_ROWS8=16", "AMT_STATS_ROWS=8"], "w4_r8_r8": ["AMT_STATS_WAVES=4", "AMT_STATS_ROWS8=8", "AMT_STATS_ROWS=8"],
             "w3_r14_r10": ["AMT_STATS_WAVES=3", "AMT_STATS_ROWS8=14", "AMT_STATS_ROWS=10"],
-            "deal2": ["AMT_STATS_DEAL=2"], "deal2_rows16": ["AMT_STATS_DEAL=2", "AMT_STATS_ROWS8=16"], "deal2_rows20": ["AMT_STATS_DEAL=2", "AMT_STATS_ROWS8=20"],
-            "deal1": ["AMT_STATS_DEAL=1"], "deal1_no_nt": ["AMT_STATS_DEAL=1", "AMT_STATS_NT=0"], "deal1_run64": ["AMT_STATS_DEAL=1", "AMT_STATS_RUN=64"],
-            "deal1_rows16": ["AMT_STATS_DEAL=1", "AMT_STATS_ROWS8=16"], "run64": ["AMT_STATS_RUN=64"], "no_nt": ["AMT_STATS_NT=0"],
+            "run64": ["AMT_STATS_RUN=64"], "no_nt": ["AMT_STATS_NT=0"],
             "rows8bit_16": ["AMT_STATS_ROWS8=16"], "rows8bit_20": ["AMT_STATS_ROWS8=20"], "rows8bit_28": ["AMT_STATS_ROWS8=28"]}
 ONLY = [a for a in sys.argv[1:] if not a.startswith("--")]
 if ONLY:
