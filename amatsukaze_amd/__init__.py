@@ -4,7 +4,9 @@ Product code only: HIP kernels + C ABI (csrc/, libamt_gpu.so) and the Python mir
 filter interface (api.py).  Nothing here imports the CPU oracle.
 """
 from .api import (AMTAnalyzeLogo, AMTEraseLogo, AmtError, AmtsFile, Context, DeviceClip, FrameStats, Logo, LogoCandidate, LogoFinder,
-                  LogoFrame, LogoScan, ScanLogo, ScanLogoAuto, ScanLogoFile, ScanLogoFileAuto, weave_fields)
+                  LogoFrame, LogoScan, ScanLogo, ScanLogoAuto, ScanLogoAutoStream, ScanLogoFile, ScanLogoFileAuto, ScanLogoStream,
+                  weave_fields)
 
 __all__ = ["AMTAnalyzeLogo", "AMTEraseLogo", "AmtError", "AmtsFile", "Context", "DeviceClip", "FrameStats", "Logo", "LogoCandidate",
-           "LogoFinder", "LogoFrame", "LogoScan", "ScanLogo", "ScanLogoAuto", "ScanLogoFile", "ScanLogoFileAuto", "weave_fields"]
+           "LogoFinder", "LogoFrame", "LogoScan", "ScanLogo", "ScanLogoAuto", "ScanLogoAutoStream", "ScanLogoFile", "ScanLogoFileAuto",
+           "ScanLogoStream", "weave_fields"]

@@ -665,6 +665,71 @@ def ScanLogoFileAuto(ctx: Context, srcpath, serviceid, workfile, dstpath, thy, n
     return bool(ok), (LogoCandidate._of(found) if found.w > 0 else None)
 
 
+class ScanLogoStream:
+    """ScanLogo as a session fed with frame batches (amtgpu_scanlogo_stream_*): for a clip that is decoded as it goes and never
+    resident.  feed / feed_rect return (frames kept so far, done); finish writes the .lgd -- byte-identical to ScanLogo over the same
+    frames -- and returns True / False like ScanLogo (the message stays on the context).  A batch may be overwritten by work on the
+    context's stream as soon as its feed has returned."""
+
+    def __init__(self, ctx: Context, imgw, imgh, imgx, imgy, w, h, thy, numMaxFrames):
+        self.ctx = ctx
+        self.h = ctx.lib.amtgpu_scanlogo_stream_create(ctx.h, imgw, imgh, imgx, imgy, w, h, thy, numMaxFrames)
+        ctx.check(self.h, "ScanLogoStream")
+
+    def _fed(self, fn, Y, U, V, strideY, strideUV, pitchY, pitchUV, n):
+        nkept, done = C.c_int(), C.c_int()
+        self.ctx.check(fn(self.h, _p(Y), _p(U), _p(V), strideY, strideUV, pitchY, pitchUV, n, C.byref(nkept), C.byref(done)), "ScanLogoStream")
+        return nkept.value, bool(done.value)
+
+    def feed(self, clip: DeviceClip):
+        """the next frames of the stream, full 8-bit frames"""
+        if clip.bits != 8:
+            raise AmtError("ScanLogoStream: 8-bit clips only")
+        return self._fed(self.ctx.lib.amtgpu_scanlogo_stream_feed, clip.Y, clip.U, clip.V, clip.strideY, clip.strideUV, clip.pitchY,
+                         clip.pitchUV, clip.num_frames)
+
+    def feed_rect(self, Y, U, V):
+        """the same on device planes that hold only the rectangle: Y [n, h, w], U / V [n, h/2, w/2] uint8 (any row pitch)"""
+        return self._fed(self.ctx.lib.amtgpu_scanlogo_stream_feed_rect, Y, U, V, int(Y.stride(0)), int(U.stride(0)), int(Y.stride(1)),
+                         int(U.stride(1)), int(Y.shape[0]))
+
+    def status(self):
+        """{"nread": frames consumed up to and including the one that closed the stream, "nkept", "done"}"""
+        nread, nkept, done = C.c_int64(), C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.lib.amtgpu_scanlogo_stream_status(self.h, C.byref(nread), C.byref(nkept), C.byref(done)))
+        return {"nread": nread.value, "nkept": nkept.value, "done": bool(done.value)}
+
+    def finish(self, serviceid, dstpath, cb=None):
+        cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
+        return bool(self.ctx.lib.amtgpu_scanlogo_stream_finish(self.h, serviceid, str(dstpath).encode(), cbf))
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.ctx.lib.amtgpu_scanlogo_stream_destroy(self.h)
+        except Exception:
+            pass
+
+
+def ScanLogoAutoStream(ctx: Context, batches, width, height, serviceid, dstpath, thy, numMaxFrames, cb=None, **params):
+    """ScanLogoAuto over a clip that is streamed, not resident: `batches` is a callable that returns a fresh iterator of DeviceClip
+    batches (8-bit, in stream order).  Pass 1 feeds every batch to a LogoFinder; pass 2 feeds a ScanLogoStream on the best candidate and
+    stops iterating once its quota is full.  Returns the LogoCandidate; raises AmtError ("no logo found", or ScanLogo's message)."""
+    finder = LogoFinder(ctx, width, height, 8)
+    for clip in batches():
+        finder.add(clip)
+    cands = finder.candidates(1, **params)
+    if not cands:
+        raise AmtError("no logo found")
+    r = cands[0]
+    stream = ScanLogoStream(ctx, width, height, r.imgx, r.imgy, r.w, r.h, thy, numMaxFrames)
+    for clip in batches():
+        if stream.feed(clip)[1]:
+            break
+    ctx.check(stream.finish(serviceid, dstpath, cb), "ScanLogoStream")
+    return r
+
+
 class FrameStats:
     """Self-specified whole-frame field-difference / combing metrics."""
 

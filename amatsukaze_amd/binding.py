@@ -166,6 +166,13 @@ SIGNATURES = {
     "amtgpu_scanlogo_auto": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_s, c_i, c_i, CB, c_p, c_p]),
     "amtgpu_scanlogo_auto_sharded": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_s, c_i, c_i, CB, c_p, c_p]),
     "amtgpu_scanlogo_file_auto": (c_i, [c_p, c_s, c_i, c_s, c_s, c_i, c_i, CB, c_p, c_p]),
+    "amtgpu_scanlogo_stream_create": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    "amtgpu_scanlogo_stream_destroy": (None, [c_p]),
+    "amtgpu_scanlogo_stream_feed": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_p, c_p]),
+    "amtgpu_scanlogo_stream_feed_rect": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_p, c_p]),
+    "amtgpu_scanlogo_stream_status": (c_i, [c_p, c_p, c_p, c_p]),
+    "amtgpu_scanlogo_stream_finish": (c_i, [c_p, c_i, c_s, CB]),
+    "amtgpu_scanlogo_stream_finish_sharded": (c_i, [c_p, c_p, c_i, c_s, CB]),
 }
 
 _lib = None

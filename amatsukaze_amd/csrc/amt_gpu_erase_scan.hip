@@ -582,7 +582,227 @@ int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const PlaneBa
 
 } // namespace
 
+// ---------------------------------------------------------------------------------------------
+// ScanLogo as a session fed with frame batches: what InitialLogoCreator::onFrame does per decoded frame (LogoScan.hpp:881-914) -- border
+// verdict, keep the rectangle of a valid frame until numMaxFrames are kept -- per batch, with the rectangles kept in HBM instead of the
+// reference's lossless work file; the finish is MakeInitialLogo's regression and the two ReMakeLogo rounds over that store.
+// ---------------------------------------------------------------------------------------------
+struct AmtGpuScanLogoStream {
+    AmtGpuContext* ctx = nullptr;
+    int imgw = 0, imgh = 0, thy = 0, numMaxFrames = 0;
+    ScanRect rect{};                            // the rectangle in a full frame
+    std::unique_ptr<AmtGpuLogoScan> scan;       // the feeds' border verdicts; round 0's sums, accumulated from the store at the finish
+    DevBuf<uint8_t> storeY, storeU, storeV;     // rectangles of the kept frames, tight: Y [n][h][w], U / V [n][h/2][w/2]
+    int cap = 0;                                // frames the store has room for
+    std::vector<int4> keptVerdict;              // {1, bgY, bgU, bgV} of every kept frame
+    int64_t nread = 0;                          // readCount (:883): frames consumed up to and including the one that closed the stream
+    bool done = false, spent = false;
+    // batch-local indices of a feed's kept frames: pinned, rewritten only after the upload that read it (keepUploaded)
+    int* hKeep = nullptr;
+    size_t keepCap = 0;
+    DevBuf<int> dKeep;
+    hipEvent_t keepUploaded = nullptr;
+    int nkept() const { return (int)keptVerdict.size(); }
+    ~AmtGpuScanLogoStream()
+    {
+        if (keepUploaded) { (void)hipEventSynchronize(keepUploaded); (void)hipEventDestroy(keepUploaded); }
+        if (hKeep) (void)hipHostFree(hKeep);
+    }
+};
+
+namespace {
+
+AmtGpuScanLogoStream* stream_new(AmtGpuContext* c, int imgw, int imgh, int imgx, int imgy, int w, int h, int thy, int numMaxFrames)
+{
+    if (imgx < 0 || imgy < 0 || w > imgw - imgx || h > imgh - imgy) throw std::runtime_error("scan rectangle outside the frame");
+    std::unique_ptr<AmtGpuScanLogoStream> s(new AmtGpuScanLogoStream);
+    s->ctx = c;
+    s->imgw = imgw; s->imgh = imgh; s->thy = thy;
+    s->numMaxFrames = std::max(0, numMaxFrames);
+    s->scan.reset(logoscan_new(c, w, h, 1, 1, thy));       // (refuses odd and non-positive sizes)
+    s->rect = scan_rect(imgx, imgy, w, h);
+    s->done = s->numMaxFrames == 0;
+    // the store grows with what is kept: numMaxFrames is a limit (callers pass 1 << 30), not a size
+    s->cap = std::max(1, std::min(s->numMaxFrames, 256));
+    const ScanRect& r = s->rect;
+    s->storeY.alloc((size_t)s->cap * r.w * r.h);
+    s->storeU.alloc((size_t)s->cap * r.wUV * r.hUV);
+    s->storeV.alloc((size_t)s->cap * r.wUV * r.hUV);
+    AMT_HIP(hipEventCreateWithFlags(&s->keepUploaded, hipEventDisableTiming));
+    return s.release();
+}
+
+// room for `need` kept frames: the store doubles, what it holds moves on the stream
+void stream_reserve(AmtGpuScanLogoStream* s, int need)
+{
+    if (need <= s->cap) return;
+    const int ncap = (int)std::min<int64_t>(s->numMaxFrames, std::max<int64_t>(need, 2 * (int64_t)s->cap));
+    const ScanRect& r = s->rect;
+    const size_t ysz = (size_t)r.w * r.h, csz = (size_t)r.wUV * r.hUV, n = (size_t)s->nkept();
+    DevBuf<uint8_t> nY(ysz * ncap), nU(csz * ncap), nV(csz * ncap);
+    if (n) {
+        hipStream_t st = s->ctx->stream;
+        AMT_HIP(hipMemcpyAsync(nY.get(), s->storeY.get(), ysz * n, hipMemcpyDeviceToDevice, st));
+        AMT_HIP(hipMemcpyAsync(nU.get(), s->storeU.get(), csz * n, hipMemcpyDeviceToDevice, st));
+        AMT_HIP(hipMemcpyAsync(nV.get(), s->storeV.get(), csz * n, hipMemcpyDeviceToDevice, st));
+        AMT_HIP(hipStreamSynchronize(st));                   // the old store is freed below
+    }
+    s->storeY = std::move(nY); s->storeU = std::move(nU); s->storeV = std::move(nV);
+    s->cap = ncap;
+}
+
+// the next nframes frames of the stream; rect_only: the planes hold the rectangle alone
+void stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV,
+                 int nframes, bool rect_only)
+{
+    if (s->spent) throw std::runtime_error("[ScanLogo] the session has been finished");
+    if (nframes < 0) throw std::runtime_error("[ScanLogo] negative frame count");
+    if (nframes == 0 || s->done) return;
+    if (!dY || !dU || !dV) throw std::runtime_error("[ScanLogo] null plane");
+    const ScanRect r = rect_only ? scan_rect(0, 0, s->rect.w, s->rect.h) : s->rect;
+    if (pitchY < r.imgx + r.w || pitchUV < r.cx + r.wUV) throw std::runtime_error("[ScanLogo] pitch smaller than the rectangle's rows");
+    const PlaneBatch b = plane_batch(8, dY, dU, dV, strideY, strideUV, pitchY, pitchUV);
+    AmtGpuContext* c = s->ctx;
+    // verdicts alone (quota 0): which valid frames count is decided here, in stream order
+    logoscan_add(s->scan.get(), b, r, 8, nframes, 0, nullptr, nullptr, nullptr, nullptr);
+    const std::vector<int4>& v = s->scan->lastVerdicts;
+    AMT_HIP(hipEventSynchronize(s->keepUploaded));
+    if (s->keepCap < (size_t)nframes) {
+        if (s->hKeep) AMT_HIP(hipHostFree(s->hKeep));
+        s->hKeep = nullptr; s->keepCap = 0;
+        AMT_HIP(hipHostMalloc((void**)&s->hKeep, (size_t)nframes * sizeof(int), hipHostMallocDefault));
+        s->keepCap = (size_t)nframes;
+        s->dKeep.alloc(nframes);
+    }
+    const int first = s->nkept(), room = s->numMaxFrames - first;      // room > 0: the stream is open
+    int m = 0, consumed = nframes;
+    for (int i = 0; i < nframes; ++i) {
+        if (!v[i].x) continue;
+        s->hKeep[m++] = i;
+        if (m == room) { consumed = i + 1; break; }
+    }
+    if (m) {
+        stream_reserve(s, first + m);
+        AMT_HIP(hipMemcpyAsync(s->dKeep.get(), s->hKeep, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        AMT_HIP(hipEventRecord(s->keepUploaded, c->stream));
+        const int sp = c->prof_begin("scan_keep_kernel");
+        AMT_HIP(launch_scan_keep(c->stream, b, r, s->dKeep.get(), m, PlanesOut{s->storeY.get(), s->storeU.get(), s->storeV.get()}, first));
+        c->prof_end(sp);
+        for (int k = 0; k < m; ++k) s->keptVerdict.push_back(v[s->hKeep[k]]);
+    }
+    s->nread += consumed;
+    s->done = m == room;
+}
+
+// MakeInitialLogo's regression and the two ReMakeLogo rounds over the store (LogoScan.hpp:845-848, 1065-1071); sharded: this rank's share of
+// the quota first, as scanlogo_impl hands it out
+void stream_finish(AmtGpuScanLogoStream* s, const AmtGpuCollectives* coll, int serviceid, const char* dstpath, AMTGPU_LOGO_ANALYZE_CB cb)
+{
+    AmtGpuContext* c = s->ctx;
+    const bool sharded = coll && coll->world > 1;
+    const bool usable = !sharded || (coll->allgather && coll->allreduce_sum_i64 && coll->rank >= 0 && coll->rank < coll->world);
+    ShardGuard sg;
+    sg.coll = sharded && usable ? coll : nullptr;
+    auto progress = [&](float p, int nread, int total, int ngather) {
+        if (cb && !cb(p, nread, total, ngather)) {
+            if (!sharded) throw std::runtime_error("Cancel requested");
+            sg.cancel = 1;
+        }
+    };
+    // (a spent session on one rank of a sharded finish must not strand the others: its refusal rides along like any other failure)
+    sg.attempt([&] { if (s->spent) throw std::runtime_error("[ScanLogo] the session has been finished"); });
+    s->spent = true;
+    if (!usable) throw std::runtime_error("AmtGpuCollectives incomplete");
+    if (!sharded && !dstpath) throw std::runtime_error("[ScanLogo] null destination path");
+    c->bind();
+    int n = sg.error.empty() ? s->nkept() : 0;
+    if (sharded) {
+        std::vector<int64_t> counts((size_t)coll->world * 2, 0);
+        const int64_t mine[2] = {n, sg.status()};
+        if (!coll->allgather(coll->user, mine, counts.data(), sizeof mine)) throw std::runtime_error("allgather failed");
+        int64_t before = 0, summed = 0;
+        for (int k = 0; k < coll->world; ++k) summed += counts[2 * k + 1];
+        for (int k = 0; k < coll->rank; ++k) before += counts[2 * k];
+        sg.agree(summed);
+        n = (int)std::max<int64_t>(0, std::min<int64_t>(n, (int64_t)s->numMaxFrames - before));
+    }
+    const ScanRect& fr = s->rect;
+    const ScanRect r = scan_rect(0, 0, fr.w, fr.h);
+    const size_t npx = (size_t)3 * ((size_t)r.w * r.h + 2 * (size_t)r.wUV * r.hUV);
+    const PlaneBatch crops{s->storeY.get(), s->storeU.get(), s->storeV.get(), (long long)r.w * r.h, (long long)r.wUV * r.hUV, r.w, r.wUV};
+    std::vector<int> kept(n);
+    for (int i = 0; i < n; ++i) kept[i] = i;
+    const std::vector<int4> verdicts(s->keptVerdict.begin(), s->keptVerdict.begin() + n);
+    sg.attempt([&] {
+        if (n) logoscan_add(s->scan.get(), crops, r, 8, n, n, nullptr, nullptr, kept.data(), verdicts.data());
+    });
+    reduce_scan(s->scan.get(), sg, npx);
+    std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, s->scan.get(), crops, r, s->thy, kept, verdicts, s->imgw, s->imgh, fr.imgx, fr.imgy,
+                                                     progress);
+    progress(1, n, n, n);
+    if (dstpath && (!sharded || coll->rank == 0)) save_lgd(logo->planes, dstpath, "No Name", serviceid);
+}
+
+void stream_report(const AmtGpuScanLogoStream* s, int64_t* nread, int* nkept, int* done)
+{
+    if (nread) *nread = s->nread;
+    if (nkept) *nkept = s->nkept();
+    if (done) *done = s->done ? 1 : 0;
+}
+
+} // namespace
+
 extern "C" {
+
+AmtGpuScanLogoStream* amtgpu_scanlogo_stream_create(AmtGpuContext* c, int imgw, int imgh, int imgx, int imgy, int w, int h, int thy,
+                                                    int numMaxFrames)
+{
+    if (!c) return nullptr;
+    AmtGpuScanLogoStream* s = nullptr;
+    guard(c, [&] { s = stream_new(c, imgw, imgh, imgx, imgy, w, h, thy, numMaxFrames); });
+    return s;
+}
+
+void amtgpu_scanlogo_stream_destroy(AmtGpuScanLogoStream* s) { delete s; }
+
+int amtgpu_scanlogo_stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
+                                int pitchY, int pitchUV, int nframes, int* nkept, int* done)
+{
+    if (!s) return 0;
+    return guard(s->ctx, [&] {
+        stream_feed(s, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, nframes, false);
+        stream_report(s, nullptr, nkept, done);
+    });
+}
+
+int amtgpu_scanlogo_stream_feed_rect(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
+                                     int pitchY, int pitchUV, int nframes, int* nkept, int* done)
+{
+    if (!s) return 0;
+    return guard(s->ctx, [&] {
+        stream_feed(s, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, nframes, true);
+        stream_report(s, nullptr, nkept, done);
+    });
+}
+
+int amtgpu_scanlogo_stream_status(const AmtGpuScanLogoStream* s, int64_t* nread, int* nkept, int* done)
+{
+    if (!s) return 0;
+    return guard(s->ctx, [&] { stream_report(s, nread, nkept, done); });
+}
+
+int amtgpu_scanlogo_stream_finish(AmtGpuScanLogoStream* s, int serviceid, const char* dstpath, AMTGPU_LOGO_ANALYZE_CB cb)
+{
+    if (!s) return 0;
+    return guard(s->ctx, [&] { stream_finish(s, nullptr, serviceid, dstpath, cb); });
+}
+
+int amtgpu_scanlogo_stream_finish_sharded(AmtGpuScanLogoStream* s, const AmtGpuCollectives* coll, int serviceid, const char* dstpath,
+                                          AMTGPU_LOGO_ANALYZE_CB cb)
+{
+    if (!s) return 0;
+    return guard(s->ctx, [&] { stream_finish(s, coll, serviceid, dstpath, cb); });
+}
 
 int amtgpu_scanlogo(AmtGpuContext* c, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
                     int pitchY, int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath, int imgx,
@@ -594,9 +814,9 @@ int amtgpu_scanlogo(AmtGpuContext* c, const void* dY, const void* dU, const void
 
 // The reference's exported ScanLogo, argument for argument (LogoScan.hpp:1083-1098; C# P/Invoke AmatsukazeNatives.cs:391-393), over a
 // raw 8-bit 4:2:0 clip file instead of a transport stream (decode is out of scope): int32 {'AMTR', width, height, nframes} followed by
-// tight Y, U, V planes per frame.  Frames are streamed through the pinned ring in chunks; only the rectangles of accepted frames
-// stay in HBM for the two ReMakeLogo rounds (the reference keeps them in `workfile` through a lossless codec, :840-912 -- here the
-// argument is accepted and the file left untouched).
+// tight Y, U, V planes per frame.  Frames are streamed through the pinned ring in chunks and fed to a ScanLogo session (above): only
+// the rectangles of accepted frames stay in HBM for the two ReMakeLogo rounds (the reference keeps them in `workfile` through a
+// lossless codec, :840-912 -- here the argument is accepted and the file left untouched).
 int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, const char* workfile, const char* dstpath, int imgx, int imgy,
                          int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
 {
@@ -612,21 +832,13 @@ int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, c
         if (!f || hdr[0] != 0x52544D41 || hdr[1] <= 0 || hdr[2] <= 0 || hdr[3] < 0 || (hdr[1] & 1) || (hdr[2] & 1))
             throw std::runtime_error("not a raw AMTR clip (int32 'AMTR', width, height, frames; 8-bit 4:2:0 planes)");
         const int W = hdr[1], H = hdr[2], N = hdr[3];
-        if (imgx < 0 || imgy < 0 || imgx + w > W || imgy + h > H) throw std::runtime_error("scan rectangle outside the frame");
-        if (numMaxFrames < 0) numMaxFrames = 0;
         const size_t ysz = (size_t)W * H, csz = (size_t)(W / 2) * (H / 2), fsz = ysz + 2 * csz;
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>(1024, (256u << 20) / fsz));
-        const int wUV = w / 2, hUV = h / 2;
         c->bind();
-        std::unique_ptr<AmtGpuLogoScan> scan(logoscan_new(c, w, h, 1, 1, thy));
+        std::unique_ptr<AmtGpuScanLogoStream> s(stream_new(c, W, H, imgx, imgy, w, h, thy, numMaxFrames));
         DevBuf<uint8_t> dChunk(fsz * chunk);
-        // rectangles of the accepted frames, tight: Y [n][h][w], U / V [n][h/2][w/2]
-        const int cap = std::min(numMaxFrames, N);
-        DevBuf<uint8_t> cropY((size_t)std::max(1, cap) * w * h), cropU((size_t)std::max(1, cap) * wUV * hUV), cropV((size_t)std::max(1, cap) * wUV * hUV);
         std::vector<uint8_t> host(fsz * chunk), planar(fsz * chunk);
-        std::vector<int4> keptVerdict;
-        int nkept = 0;
-        for (int f0 = 0; f0 < N && nkept < numMaxFrames; f0 += chunk) {
+        for (int f0 = 0; f0 < N && !s->done; f0 += chunk) {
             const int n = std::min(chunk, N - f0);
             f.read(reinterpret_cast<char*>(host.data()), (std::streamsize)(fsz * n));
             if (!f) throw std::runtime_error("raw clip truncated");
@@ -638,30 +850,11 @@ int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, c
             }
             if (!amtgpu_frames_upload(c, dChunk.get(), planar.data(), fsz * n) || !amtgpu_frames_upload_wait(c)) throw std::runtime_error(c->err);
             const uint8_t *dY = dChunk.get(), *dU = dY + ysz * n, *dV = dU + csz * n;
-            std::vector<uint8_t> valid(n);
-            logoscan_add(scan.get(), PlaneBatch{dY, dU, dV, (long long)ysz, (long long)csz, W, W / 2}, scan_rect(imgx, imgy, w, h), 8, n,
-                         numMaxFrames - nkept, nullptr, valid.data(), nullptr, nullptr);
-            for (int i = 0; i < n; ++i) {
-                if (!valid[i]) continue;
-                // (the library's own row kernel, not the runtime's 2-D copy: amt_gpu_upload.hip)
-                auto crop = [&](const uint8_t* src, int pitch, uint8_t* dst, int cw, int ch) { AMT_HIP(launch_ingest_rows(c->stream, src, pitch, dst, cw, (unsigned long long)cw, ch)); };
-                crop(dY + ysz * i + (size_t)imgy * W + imgx, W, cropY.get() + (size_t)nkept * w * h, w, h);
-                crop(dU + csz * i + (size_t)(imgy / 2) * (W / 2) + imgx / 2, W / 2, cropU.get() + (size_t)nkept * wUV * hUV, wUV, hUV);
-                crop(dV + csz * i + (size_t)(imgy / 2) * (W / 2) + imgx / 2, W / 2, cropV.get() + (size_t)nkept * wUV * hUV, wUV, hUV);
-                keptVerdict.push_back(scan->lastVerdicts[i]);
-                ++nkept;
-            }
+            stream_feed(s.get(), dY, dU, dV, (int64_t)ysz, (int64_t)csz, W, W / 2, n, false);
             AMT_HIP(hipStreamSynchronize(c->stream));          // the chunk buffer is refilled by the next upload
-            progress(50.0f * (f0 + n) / std::max(1, N), f0 + n, 0, nkept);
+            progress(50.0f * (f0 + n) / std::max(1, N), f0 + n, 0, s->nkept());
         }
-        std::vector<int> kept(nkept);
-        for (int i = 0; i < nkept; ++i) kept[i] = i;
-        ShardGuard unsharded;
-        const PlaneBatch crops{cropY.get(), cropU.get(), cropV.get(), (long long)w * h, (long long)wUV * hUV, w, wUV};
-        std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, unsharded, scan.get(), crops, scan_rect(0, 0, w, h), thy, kept, keptVerdict, W, H, imgx, imgy,
-                                                         progress);
-        progress(1, nkept, nkept, nkept);
-        save_lgd(logo->planes, dstpath, "No Name", serviceid);
+        stream_finish(s.get(), nullptr, serviceid, dstpath, cb);
     });
 }
 

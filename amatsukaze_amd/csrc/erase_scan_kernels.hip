@@ -518,4 +518,79 @@ hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b,
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// The streamed ScanLogo's store (InitialLogoCreator::onFrame keeps every accepted frame's rectangle, LogoScan.hpp:899-903): the
+// rectangles of the `nkeep` frames of a batch listed in `keep` (batch-local indices, ascending) go to consecutive slots of the tight
+// store, Y [slot][h][w], U / V [slot][h/2][w/2], all three planes of all listed frames in one launch.  A pure HBM copy addressed like
+// ingest_rows_kernel: a row's lanes sit on consecutive bytes, one lane moves 16 bytes where the plane's base, stride, pitch, origin
+// and width are all multiples of 16, else 4, else 1 -- decided per plane kind (luma / chroma) by the launcher, so an odd chroma
+// origin costs the luma rows nothing.  8-bit samples: strides and pitches in samples are bytes.
+// ------------------------------------------------------------------------------------------------
+struct ScanKeepArgs {
+    const uint8_t *srcY, *srcU, *srcV;     // the rectangle's first sample in frame 0 of the batch
+    long long strideY, strideUV;
+    int pitchY, pitchUV;
+    uint8_t *dstY, *dstU, *dstV;           // the first free slot of the store
+    int w, h, wUV, hUV;
+    int vbY, vbC;                          // bytes one lane moves in a luma / chroma row (16, 4 or 1)
+    int vrowY, vrowC;                      // w / vbY, wUV / vbC
+    int vecsY, vecsC;                      // vrowY * h, vrowC * hUV
+};
+
+__device__ __forceinline__ void keep_vec(uint8_t* d, const uint8_t* s, int vb)
+{
+    if (vb == 16) *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(s);
+    else if (vb == 4) *reinterpret_cast<uint32_t*>(d) = *reinterpret_cast<const uint32_t*>(s);
+    else *d = *s;
+}
+
+__global__ __launch_bounds__(256)
+void scan_keep_kernel(ScanKeepArgs a, const int* __restrict__ keep, long long total_vecs)
+{
+    const int per_frame = a.vecsY + 2 * a.vecsC;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total_vecs; i += (long long)gridDim.x * blockDim.x) {
+        const int slot = (int)(i / per_frame);
+        int v = (int)(i - (long long)slot * per_frame);
+        const long long frame = keep[slot];
+        if (v < a.vecsY) {
+            const int y = v / a.vrowY, x = (v - y * a.vrowY) * a.vbY;
+            keep_vec(a.dstY + ((long long)slot * a.h + y) * a.w + x, a.srcY + frame * a.strideY + (long long)y * a.pitchY + x, a.vbY);
+        } else {
+            v -= a.vecsY;
+            const bool second = v >= a.vecsC;
+            if (second) v -= a.vecsC;
+            const int y = v / a.vrowC, x = (v - y * a.vrowC) * a.vbC;
+            keep_vec((second ? a.dstV : a.dstU) + ((long long)slot * a.hUV + y) * a.wUV + x,
+                     (second ? a.srcV : a.srcU) + frame * a.strideUV + (long long)y * a.pitchUV + x, a.vbC);
+        }
+    }
+}
+
+hipError_t launch_scan_keep(hipStream_t st, const PlaneBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
+                            long long first_slot)
+{
+    if (nkeep <= 0 || r.w <= 0 || r.h <= 0) return hipSuccess;
+    ScanKeepArgs a;
+    a.srcY = (const uint8_t*)b.Y + (long long)r.imgy * b.pitchY + r.imgx;
+    a.srcU = (const uint8_t*)b.U + (long long)r.cy * b.pitchUV + r.cx;
+    a.srcV = (const uint8_t*)b.V + (long long)r.cy * b.pitchUV + r.cx;
+    a.strideY = b.strideY; a.strideUV = b.strideUV; a.pitchY = b.pitchY; a.pitchUV = b.pitchUV;
+    a.dstY = (uint8_t*)store.Y + first_slot * r.w * r.h;
+    a.dstU = (uint8_t*)store.U + first_slot * r.wUV * r.hUV;
+    a.dstV = (uint8_t*)store.V + first_slot * r.wUV * r.hUV;
+    a.w = r.w; a.h = r.h; a.wUV = r.wUV; a.hUV = r.hUV;
+    // a slot's rows start at multiples of the row width from the store's base, so the width covers the destination's alignment too
+    auto width = [](uintptr_t v) { return v % 16 == 0 ? 16 : v % 4 == 0 ? 4 : 1; };
+    a.vbY = width((uintptr_t)a.srcY | (uintptr_t)store.Y | (uintptr_t)b.strideY | (uintptr_t)b.pitchY | (uintptr_t)r.w);
+    a.vbC = width((uintptr_t)a.srcU | (uintptr_t)a.srcV | (uintptr_t)store.U | (uintptr_t)store.V | (uintptr_t)b.strideUV | (uintptr_t)b.pitchUV |
+                  (uintptr_t)r.wUV);
+    a.vrowY = r.w / a.vbY; a.vrowC = r.wUV / a.vbC;
+    a.vecsY = a.vrowY * r.h; a.vecsC = a.vrowC * r.hUV;
+    const long long total = (long long)(a.vecsY + 2 * a.vecsC) * nkeep;
+    if (total <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(scan_keep_kernel, dim3(grid), dim3(256), 0, st, a, dkeep, total);
+    return hipGetLastError();
+}
+
 } // namespace amt

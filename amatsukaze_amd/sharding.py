@@ -162,6 +162,15 @@ def scan_logo_sharded(ctx, clip_local, serviceid, dstpath, imgx, imgy, w, h, thy
     return bool(ok)
 
 
+def scan_logo_stream_finish_sharded(stream, serviceid, dstpath, coll: TorchCollectives, cb=None):
+    """amtgpu_scanlogo_stream_finish_sharded: every rank has fed its own contiguous range of the stream (rank 0 the first frames) into
+    its own api.ScanLogoStream; the ranks agree on the quota, all-reduce each round's sums and rank 0 writes dstpath -- the .lgd of one
+    session fed the whole stream.  True/False like ScanLogoStream.finish."""
+    cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
+    return bool(stream.ctx.lib.amtgpu_scanlogo_stream_finish_sharded(stream.h, coll.ref(), serviceid, str(dstpath).encode() if dstpath else None,
+                                                                    cbf))
+
+
 def find_logo_sharded(ctx, clip_local, coll: TorchCollectives, cap=64, **params):
     """Automatic logo detection over frame-sharded ranks: each rank adds its own frames, the exact int64 sums (with the frame count)
     are all-reduced, every rank ranks the same candidates.  Returns (LogoFinder holding the whole clip's sums, candidates)."""

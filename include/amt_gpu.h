@@ -38,7 +38,8 @@ extern "C" {
                                    *    amtgpu_analyze_set_fixup_queue, amtgpu_erase_batch_dfades_to
                                    * 5 (later additions): AMTGPU_ANALYZE_LINEAR_MONITORED, amtgpu_analyze_set_monitor,
                                    *    amtgpu_analyze_monitor_stats; automatic logo detection (amtgpu_logofind_*,
-                                   *    amtgpu_scanlogo_auto, _auto_sharded, _file_auto) */
+                                   *    amtgpu_scanlogo_auto, _auto_sharded, _file_auto); the streamed ScanLogo session
+                                   *    (amtgpu_scanlogo_stream_*) */
 #define AMTGPU_NUM_FADE 11            /* LogoAnalyzeFrame p/t/b[11]  (LogoScan.hpp:1100-1103) */
 #define AMTGPU_ANALYZE_FLOATS 33      /* floats per source frame in an analysis record */
 
@@ -391,6 +392,38 @@ int  amtgpu_scanlogo_file(AmtGpuContext* ctx, const char* srcpath, int serviceid
 int  amtgpu_scanlogo_fileW(AmtGpuContext* ctx, const uint16_t* srcpath, int serviceid, const uint16_t* workfile, const uint16_t* dstpath,
                            int imgx, int imgy, int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb);
 
+/* ---- ScanLogo as a streaming session: the same logo generation for a host that decodes (an FFmpeg loop, an AviSynth clip, a pipe)
+ *      and cannot hold the clip in HBM.  create with the rectangle, feed device batches in stream order as they arrive, finish to get
+ *      the .lgd -- byte-identical to amtgpu_scanlogo over the same frames.  8-bit 4:2:0 like ScanLogo itself (LogoScan.hpp:813).  What
+ *      the session keeps in HBM is the rectangle of every kept frame (w*h*3/2 bytes each; the reference's work file, :899-903): the
+ *      store starts at min(numMaxFrames, 256) frames and doubles, so numMaxFrames may be "no limit" (1 << 30).
+ *      amtgpu_scanlogo_file is a client of it. ---- */
+typedef struct AmtGpuScanLogoStream AmtGpuScanLogoStream;
+/* NULL (message on the context) for the rectangles amtgpu_scanlogo refuses: outside the imgw x imgh frame, odd or non-positive w / h.
+ * numMaxFrames < 0 counts as 0 */
+AmtGpuScanLogoStream* amtgpu_scanlogo_stream_create(AmtGpuContext* ctx, int imgw, int imgh, int imgx, int imgy, int w, int h,
+                                                    int thy, int numMaxFrames);
+void amtgpu_scanlogo_stream_destroy(AmtGpuScanLogoStream* s);
+/* the next nframes frames of the stream, full frames on the device (strides in bytes, pitches in elements).  Valid frames (AddFrame's
+ * border verdict, :604-653) are kept in stream order until numMaxFrames are kept (:885); the frame that fills the quota may sit in
+ * the middle of a batch -- the frames behind it are neither kept nor counted as read.  *nkept = frames kept so far, *done = 1 from the
+ * call that fills the quota on (either may be NULL); a feed after that, or of 0 frames, returns 1 and changes nothing.
+ * Returns once the batch's verdicts have been read back (synchronises the context's stream up to them); the copy of the kept
+ * rectangles is only ENQUEUED on that stream when the call returns: overwrite the batch with work on the same stream, or after a
+ * marker / amtgpu_context_synchronize from anywhere else. */
+int  amtgpu_scanlogo_stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
+                                 int pitchY, int pitchUV, int nframes, int* nkept, int* done);
+/* the same on planes that hold ONLY the rectangle (w x h luma, w/2 x h/2 chroma per frame), as amtgpu_erase_rect_batch takes them */
+int  amtgpu_scanlogo_stream_feed_rect(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
+                                      int pitchY, int pitchUV, int nframes, int* nkept, int* done);
+/* *nread = the reference's readCount (:883): frames consumed up to and including the one that closed the stream; any pointer may be NULL */
+int  amtgpu_scanlogo_stream_status(const AmtGpuScanLogoStream* s, int64_t* nread, int* nkept, int* done);
+/* the initial regression and the two ReMakeLogo rounds (:923-1036) over the kept rectangles, cb driven from 50 % upward as by
+ * amtgpu_scanlogo; writes dstpath.  0 with "Insufficient logo frames" when nothing was kept or the regression fails, 0 with "Cancel
+ * requested" when cb returns 0.  The session is spent afterwards, whatever the outcome: a later feed or finish returns 0 with a message;
+ * destroy is always allowed. */
+int  amtgpu_scanlogo_stream_finish(AmtGpuScanLogoStream* s, int serviceid, const char* dstpath, AMTGPU_LOGO_ANALYZE_CB cb);
+
 /* ---- frame-sharded runs (one process per GPU).  The library does no communication itself: the host
  *      supplies two collectives over HOST memory -- RCCL in a C++ host (include/amt_rccl_collectives.hpp wraps an ncclComm_t),
  *      torch.distributed in the Python mirror (amatsukaze_amd/sharding.py).  Ranks hold contiguous frame ranges in stream
@@ -418,6 +451,14 @@ int  amtgpu_scanlogo_sharded(AmtGpuContext* ctx, const AmtGpuCollectives* coll, 
                              int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh,
                              int nframes_local, int serviceid, const char* dstpath, int imgx, int imgy, int w, int h,
                              int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb);
+
+/* The streamed ScanLogo session (amtgpu_scanlogo_stream_create above) frame-sharded: every rank has fed its own contiguous range of
+ * the stream into its own session, rank 0 the first frames, each keeping at most numMaxFrames of its own.  An all-gather of the kept counts cuts every rank's store to its share
+ * of the first numMaxFrames valid frames of the whole stream, the sums of each round are all-reduced, every rank solves, rank 0
+ * writes dstpath (others may pass NULL): the .lgd of one session fed the whole stream.  Failure and cancel on any rank end the call
+ * on all, as in amtgpu_scanlogo_sharded. */
+int  amtgpu_scanlogo_stream_finish_sharded(AmtGpuScanLogoStream* s, const AmtGpuCollectives* coll, int serviceid, const char* dstpath,
+                                           AMTGPU_LOGO_ANALYZE_CB cb);
 
 /* ---- self-specified whole-frame passes (NO in-tree reference arithmetic: SURVEY.md section 0;
  *      "parity unpinned").  Stand in for what chapter_exe (CMAnalyze.hpp:319-337) and KFMDeint's
