@@ -533,16 +533,19 @@ class LogoScan:
 
 
 def ScanLogo(ctx: Context, clip: DeviceClip, serviceid, dstpath, imgx, imgy, w, h, thy, numMaxFrames, cb=None):
-    """The exported ScanLogo (LogoScan.hpp:1083-1098) over a device clip; returns True/False like it."""
+    """The exported ScanLogo (LogoScan.hpp:1083-1098) over a device clip; returns True/False like it.  The clip's depth is clip.bits
+    (8, or 9..12 in 16-bit containers); thy is in container units of that depth."""
     cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
-    ok = ctx.lib.amtgpu_scanlogo(ctx.h, _p(clip.Y), _p(clip.U), _p(clip.V), clip.strideY, clip.strideUV, clip.pitchY, clip.pitchUV,
-                                 clip.width, clip.height, clip.num_frames, serviceid, str(dstpath).encode(), imgx, imgy, w, h, thy,
-                                 numMaxFrames, cbf)
-    return bool(ok)
+    planes = (ctx.h, _p(clip.Y), _p(clip.U), _p(clip.V), clip.strideY, clip.strideUV, clip.pitchY, clip.pitchUV, clip.width, clip.height)
+    rest = (clip.num_frames, serviceid, str(dstpath).encode(), imgx, imgy, w, h, thy, numMaxFrames, cbf)
+    if clip.bits == 8:
+        return bool(ctx.lib.amtgpu_scanlogo(*planes, *rest))
+    return bool(ctx.lib.amtgpu_scanlogo_bits(*planes, clip.bits, *rest))
 
 
 def ScanLogoFile(ctx: Context, srcpath, serviceid, workfile, dstpath, imgx, imgy, w, h, thy, numMaxFrames, cb=None):
-    """ScanLogo with the reference's own argument list (LogoScan.hpp:1083-1098) over a raw 'AMTR' clip file; True/False like it."""
+    """ScanLogo with the reference's own argument list (LogoScan.hpp:1083-1098) over a raw clip file ('AMTR': 8-bit, 'AMTH': 9..12-bit);
+    True/False like it."""
     cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
     return bool(ctx.lib.amtgpu_scanlogo_file(ctx.h, str(srcpath).encode(), serviceid, str(workfile).encode(), str(dstpath).encode(), imgx, imgy,
                                              w, h, thy, numMaxFrames, cbf))
@@ -645,18 +648,21 @@ class LogoFinder:
 
 def ScanLogoAuto(ctx: Context, clip: DeviceClip, serviceid, dstpath, thy, numMaxFrames, cb=None, **params):
     """ScanLogo without a rectangle: detection over the whole clip, then ScanLogo on the best candidate.  Returns (ok, LogoCandidate or
-    None); with no candidate ok is False and the context's message is "no logo found"."""
+    None); with no candidate ok is False and the context's message is "no logo found".  Detection and scan run at clip.bits."""
     cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
     found = binding.LogoRect()
     p = logo_find_params(**params)
-    ok = ctx.lib.amtgpu_scanlogo_auto(ctx.h, _p(clip.Y), _p(clip.U), _p(clip.V), clip.strideY, clip.strideUV, clip.pitchY, clip.pitchUV,
-                                      clip.width, clip.height, clip.num_frames, serviceid, str(dstpath).encode() if dstpath else None, thy,
-                                      numMaxFrames, cbf, C.byref(p), C.byref(found))
+    planes = (ctx.h, _p(clip.Y), _p(clip.U), _p(clip.V), clip.strideY, clip.strideUV, clip.pitchY, clip.pitchUV, clip.width, clip.height)
+    rest = (clip.num_frames, serviceid, str(dstpath).encode() if dstpath else None, thy, numMaxFrames, cbf, C.byref(p), C.byref(found))
+    if clip.bits == 8:
+        ok = ctx.lib.amtgpu_scanlogo_auto(*planes, *rest)
+    else:
+        ok = ctx.lib.amtgpu_scanlogo_auto_bits(*planes, clip.bits, *rest)
     return bool(ok), (LogoCandidate._of(found) if found.w > 0 else None)
 
 
 def ScanLogoFileAuto(ctx: Context, srcpath, serviceid, workfile, dstpath, thy, numMaxFrames, cb=None, **params):
-    """ScanLogoFile without a rectangle (the raw 'AMTR' clip is read twice); returns (ok, LogoCandidate or None)"""
+    """ScanLogoFile without a rectangle (the raw 'AMTR' / 'AMTH' clip is read twice); returns (ok, LogoCandidate or None)"""
     cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
     found = binding.LogoRect()
     p = logo_find_params(**params)
@@ -669,11 +675,14 @@ class ScanLogoStream:
     """ScanLogo as a session fed with frame batches (amtgpu_scanlogo_stream_*): for a clip that is decoded as it goes and never
     resident.  feed / feed_rect return (frames kept so far, done); finish writes the .lgd -- byte-identical to ScanLogo over the same
     frames -- and returns True / False like ScanLogo (the message stays on the context).  A batch may be overwritten by work on the
-    context's stream as soon as its feed has returned."""
+    context's stream as soon as its feed has returned.  bits: the depth of every frame fed (8, or 9..12 in 16-bit containers)."""
 
-    def __init__(self, ctx: Context, imgw, imgh, imgx, imgy, w, h, thy, numMaxFrames):
-        self.ctx = ctx
-        self.h = ctx.lib.amtgpu_scanlogo_stream_create(ctx.h, imgw, imgh, imgx, imgy, w, h, thy, numMaxFrames)
+    def __init__(self, ctx: Context, imgw, imgh, imgx, imgy, w, h, thy, numMaxFrames, bits=8):
+        self.ctx, self.bits = ctx, bits
+        if bits == 8:
+            self.h = ctx.lib.amtgpu_scanlogo_stream_create(ctx.h, imgw, imgh, imgx, imgy, w, h, thy, numMaxFrames)
+        else:
+            self.h = ctx.lib.amtgpu_scanlogo_stream_create_bits(ctx.h, imgw, imgh, bits, imgx, imgy, w, h, thy, numMaxFrames)
         ctx.check(self.h, "ScanLogoStream")
 
     def _fed(self, fn, Y, U, V, strideY, strideUV, pitchY, pitchUV, n):
@@ -682,15 +691,20 @@ class ScanLogoStream:
         return nkept.value, bool(done.value)
 
     def feed(self, clip: DeviceClip):
-        """the next frames of the stream, full 8-bit frames"""
-        if clip.bits != 8:
-            raise AmtError("ScanLogoStream: 8-bit clips only")
+        """the next frames of the stream, full frames of the session's depth"""
+        if clip.bits != self.bits:
+            raise AmtError(f"ScanLogoStream: a {clip.bits}-bit clip fed to a {self.bits}-bit session")
         return self._fed(self.ctx.lib.amtgpu_scanlogo_stream_feed, clip.Y, clip.U, clip.V, clip.strideY, clip.strideUV, clip.pitchY,
                          clip.pitchUV, clip.num_frames)
 
     def feed_rect(self, Y, U, V):
-        """the same on device planes that hold only the rectangle: Y [n, h, w], U / V [n, h/2, w/2] uint8 (any row pitch)"""
-        return self._fed(self.ctx.lib.amtgpu_scanlogo_stream_feed_rect, Y, U, V, int(Y.stride(0)), int(U.stride(0)), int(Y.stride(1)),
+        """the same on device planes that hold only the rectangle: Y [n, h, w], U / V [n, h/2, w/2] (any row pitch); uint8, or int16 /
+        uint16 when the session is deeper than 8 bits"""
+        es = 1 if self.bits <= 8 else 2
+        for t in (Y, U, V):
+            if t.element_size() != es:
+                raise AmtError(f"ScanLogoStream: {es}-byte samples expected for a {self.bits}-bit session, got {t.dtype}")
+        return self._fed(self.ctx.lib.amtgpu_scanlogo_stream_feed_rect, Y, U, V, int(Y.stride(0)) * es, int(U.stride(0)) * es, int(Y.stride(1)),
                          int(U.stride(1)), int(Y.shape[0]))
 
     def status(self):
@@ -711,18 +725,18 @@ class ScanLogoStream:
             pass
 
 
-def ScanLogoAutoStream(ctx: Context, batches, width, height, serviceid, dstpath, thy, numMaxFrames, cb=None, **params):
+def ScanLogoAutoStream(ctx: Context, batches, width, height, serviceid, dstpath, thy, numMaxFrames, cb=None, bits=8, **params):
     """ScanLogoAuto over a clip that is streamed, not resident: `batches` is a callable that returns a fresh iterator of DeviceClip
-    batches (8-bit, in stream order).  Pass 1 feeds every batch to a LogoFinder; pass 2 feeds a ScanLogoStream on the best candidate and
+    batches (`bits` deep, in stream order).  Pass 1 feeds every batch to a LogoFinder; pass 2 feeds a ScanLogoStream on the best candidate and
     stops iterating once its quota is full.  Returns the LogoCandidate; raises AmtError ("no logo found", or ScanLogo's message)."""
-    finder = LogoFinder(ctx, width, height, 8)
+    finder = LogoFinder(ctx, width, height, bits)
     for clip in batches():
         finder.add(clip)
     cands = finder.candidates(1, **params)
     if not cands:
         raise AmtError("no logo found")
     r = cands[0]
-    stream = ScanLogoStream(ctx, width, height, r.imgx, r.imgy, r.w, r.h, thy, numMaxFrames)
+    stream = ScanLogoStream(ctx, width, height, r.imgx, r.imgy, r.w, r.h, thy, numMaxFrames, bits=bits)
     for clip in batches():
         if stream.feed(clip)[1]:
             break

@@ -173,6 +173,14 @@ SIGNATURES = {
     "amtgpu_scanlogo_stream_status": (c_i, [c_p, c_p, c_p, c_p]),
     "amtgpu_scanlogo_stream_finish": (c_i, [c_p, c_i, c_s, CB]),
     "amtgpu_scanlogo_stream_finish_sharded": (c_i, [c_p, c_p, c_i, c_s, CB]),
+    # ScanLogo for 8..12-bit clips: the signatures above with `int bits` after imgh
+    "amtgpu_scanlogo_bits": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_s, c_i, c_i, c_i, c_i, c_i, c_i, CB]),
+    "amtgpu_scanlogo_sharded_bits": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_s, c_i, c_i, c_i, c_i, c_i,
+                                           c_i, CB]),
+    "amtgpu_scanlogo_stream_create_bits": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    "amtgpu_scanlogo_auto_bits": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_s, c_i, c_i, CB, c_p, c_p]),
+    "amtgpu_scanlogo_auto_sharded_bits": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_s, c_i, c_i, CB, c_p,
+                                                c_p]),
 }
 
 _lib = None

@@ -22,6 +22,22 @@ static PlaneBatch plane_batch(int bits, const void* Y, const void* U, const void
     return PlaneBatch{Y, U, V, strideY / es, strideUV / es, pitchY, pitchUV};
 }
 
+// What every ScanLogo entry point checks before it touches a plane: the depth (8: bytes; 9..12: 16-bit little-endian containers, the
+// range LogoColor::Add's int products hold), thy against the border histogram, and strides / plane bases against the sample size.
+static int scan_sample_size(int bits, int thy)
+{
+    if (bits < 8 || bits > 12) throw std::runtime_error("[ScanLogo] bits must be 8..12");
+    if (bits > 8 && thy >= (1 << bits)) throw std::runtime_error("[ScanLogo] thy must be below 1 << bits for a clip of more than 8 bits");
+    return bits <= 8 ? 1 : 2;
+}
+static PlaneBatch scan_plane_batch(int bits, const void* Y, const void* U, const void* V, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV)
+{
+    const int es = bits <= 8 ? 1 : 2;
+    if (strideY % es || strideUV % es) throw std::runtime_error("[ScanLogo] odd byte stride for 16-bit samples");
+    if ((uintptr_t)Y % es || (uintptr_t)U % es || (uintptr_t)V % es) throw std::runtime_error("[ScanLogo] plane base not aligned to the sample size");
+    return PlaneBatch{Y, U, V, strideY / es, strideUV / es, pitchY, pitchUV};
+}
+
 // ---------------------------------------------------------------------------------------------
 // AMTEraseLogo
 // ---------------------------------------------------------------------------------------------
@@ -467,17 +483,18 @@ void reduce_scan(AmtGpuLogoScan* s, ShardGuard& sg, size_t npx)
     if (!amtgpu_logoscan_set_sums(s, buf.data(), buf.data() + npx, (int)buf[npx + 6])) throw std::runtime_error(s->ctx->err);
 }
 
-// ReMakeLogo twice (LogoScan.hpp:923-1036, 1065-1071) over a device-resident 8-bit clip: `kept` lists the frames round 0 accepted (indices
-// into the clip), whose rectangle is r; the finished logo's header gets (himgw, himgh, himgx, himgy).
+// ReMakeLogo twice (LogoScan.hpp:923-1036, 1065-1071) over a device-resident clip `bits` deep (maxv wherever the 8-bit text says 255,
+// as AMTAnalyzeLogo does, :1130): `kept` lists the frames round 0 accepted (indices into the clip), whose rectangle is r; the finished
+// logo's header gets (himgw, himgh, himgx, himgy).
 template <typename Progress>
-std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtGpuLogoScan* scan0, const PlaneBatch& clip, const ScanRect& r, int thy,
+std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtGpuLogoScan* scan0, const PlaneBatch& clip, int bits, const ScanRect& r, int thy,
                                           const std::vector<int>& kept, const std::vector<int4>& keptVerdict, int himgw, int himgh, int himgx,
                                           int himgy, Progress&& progress)
 {
     const size_t npx = (size_t)3 * ((size_t)r.w * r.h + 2 * (size_t)r.wUV * r.hUV);
-    const int bits = 8;
+    const int maxv = (1 << bits) - 1;
     const int numFrames = (int)kept.size();
-    std::unique_ptr<AmtGpuLogo> logo(amtgpu_logoscan_get_logo(scan0, 255, 0, himgw, himgh, himgx, himgy));
+    std::unique_ptr<AmtGpuLogo> logo(amtgpu_logoscan_get_logo(scan0, maxv, 0, himgw, himgh, himgx, himgy));
     if (!logo) throw std::runtime_error(c->err);
     DevBuf<int> dMap;
     if (numFrames) dMap.upload(kept, c->stream);
@@ -498,7 +515,7 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
             EvalEngine eng(c, std::move(specs), fades, true, 20, "logo_eval_fused_kernel.remake");
             std::vector<uint8_t> use(numFrames, 0);
             if (numFrames) {
-                eng.run(clip.Y, clip.strideY, clip.pitchY, bits, numFrames, dEval.get(), dMap.get());       // (8 bits: a sample is a byte)
+                eng.run(clip.Y, clip.strideY * (bits <= 8 ? 1 : 2), clip.pitchY, bits, numFrames, dEval.get(), dMap.get());       // (stride in bytes)
                 download_via_pinned(c, hEval.data(), dEval.get(), hEval.size() * sizeof(float));
             }
             for (int i = 0; i < numFrames; ++i) {
@@ -513,16 +530,20 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
             if (numFrames) logoscan_add(rescan.get(), clip, r, bits, numFrames, numFrames, use.data(), nullptr, kept.data(), keptVerdict.data());
         });
         reduce_scan(rescan.get(), sg, npx);
-        logo.reset(amtgpu_logoscan_get_logo(rescan.get(), 255, 1, himgw, himgh, himgx, himgy));
+        logo.reset(amtgpu_logoscan_get_logo(rescan.get(), maxv, 1, himgw, himgh, himgx, himgy));
         if (!logo) throw std::runtime_error(c->err);
     }
     return logo;
 }
 
-int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const PlaneBatch& clip, int imgw, int imgh, int nframes, int serviceid,
-                  const char* dstpath, const ScanRect& r, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
+int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
+                  int pitchY, int pitchUV, int imgw, int imgh, int bits, int nframes, int serviceid, const char* dstpath, const ScanRect& r, int thy,
+                  int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
 {
+    if (!c) return 0;
     return guard(c, [&] {
+        const int es = scan_sample_size(bits, thy);          // (refused before anything is exchanged: the same on every rank)
+        PlaneBatch clip{};
         const bool sharded = coll && coll->world > 1;
         if (sharded && (!coll->allgather || !coll->allreduce_sum_i64 || coll->rank < 0 || coll->rank >= coll->world))
             throw std::runtime_error("AmtGpuCollectives incomplete");
@@ -534,7 +555,6 @@ int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const PlaneBa
                 sg.cancel = 1;                                  // the other ranks learn about it with the next exchange
             }
         };
-        const int bits = 8, es = 1;                           // the reference's scan path is 8-bit only (:813)
         const size_t npx = (size_t)3 * ((size_t)std::max(0, r.w) * std::max(0, r.h) + 2 * (size_t)(std::max(0, r.w) / 2) * (std::max(0, r.h) / 2));
         std::unique_ptr<AmtGpuLogoScan> scan;
         std::vector<int> kept;              // frame index (within this rank's frames) of every kept frame
@@ -545,6 +565,7 @@ int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const PlaneBa
         auto wanted = [&] { return sharded || (int)kept.size() < numMaxFrames; };
         sg.attempt([&] {
             if (r.imgx < 0 || r.imgy < 0 || r.imgx + r.w > imgw || r.imgy + r.h > imgh) throw std::runtime_error("scan rectangle outside the frame");
+            clip = scan_plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV);
             scan.reset(logoscan_new(c, r.w, r.h, 1, 1, thy));
             for (int f0 = 0; f0 < nframes && wanted(); f0 += chunk) {
                 const int n = std::min(chunk, nframes - f0);
@@ -574,7 +595,7 @@ int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const PlaneBa
             reduce_scan(scan.get(), sg, npx);
         }
         const int numFrames = (int)kept.size();
-        std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, scan.get(), clip, r, thy, kept, keptVerdict, imgw, imgh, r.imgx, r.imgy, progress);
+        std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, scan.get(), clip, bits, r, thy, kept, keptVerdict, imgw, imgh, r.imgx, r.imgy, progress);
         progress(1, numFrames, numFrames, numFrames);
         if (dstpath && (!sharded || coll->rank == 0)) save_lgd(logo->planes, dstpath, "No Name", serviceid);
     });
@@ -590,9 +611,10 @@ int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const PlaneBa
 struct AmtGpuScanLogoStream {
     AmtGpuContext* ctx = nullptr;
     int imgw = 0, imgh = 0, thy = 0, numMaxFrames = 0;
+    int bits = 8, es = 1;                       // depth of the clip, bytes per sample
     ScanRect rect{};                            // the rectangle in a full frame
     std::unique_ptr<AmtGpuLogoScan> scan;       // the feeds' border verdicts; round 0's sums, accumulated from the store at the finish
-    DevBuf<uint8_t> storeY, storeU, storeV;     // rectangles of the kept frames, tight: Y [n][h][w], U / V [n][h/2][w/2]
+    DevBuf<uint8_t> storeY, storeU, storeV;     // rectangles of the kept frames, tight: Y [n][h][w], U / V [n][h/2][w/2] samples of es bytes
     int cap = 0;                                // frames the store has room for
     std::vector<int4> keptVerdict;              // {1, bgY, bgU, bgV} of every kept frame
     int64_t nread = 0;                          // readCount (:883): frames consumed up to and including the one that closed the stream
@@ -603,6 +625,8 @@ struct AmtGpuScanLogoStream {
     DevBuf<int> dKeep;
     hipEvent_t keepUploaded = nullptr;
     int nkept() const { return (int)keptVerdict.size(); }
+    size_t slotY() const { return (size_t)rect.w * rect.h * es; }           // bytes of one kept frame's luma / chroma rectangle
+    size_t slotC() const { return (size_t)rect.wUV * rect.hUV * es; }
     ~AmtGpuScanLogoStream()
     {
         if (keepUploaded) { (void)hipEventSynchronize(keepUploaded); (void)hipEventDestroy(keepUploaded); }
@@ -612,22 +636,23 @@ struct AmtGpuScanLogoStream {
 
 namespace {
 
-AmtGpuScanLogoStream* stream_new(AmtGpuContext* c, int imgw, int imgh, int imgx, int imgy, int w, int h, int thy, int numMaxFrames)
+AmtGpuScanLogoStream* stream_new(AmtGpuContext* c, int imgw, int imgh, int bits, int imgx, int imgy, int w, int h, int thy, int numMaxFrames)
 {
+    const int es = scan_sample_size(bits, thy);
     if (imgx < 0 || imgy < 0 || w > imgw - imgx || h > imgh - imgy) throw std::runtime_error("scan rectangle outside the frame");
     std::unique_ptr<AmtGpuScanLogoStream> s(new AmtGpuScanLogoStream);
     s->ctx = c;
     s->imgw = imgw; s->imgh = imgh; s->thy = thy;
+    s->bits = bits; s->es = es;
     s->numMaxFrames = std::max(0, numMaxFrames);
     s->scan.reset(logoscan_new(c, w, h, 1, 1, thy));       // (refuses odd and non-positive sizes)
     s->rect = scan_rect(imgx, imgy, w, h);
     s->done = s->numMaxFrames == 0;
     // the store grows with what is kept: numMaxFrames is a limit (callers pass 1 << 30), not a size
     s->cap = std::max(1, std::min(s->numMaxFrames, 256));
-    const ScanRect& r = s->rect;
-    s->storeY.alloc((size_t)s->cap * r.w * r.h);
-    s->storeU.alloc((size_t)s->cap * r.wUV * r.hUV);
-    s->storeV.alloc((size_t)s->cap * r.wUV * r.hUV);
+    s->storeY.alloc(s->cap * s->slotY());
+    s->storeU.alloc(s->cap * s->slotC());
+    s->storeV.alloc(s->cap * s->slotC());
     AMT_HIP(hipEventCreateWithFlags(&s->keepUploaded, hipEventDisableTiming));
     return s.release();
 }
@@ -637,8 +662,7 @@ void stream_reserve(AmtGpuScanLogoStream* s, int need)
 {
     if (need <= s->cap) return;
     const int ncap = (int)std::min<int64_t>(s->numMaxFrames, std::max<int64_t>(need, 2 * (int64_t)s->cap));
-    const ScanRect& r = s->rect;
-    const size_t ysz = (size_t)r.w * r.h, csz = (size_t)r.wUV * r.hUV, n = (size_t)s->nkept();
+    const size_t ysz = s->slotY(), csz = s->slotC(), n = (size_t)s->nkept();
     DevBuf<uint8_t> nY(ysz * ncap), nU(csz * ncap), nV(csz * ncap);
     if (n) {
         hipStream_t st = s->ctx->stream;
@@ -661,10 +685,10 @@ void stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const 
     if (!dY || !dU || !dV) throw std::runtime_error("[ScanLogo] null plane");
     const ScanRect r = rect_only ? scan_rect(0, 0, s->rect.w, s->rect.h) : s->rect;
     if (pitchY < r.imgx + r.w || pitchUV < r.cx + r.wUV) throw std::runtime_error("[ScanLogo] pitch smaller than the rectangle's rows");
-    const PlaneBatch b = plane_batch(8, dY, dU, dV, strideY, strideUV, pitchY, pitchUV);
+    const PlaneBatch b = scan_plane_batch(s->bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV);
     AmtGpuContext* c = s->ctx;
     // verdicts alone (quota 0): which valid frames count is decided here, in stream order
-    logoscan_add(s->scan.get(), b, r, 8, nframes, 0, nullptr, nullptr, nullptr, nullptr);
+    logoscan_add(s->scan.get(), b, r, s->bits, nframes, 0, nullptr, nullptr, nullptr, nullptr);
     const std::vector<int4>& v = s->scan->lastVerdicts;
     AMT_HIP(hipEventSynchronize(s->keepUploaded));
     if (s->keepCap < (size_t)nframes) {
@@ -686,7 +710,7 @@ void stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const 
         AMT_HIP(hipMemcpyAsync(s->dKeep.get(), s->hKeep, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
         AMT_HIP(hipEventRecord(s->keepUploaded, c->stream));
         const int sp = c->prof_begin("scan_keep_kernel");
-        AMT_HIP(launch_scan_keep(c->stream, b, r, s->dKeep.get(), m, PlanesOut{s->storeY.get(), s->storeU.get(), s->storeV.get()}, first));
+        AMT_HIP(launch_scan_keep(c->stream, s->es, b, r, s->dKeep.get(), m, PlanesOut{s->storeY.get(), s->storeU.get(), s->storeV.get()}, first));
         c->prof_end(sp);
         for (int k = 0; k < m; ++k) s->keptVerdict.push_back(v[s->hKeep[k]]);
     }
@@ -734,10 +758,10 @@ void stream_finish(AmtGpuScanLogoStream* s, const AmtGpuCollectives* coll, int s
     for (int i = 0; i < n; ++i) kept[i] = i;
     const std::vector<int4> verdicts(s->keptVerdict.begin(), s->keptVerdict.begin() + n);
     sg.attempt([&] {
-        if (n) logoscan_add(s->scan.get(), crops, r, 8, n, n, nullptr, nullptr, kept.data(), verdicts.data());
+        if (n) logoscan_add(s->scan.get(), crops, r, s->bits, n, n, nullptr, nullptr, kept.data(), verdicts.data());
     });
     reduce_scan(s->scan.get(), sg, npx);
-    std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, s->scan.get(), crops, r, s->thy, kept, verdicts, s->imgw, s->imgh, fr.imgx, fr.imgy,
+    std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, s->scan.get(), crops, s->bits, r, s->thy, kept, verdicts, s->imgw, s->imgh, fr.imgx, fr.imgy,
                                                      progress);
     progress(1, n, n, n);
     if (dstpath && (!sharded || coll->rank == 0)) save_lgd(logo->planes, dstpath, "No Name", serviceid);
@@ -754,13 +778,19 @@ void stream_report(const AmtGpuScanLogoStream* s, int64_t* nread, int* nkept, in
 
 extern "C" {
 
-AmtGpuScanLogoStream* amtgpu_scanlogo_stream_create(AmtGpuContext* c, int imgw, int imgh, int imgx, int imgy, int w, int h, int thy,
-                                                    int numMaxFrames)
+AmtGpuScanLogoStream* amtgpu_scanlogo_stream_create_bits(AmtGpuContext* c, int imgw, int imgh, int bits, int imgx, int imgy, int w, int h, int thy,
+                                                         int numMaxFrames)
 {
     if (!c) return nullptr;
     AmtGpuScanLogoStream* s = nullptr;
-    guard(c, [&] { s = stream_new(c, imgw, imgh, imgx, imgy, w, h, thy, numMaxFrames); });
+    guard(c, [&] { s = stream_new(c, imgw, imgh, bits, imgx, imgy, w, h, thy, numMaxFrames); });
     return s;
+}
+
+AmtGpuScanLogoStream* amtgpu_scanlogo_stream_create(AmtGpuContext* c, int imgw, int imgh, int imgx, int imgy, int w, int h, int thy,
+                                                    int numMaxFrames)
+{
+    return amtgpu_scanlogo_stream_create_bits(c, imgw, imgh, 8, imgx, imgy, w, h, thy, numMaxFrames);
 }
 
 void amtgpu_scanlogo_stream_destroy(AmtGpuScanLogoStream* s) { delete s; }
@@ -804,19 +834,28 @@ int amtgpu_scanlogo_stream_finish_sharded(AmtGpuScanLogoStream* s, const AmtGpuC
     return guard(s->ctx, [&] { stream_finish(s, coll, serviceid, dstpath, cb); });
 }
 
+int amtgpu_scanlogo_bits(AmtGpuContext* c, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
+                         int pitchY, int pitchUV, int imgw, int imgh, int bits, int nframes, int serviceid, const char* dstpath, int imgx,
+                         int imgy, int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
+{
+    return scanlogo_impl(c, nullptr, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, bits, nframes, serviceid, dstpath,
+                         scan_rect(imgx, imgy, w, h), thy, numMaxFrames, cb);
+}
+
 int amtgpu_scanlogo(AmtGpuContext* c, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
                     int pitchY, int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath, int imgx,
                     int imgy, int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
 {
-    return scanlogo_impl(c, nullptr, plane_batch(8, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), imgw, imgh, nframes, serviceid, dstpath,
-                         scan_rect(imgx, imgy, w, h), thy, numMaxFrames, cb);
+    return amtgpu_scanlogo_bits(c, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, 8, nframes, serviceid, dstpath, imgx, imgy, w, h,
+                                thy, numMaxFrames, cb);
 }
 
 // The reference's exported ScanLogo, argument for argument (LogoScan.hpp:1083-1098; C# P/Invoke AmatsukazeNatives.cs:391-393), over a
-// raw 8-bit 4:2:0 clip file instead of a transport stream (decode is out of scope): int32 {'AMTR', width, height, nframes} followed by
-// tight Y, U, V planes per frame.  Frames are streamed through the pinned ring in chunks and fed to a ScanLogo session (above): only
-// the rectangles of accepted frames stay in HBM for the two ReMakeLogo rounds (the reference keeps them in `workfile` through a
-// lossless codec, :840-912 -- here the argument is accepted and the file left untouched).
+// raw 4:2:0 clip file instead of a transport stream (decode is out of scope): int32 {'AMTR', width, height, nframes} followed by
+// tight 8-bit Y, U, V planes per frame, or int32 {'AMTH', width, height, nframes, bits} (bits 9..12) followed by the same planes as
+// little-endian uint16 (amt_read_raw_clip_header, api_common.hpp).  Frames are streamed through the pinned ring in chunks and fed to a
+// ScanLogo session (above): only the rectangles of accepted frames stay in HBM for the two ReMakeLogo rounds (the reference keeps them
+// in `workfile` through a lossless codec, :840-912 -- here the argument is accepted and the file left untouched).
 int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, const char* workfile, const char* dstpath, int imgx, int imgy,
                          int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
 {
@@ -827,15 +866,13 @@ int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, c
         };
         std::ifstream f(srcpath, std::ios::binary);
         if (!f) throw std::runtime_error(std::string("failed to open file ") + srcpath);
-        int32_t hdr[4];
-        f.read(reinterpret_cast<char*>(hdr), sizeof hdr);
-        if (!f || hdr[0] != 0x52544D41 || hdr[1] <= 0 || hdr[2] <= 0 || hdr[3] < 0 || (hdr[1] & 1) || (hdr[2] & 1))
-            throw std::runtime_error("not a raw AMTR clip (int32 'AMTR', width, height, frames; 8-bit 4:2:0 planes)");
-        const int W = hdr[1], H = hdr[2], N = hdr[3];
-        const size_t ysz = (size_t)W * H, csz = (size_t)(W / 2) * (H / 2), fsz = ysz + 2 * csz;
+        const RawClipHeader hd = amt_read_raw_clip_header(f);
+        const int W = hd.width, H = hd.height, N = hd.frames, es = hd.bits <= 8 ? 1 : 2;
+        // (sizes in bytes)
+        const size_t ysz = (size_t)W * H * es, csz = (size_t)(W / 2) * (H / 2) * es, fsz = ysz + 2 * csz;
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>(1024, (256u << 20) / fsz));
         c->bind();
-        std::unique_ptr<AmtGpuScanLogoStream> s(stream_new(c, W, H, imgx, imgy, w, h, thy, numMaxFrames));
+        std::unique_ptr<AmtGpuScanLogoStream> s(stream_new(c, W, H, hd.bits, imgx, imgy, w, h, thy, numMaxFrames));
         DevBuf<uint8_t> dChunk(fsz * chunk);
         std::vector<uint8_t> host(fsz * chunk), planar(fsz * chunk);
         for (int f0 = 0; f0 < N && !s->done; f0 += chunk) {
@@ -850,7 +887,7 @@ int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, c
             }
             if (!amtgpu_frames_upload(c, dChunk.get(), planar.data(), fsz * n) || !amtgpu_frames_upload_wait(c)) throw std::runtime_error(c->err);
             const uint8_t *dY = dChunk.get(), *dU = dY + ysz * n, *dV = dU + csz * n;
-            stream_feed(s.get(), dY, dU, dV, (int64_t)ysz, (int64_t)csz, W, W / 2, n, false);
+            stream_feed(s.get(), dY, dU, dV, (int64_t)ysz, (int64_t)csz, W, W / 2, n, false);      // (strides in bytes, pitches in samples)
             AMT_HIP(hipStreamSynchronize(c->stream));          // the chunk buffer is refilled by the next upload
             progress(50.0f * (f0 + n) / std::max(1, N), f0 + n, 0, s->nkept());
         }
@@ -865,13 +902,22 @@ int amtgpu_scanlogo_fileW(AmtGpuContext* c, const uint16_t* srcpath, int service
     return amtgpu_scanlogo_file(c, src.c_str(), serviceid, work.c_str(), dst.c_str(), imgx, imgy, w, h, thy, numMaxFrames, cb);
 }
 
+int amtgpu_scanlogo_sharded_bits(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,
+                                 int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int bits, int nframes_local,
+                                 int serviceid, const char* dstpath, int imgx, int imgy, int w, int h, int thy, int numMaxFrames,
+                                 AMTGPU_LOGO_ANALYZE_CB cb)
+{
+    return scanlogo_impl(c, coll, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, bits, nframes_local, serviceid, dstpath,
+                         scan_rect(imgx, imgy, w, h), thy, numMaxFrames, cb);
+}
+
 int amtgpu_scanlogo_sharded(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,
                             int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int nframes_local,
                             int serviceid, const char* dstpath, int imgx, int imgy, int w, int h, int thy, int numMaxFrames,
                             AMTGPU_LOGO_ANALYZE_CB cb)
 {
-    return scanlogo_impl(c, coll, plane_batch(8, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), imgw, imgh, nframes_local, serviceid, dstpath,
-                         scan_rect(imgx, imgy, w, h), thy, numMaxFrames, cb);
+    return amtgpu_scanlogo_sharded_bits(c, coll, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, 8, nframes_local, serviceid, dstpath,
+                                        imgx, imgy, w, h, thy, numMaxFrames, cb);
 }
 
 } // extern "C"

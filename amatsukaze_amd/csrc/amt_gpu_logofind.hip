@@ -109,6 +109,15 @@ void logofind_reduce(AmtGpuLogoFind* lf, const AmtGpuCollectives* coll, std::str
 
 void zero_found(AmtGpuLogoRect* found) { if (found) std::memset(found, 0, sizeof *found); }
 
+// what amtgpu_scanlogo_*_bits refuses about the planes, before the detection reads them
+void check_scan_planes(int bits, const void* dY, int64_t strideY)
+{
+    if (bits < 8 || bits > 12) throw std::runtime_error("[ScanLogo] bits must be 8..12");
+    const int es = bits <= 8 ? 1 : 2;
+    if (strideY % es) throw std::runtime_error("[ScanLogo] odd byte stride for 16-bit samples");
+    if ((uintptr_t)dY % es) throw std::runtime_error("[ScanLogo] plane base not aligned to the sample size");
+}
+
 } // namespace
 
 extern "C" {
@@ -171,22 +180,56 @@ int amtgpu_logofind_allreduce(AmtGpuLogoFind* lf, const AmtGpuCollectives* coll)
     });
 }
 
-int amtgpu_scanlogo_auto(AmtGpuContext* c, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV, int pitchY,
-                         int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath, int thy, int numMaxFrames,
-                         AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found)
+int amtgpu_scanlogo_auto_bits(AmtGpuContext* c, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV, int pitchY,
+                              int pitchUV, int imgw, int imgh, int bits, int nframes, int serviceid, const char* dstpath, int thy, int numMaxFrames,
+                              AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found)
 {
     if (!c) return 0;
     zero_found(found);
     AmtGpuLogoRect r{};
     const int ok = guard(c, [&] {
-        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, 8));
+        check_scan_planes(bits, dY, strideY);
+        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, bits));
         logofind_add(lf.get(), dY, strideY, pitchY, nframes);
         r = best_rect(lf.get(), params);
     });
     if (!ok) return 0;
     if (found) *found = r;
-    return amtgpu_scanlogo(c, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, nframes, serviceid, dstpath, r.imgx, r.imgy, r.w, r.h,
-                           thy, numMaxFrames, cb);
+    return amtgpu_scanlogo_bits(c, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, bits, nframes, serviceid, dstpath, r.imgx, r.imgy,
+                                r.w, r.h, thy, numMaxFrames, cb);
+}
+
+int amtgpu_scanlogo_auto(AmtGpuContext* c, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV, int pitchY,
+                         int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath, int thy, int numMaxFrames,
+                         AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found)
+{
+    return amtgpu_scanlogo_auto_bits(c, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, 8, nframes, serviceid, dstpath, thy,
+                                     numMaxFrames, cb, params, found);
+}
+
+int amtgpu_scanlogo_auto_sharded_bits(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,
+                                      int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int bits, int nframes_local,
+                                      int serviceid, const char* dstpath, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb,
+                                      const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found)
+{
+    if (!c) return 0;
+    zero_found(found);
+    AmtGpuLogoRect r{};
+    const int ok = guard(c, [&] {
+        if (bits < 8 || bits > 12) throw std::runtime_error("[ScanLogo] bits must be 8..12");       // (the same on every rank)
+        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, bits));
+        std::string err;
+        try {
+            check_scan_planes(bits, dY, strideY);
+            logofind_add(lf.get(), dY, strideY, pitchY, nframes_local);
+        } catch (const std::exception& e) { err = e.what(); }
+        logofind_reduce(lf.get(), coll, err);
+        r = best_rect(lf.get(), params);       // identical sums on every rank: the same answer (or the same "no logo found") everywhere
+    });
+    if (!ok) return 0;
+    if (found) *found = r;
+    return amtgpu_scanlogo_sharded_bits(c, coll, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, bits, nframes_local, serviceid,
+                                        dstpath, r.imgx, r.imgy, r.w, r.h, thy, numMaxFrames, cb);
 }
 
 int amtgpu_scanlogo_auto_sharded(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV, int64_t strideY,
@@ -194,23 +237,11 @@ int amtgpu_scanlogo_auto_sharded(AmtGpuContext* c, const AmtGpuCollectives* coll
                                  const char* dstpath, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params,
                                  AmtGpuLogoRect* found)
 {
-    if (!c) return 0;
-    zero_found(found);
-    AmtGpuLogoRect r{};
-    const int ok = guard(c, [&] {
-        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, 8));
-        std::string err;
-        try { logofind_add(lf.get(), dY, strideY, pitchY, nframes_local); } catch (const std::exception& e) { err = e.what(); }
-        logofind_reduce(lf.get(), coll, err);
-        r = best_rect(lf.get(), params);       // identical sums on every rank: the same answer (or the same "no logo found") everywhere
-    });
-    if (!ok) return 0;
-    if (found) *found = r;
-    return amtgpu_scanlogo_sharded(c, coll, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, nframes_local, serviceid, dstpath,
-                                   r.imgx, r.imgy, r.w, r.h, thy, numMaxFrames, cb);
+    return amtgpu_scanlogo_auto_sharded_bits(c, coll, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, 8, nframes_local, serviceid,
+                                             dstpath, thy, numMaxFrames, cb, params, found);
 }
 
-// pass 1 over the raw clip: the Y planes only, chunk by chunk through the pinned upload path; pass 2 is amtgpu_scanlogo_file itself
+// pass 1 over the raw clip ('AMTR' or 'AMTH'): the Y planes only, chunk by chunk through the pinned upload path; pass 2 is amtgpu_scanlogo_file itself
 int amtgpu_scanlogo_file_auto(AmtGpuContext* c, const char* srcpath, int serviceid, const char* workfile, const char* dstpath, int thy,
                               int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found)
 {
@@ -221,14 +252,12 @@ int amtgpu_scanlogo_file_auto(AmtGpuContext* c, const char* srcpath, int service
         if (!srcpath) throw std::runtime_error("null source path");
         std::ifstream f(srcpath, std::ios::binary);
         if (!f) throw std::runtime_error(std::string("failed to open file ") + srcpath);
-        int32_t hdr[4];
-        f.read(reinterpret_cast<char*>(hdr), sizeof hdr);
-        if (!f || hdr[0] != 0x52544D41 || hdr[1] <= 0 || hdr[2] <= 0 || hdr[3] < 0 || (hdr[1] & 1) || (hdr[2] & 1))
-            throw std::runtime_error("not a raw AMTR clip (int32 'AMTR', width, height, frames; 8-bit 4:2:0 planes)");
-        const int W = hdr[1], H = hdr[2], N = hdr[3];
-        const size_t ysz = (size_t)W * H, csz = (size_t)(W / 2) * (H / 2), fsz = ysz + 2 * csz;
+        const RawClipHeader hd = amt_read_raw_clip_header(f);
+        const int W = hd.width, H = hd.height, N = hd.frames, es = hd.bits <= 8 ? 1 : 2;
+        // (sizes in bytes)
+        const size_t ysz = (size_t)W * H * es, csz = (size_t)(W / 2) * (H / 2) * es, fsz = ysz + 2 * csz;
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>(1024, (256u << 20) / fsz));
-        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, W, H, 8));
+        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, W, H, hd.bits));
         DevBuf<uint8_t> dChunk(ysz * chunk);
         std::vector<uint8_t> host(fsz * chunk), planes(ysz * chunk);
         for (int f0 = 0; f0 < N; f0 += chunk) {

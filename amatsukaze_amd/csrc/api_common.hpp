@@ -5,7 +5,9 @@
 #include <cstdint>
 #include <cstring>
 #include <exception>
+#include <istream>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -47,6 +49,22 @@ inline std::string amt_utf8_from_utf16z(const uint16_t* s)
     size_t n = 0;
     while (s[n]) ++n;
     return amt_utf8_from_utf16(s, n);
+}
+
+// The header of a raw 4:2:0 clip file (amtgpu_scanlogo_file, _file_auto): little-endian int32 {'AMTR', width, height, frames} before tight
+// 8-bit Y, U, V planes per frame, or {'AMTH', width, height, frames, bits} with bits 9..12 before the same planes as little-endian uint16.
+struct RawClipHeader { int width, height, frames, bits; };
+inline RawClipHeader amt_read_raw_clip_header(std::istream& f)
+{
+    int32_t hdr[5] = {0, 0, 0, 0, 8};
+    f.read(reinterpret_cast<char*>(hdr), 4 * sizeof(int32_t));
+    const bool hibit = f && hdr[0] == 0x48544D41;
+    if (hibit) f.read(reinterpret_cast<char*>(hdr + 4), sizeof(int32_t));
+    if (!f || (hdr[0] != 0x52544D41 && !hibit) || hdr[1] <= 0 || hdr[2] <= 0 || hdr[3] < 0 || (hdr[1] & 1) || (hdr[2] & 1))
+        throw std::runtime_error("not a raw clip (int32 'AMTR', width, height, frames; 8-bit 4:2:0 planes -- or 'AMTH', width, height, frames, bits; "
+                                 "16-bit containers)");
+    if (hibit && (hdr[4] < 9 || hdr[4] > 12)) throw std::runtime_error("raw AMTH clip: bits must be 9..12 (8-bit clips are 'AMTR' files)");
+    return RawClipHeader{hdr[1], hdr[2], hdr[3], hdr[4]};
 }
 
 // run f(); on any exception keep the message on the context and return 0 (no exceptions cross the ABI)

@@ -6,6 +6,7 @@
 #include "build_knobs.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 
 #include "exact_math.h"
@@ -522,18 +523,18 @@ hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b,
 // The streamed ScanLogo's store (InitialLogoCreator::onFrame keeps every accepted frame's rectangle, LogoScan.hpp:899-903): the
 // rectangles of the `nkeep` frames of a batch listed in `keep` (batch-local indices, ascending) go to consecutive slots of the tight
 // store, Y [slot][h][w], U / V [slot][h/2][w/2], all three planes of all listed frames in one launch.  A pure HBM copy addressed like
-// ingest_rows_kernel: a row's lanes sit on consecutive bytes, one lane moves 16 bytes where the plane's base, stride, pitch, origin
-// and width are all multiples of 16, else 4, else 1 -- decided per plane kind (luma / chroma) by the launcher, so an odd chroma
-// origin costs the luma rows nothing.  8-bit samples: strides and pitches in samples are bytes.
+// ingest_rows_kernel, in BYTES whatever the sample size es (1 or 2): a row's lanes sit on consecutive bytes, one lane moves 16 bytes
+// where the plane's base, stride, pitch, origin and row length are all multiples of 16, else 4, else one sample (es) -- decided per
+// plane kind (luma / chroma) by the launcher, so an odd chroma origin costs the luma rows nothing.
 // ------------------------------------------------------------------------------------------------
 struct ScanKeepArgs {
     const uint8_t *srcY, *srcU, *srcV;     // the rectangle's first sample in frame 0 of the batch
-    long long strideY, strideUV;
-    int pitchY, pitchUV;
+    long long strideY, strideUV;           // bytes between frames
+    int pitchY, pitchUV;                   // bytes between rows
     uint8_t *dstY, *dstU, *dstV;           // the first free slot of the store
-    int w, h, wUV, hUV;
-    int vbY, vbC;                          // bytes one lane moves in a luma / chroma row (16, 4 or 1)
-    int vrowY, vrowC;                      // w / vbY, wUV / vbC
+    int rowY, h, rowC, hUV;                // row lengths in bytes (w * es, wUV * es)
+    int vbY, vbC;                          // bytes one lane moves in a luma / chroma row (16, 4 or es)
+    int vrowY, vrowC;                      // rowY / vbY, rowC / vbC
     int vecsY, vecsC;                      // vrowY * h, vrowC * hUV
 };
 
@@ -541,6 +542,7 @@ __device__ __forceinline__ void keep_vec(uint8_t* d, const uint8_t* s, int vb)
 {
     if (vb == 16) *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(s);
     else if (vb == 4) *reinterpret_cast<uint32_t*>(d) = *reinterpret_cast<const uint32_t*>(s);
+    else if (vb == 2) *reinterpret_cast<uint16_t*>(d) = *reinterpret_cast<const uint16_t*>(s);
     else *d = *s;
 }
 
@@ -554,37 +556,42 @@ void scan_keep_kernel(ScanKeepArgs a, const int* __restrict__ keep, long long to
         const long long frame = keep[slot];
         if (v < a.vecsY) {
             const int y = v / a.vrowY, x = (v - y * a.vrowY) * a.vbY;
-            keep_vec(a.dstY + ((long long)slot * a.h + y) * a.w + x, a.srcY + frame * a.strideY + (long long)y * a.pitchY + x, a.vbY);
+            keep_vec(a.dstY + ((long long)slot * a.h + y) * a.rowY + x, a.srcY + frame * a.strideY + (long long)y * a.pitchY + x, a.vbY);
         } else {
             v -= a.vecsY;
             const bool second = v >= a.vecsC;
             if (second) v -= a.vecsC;
             const int y = v / a.vrowC, x = (v - y * a.vrowC) * a.vbC;
-            keep_vec((second ? a.dstV : a.dstU) + ((long long)slot * a.hUV + y) * a.wUV + x,
+            keep_vec((second ? a.dstV : a.dstU) + ((long long)slot * a.hUV + y) * a.rowC + x,
                      (second ? a.srcV : a.srcU) + frame * a.strideUV + (long long)y * a.pitchUV + x, a.vbC);
         }
     }
 }
 
-hipError_t launch_scan_keep(hipStream_t st, const PlaneBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
+hipError_t launch_scan_keep(hipStream_t st, int es, const PlaneBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
                             long long first_slot)
 {
     if (nkeep <= 0 || r.w <= 0 || r.h <= 0) return hipSuccess;
+    if (es != 1 && es != 2) return hipErrorInvalidValue;
     ScanKeepArgs a;
-    a.srcY = (const uint8_t*)b.Y + (long long)r.imgy * b.pitchY + r.imgx;
-    a.srcU = (const uint8_t*)b.U + (long long)r.cy * b.pitchUV + r.cx;
-    a.srcV = (const uint8_t*)b.V + (long long)r.cy * b.pitchUV + r.cx;
-    a.strideY = b.strideY; a.strideUV = b.strideUV; a.pitchY = b.pitchY; a.pitchUV = b.pitchUV;
-    a.dstY = (uint8_t*)store.Y + first_slot * r.w * r.h;
-    a.dstU = (uint8_t*)store.U + first_slot * r.wUV * r.hUV;
-    a.dstV = (uint8_t*)store.V + first_slot * r.wUV * r.hUV;
-    a.w = r.w; a.h = r.h; a.wUV = r.wUV; a.hUV = r.hUV;
-    // a slot's rows start at multiples of the row width from the store's base, so the width covers the destination's alignment too
-    auto width = [](uintptr_t v) { return v % 16 == 0 ? 16 : v % 4 == 0 ? 4 : 1; };
-    a.vbY = width((uintptr_t)a.srcY | (uintptr_t)store.Y | (uintptr_t)b.strideY | (uintptr_t)b.pitchY | (uintptr_t)r.w);
-    a.vbC = width((uintptr_t)a.srcU | (uintptr_t)a.srcV | (uintptr_t)store.U | (uintptr_t)store.V | (uintptr_t)b.strideUV | (uintptr_t)b.pitchUV |
-                  (uintptr_t)r.wUV);
-    a.vrowY = r.w / a.vbY; a.vrowC = r.wUV / a.vbC;
+    // (the batch's strides and pitches are in samples; everything below is in bytes)
+    a.strideY = b.strideY * es; a.strideUV = b.strideUV * es;
+    const long long pitchY = (long long)b.pitchY * es, pitchUV = (long long)b.pitchUV * es;
+    if (pitchY > INT_MAX || pitchUV > INT_MAX) return hipErrorInvalidValue;
+    a.pitchY = (int)pitchY; a.pitchUV = (int)pitchUV;
+    a.srcY = (const uint8_t*)b.Y + (long long)r.imgy * pitchY + (long long)r.imgx * es;
+    a.srcU = (const uint8_t*)b.U + (long long)r.cy * pitchUV + (long long)r.cx * es;
+    a.srcV = (const uint8_t*)b.V + (long long)r.cy * pitchUV + (long long)r.cx * es;
+    a.rowY = r.w * es; a.h = r.h; a.rowC = r.wUV * es; a.hUV = r.hUV;
+    a.dstY = (uint8_t*)store.Y + first_slot * a.rowY * r.h;
+    a.dstU = (uint8_t*)store.U + first_slot * a.rowC * r.hUV;
+    a.dstV = (uint8_t*)store.V + first_slot * a.rowC * r.hUV;
+    // a slot's rows start at multiples of the row length from the store's base, so the row length covers the destination's alignment too
+    auto width = [es](uintptr_t v) { return v % 16 == 0 ? 16 : v % 4 == 0 ? 4 : es; };
+    a.vbY = width((uintptr_t)a.srcY | (uintptr_t)store.Y | (uintptr_t)a.strideY | (uintptr_t)a.pitchY | (uintptr_t)a.rowY);
+    a.vbC = width((uintptr_t)a.srcU | (uintptr_t)a.srcV | (uintptr_t)store.U | (uintptr_t)store.V | (uintptr_t)a.strideUV | (uintptr_t)a.pitchUV |
+                  (uintptr_t)a.rowC);
+    a.vrowY = a.rowY / a.vbY; a.vrowC = a.rowC / a.vbC;
     a.vecsY = a.vrowY * r.h; a.vecsC = a.vrowC * r.hUV;
     const long long total = (long long)(a.vecsY + 2 * a.vecsC) * nkeep;
     if (total <= 0) return hipSuccess;

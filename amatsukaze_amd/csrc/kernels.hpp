@@ -47,9 +47,10 @@ hipError_t launch_scan_border(hipStream_t st, int bits, const PlaneBatch& b, con
 // daccepted[i] = {frame, bgY, bgU, bgV}; dacc: 3 int64 per sample of the rectangle, added to
 hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, const int4* daccepted, int naccepted,
                                   unsigned long long* dacc);
-// the rectangle r of frames dkeep[0 .. nkeep) of an 8-bit batch (batch-local indices) into slots first_slot .. of a tight store:
-// Y [slot][h][w], U / V [slot][hUV][wUV].  One launch; none when nkeep <= 0
-hipError_t launch_scan_keep(hipStream_t st, const PlaneBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
+// the rectangle r of frames dkeep[0 .. nkeep) of a batch of es-byte samples (batch-local indices) into slots first_slot .. of a tight
+// store: Y [slot][h][w], U / V [slot][hUV][wUV] samples.  Plane bases (batch and store) are multiples of es.  One launch; none when
+// nkeep <= 0
+hipError_t launch_scan_keep(hipStream_t st, int es, const PlaneBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
                             long long first_slot);
 
 // ---- ingest_kernels.hip ----

@@ -152,14 +152,15 @@ def framestats_sharded(fs, Y, first: int, num_frames: int, coll: TorchCollective
 
 def scan_logo_sharded(ctx, clip_local, serviceid, dstpath, imgx, imgy, w, h, thy, numMaxFrames, coll: TorchCollectives, cb=None):
     """ScanLogo (LogoScan.hpp:1083-1098) over a stream whose frames are sharded by contiguous range: clip_local holds this
-    rank's frames.  Rank 0 writes dstpath; returns True/False like the reference's export."""
+    rank's frames (clip_local.bits deep, the same on every rank).  Rank 0 writes dstpath; returns True/False like the reference's export."""
     from .api import _p
     cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
-    ok = ctx.lib.amtgpu_scanlogo_sharded(ctx.h, coll.ref(), _p(clip_local.Y), _p(clip_local.U), _p(clip_local.V), clip_local.strideY,
-                                         clip_local.strideUV, clip_local.pitchY, clip_local.pitchUV, clip_local.width, clip_local.height,
-                                         clip_local.num_frames, serviceid, str(dstpath).encode() if dstpath else None, imgx, imgy, w, h,
-                                         thy, numMaxFrames, cbf)
-    return bool(ok)
+    planes = (ctx.h, coll.ref(), _p(clip_local.Y), _p(clip_local.U), _p(clip_local.V), clip_local.strideY, clip_local.strideUV, clip_local.pitchY,
+              clip_local.pitchUV, clip_local.width, clip_local.height)
+    rest = (clip_local.num_frames, serviceid, str(dstpath).encode() if dstpath else None, imgx, imgy, w, h, thy, numMaxFrames, cbf)
+    if clip_local.bits == 8:
+        return bool(ctx.lib.amtgpu_scanlogo_sharded(*planes, *rest))
+    return bool(ctx.lib.amtgpu_scanlogo_sharded_bits(*planes, clip_local.bits, *rest))
 
 
 def scan_logo_stream_finish_sharded(stream, serviceid, dstpath, coll: TorchCollectives, cb=None):
@@ -188,8 +189,11 @@ def scan_logo_auto_sharded(ctx, clip_local, serviceid, dstpath, thy, numMaxFrame
     cbf = binding.CB(cb) if cb else binding.CB(lambda p, a, b, c: 1)
     found = binding.LogoRect()
     p = logo_find_params(**params)
-    ok = ctx.lib.amtgpu_scanlogo_auto_sharded(ctx.h, coll.ref(), _p(clip_local.Y), _p(clip_local.U), _p(clip_local.V), clip_local.strideY,
-                                              clip_local.strideUV, clip_local.pitchY, clip_local.pitchUV, clip_local.width, clip_local.height,
-                                              clip_local.num_frames, serviceid, str(dstpath).encode() if dstpath else None, thy, numMaxFrames,
-                                              cbf, C.byref(p), C.byref(found))
+    planes = (ctx.h, coll.ref(), _p(clip_local.Y), _p(clip_local.U), _p(clip_local.V), clip_local.strideY, clip_local.strideUV, clip_local.pitchY,
+              clip_local.pitchUV, clip_local.width, clip_local.height)
+    rest = (clip_local.num_frames, serviceid, str(dstpath).encode() if dstpath else None, thy, numMaxFrames, cbf, C.byref(p), C.byref(found))
+    if clip_local.bits == 8:
+        ok = ctx.lib.amtgpu_scanlogo_auto_sharded(*planes, *rest)
+    else:
+        ok = ctx.lib.amtgpu_scanlogo_auto_sharded_bits(*planes, clip_local.bits, *rest)
     return bool(ok), (LogoCandidate._of(found) if found.w > 0 else None)

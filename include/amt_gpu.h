@@ -39,7 +39,8 @@ extern "C" {
                                    * 5 (later additions): AMTGPU_ANALYZE_LINEAR_MONITORED, amtgpu_analyze_set_monitor,
                                    *    amtgpu_analyze_monitor_stats; automatic logo detection (amtgpu_logofind_*,
                                    *    amtgpu_scanlogo_auto, _auto_sharded, _file_auto); the streamed ScanLogo session
-                                   *    (amtgpu_scanlogo_stream_*) */
+                                   *    (amtgpu_scanlogo_stream_*); ScanLogo for 9..12-bit clips (amtgpu_scanlogo_bits, _sharded_bits,
+                                   *    _stream_create_bits, _auto_bits, _auto_sharded_bits; the 'AMTH' raw clip file) */
 #define AMTGPU_NUM_FADE 11            /* LogoAnalyzeFrame p/t/b[11]  (LogoScan.hpp:1100-1103) */
 #define AMTGPU_ANALYZE_FLOATS 33      /* floats per source frame in an analysis record */
 
@@ -381,11 +382,24 @@ int  amtgpu_scanlogo(AmtGpuContext* ctx, const void* dY, const void* dU, const v
                      int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh,
                      int nframes, int serviceid, const char* dstpath, int imgx, int imgy, int w, int h,
                      int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb);
+/* The same for a clip `bits` deep.  8: amtgpu_scanlogo itself, identical bytes.  9..12: uint16 little-endian containers (strides in
+ * bytes, pitches in elements), ScanLogo (:917-1079) stated with pixel_t = uint16_t and maxv = (1 << bits) - 1 wherever the 8-bit path
+ * writes 255 (Normalize, EvaluateLogo, DeintY), as AMTAnalyzeLogo (:1130) and AMTEraseLogo (:1349) state it; an extension the
+ * reference cannot pin beyond its template text (its scan is 8-bit because of its work-file codec, :813).  DESIGN.md section 9.
+ * thy is compared unscaled, in container units: a GUI's 12 at 8 bits is 48 at 10 bits.  The .lgd is depth-agnostic (coefficients
+ * normalised by maxv).  Refused with a message: bits outside 8..12, thy >= 1 << bits when bits > 8, an odd byte stride or a plane
+ * base that is not a multiple of 2 when bits > 8.  The _bits variants below follow the same rules. */
+int  amtgpu_scanlogo_bits(AmtGpuContext* ctx, const void* dY, const void* dU, const void* dV,
+                          int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int bits,
+                          int nframes, int serviceid, const char* dstpath, int imgx, int imgy, int w, int h,
+                          int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb);
 
 /* The reference's exported ScanLogo with its own argument list (LogoScan.hpp:1083-1098; AmatsukazeNatives.cs:391-393):
  * (ctx, srcpath, serviceid, workfile, dstpath, imgx, imgy, w, h, thy, numMaxFrames, cb) -> 1 ok / 0 fail + amtgpu_last_error.
  * srcpath is a raw 8-bit 4:2:0 clip (int32 'AMTR', width, height, frames, then tight Y,U,V per frame) instead of a transport stream
- * (demux / decode are out of scope); frames stream through the pinned ring, accepted rectangles stay in HBM; workfile is unused. */
+ * (demux / decode are out of scope), or a raw 9..12-bit one: little-endian int32 {'AMTH' = 0x48544D41, width, height, frames, bits}, then
+ * tight Y,U,V per frame as little-endian uint16 (the depth comes from the file; bits 8 or above 12 in an 'AMTH' header is refused).
+ * Frames stream through the pinned ring, accepted rectangles stay in HBM; workfile is unused. */
 int  amtgpu_scanlogo_file(AmtGpuContext* ctx, const char* srcpath, int serviceid, const char* workfile, const char* dstpath,
                           int imgx, int imgy, int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb);
 /* the same with the reference's string type: NUL-terminated UTF-16 paths (P/Invoke CharSet.Unicode keeps working) */
@@ -394,8 +408,9 @@ int  amtgpu_scanlogo_fileW(AmtGpuContext* ctx, const uint16_t* srcpath, int serv
 
 /* ---- ScanLogo as a streaming session: the same logo generation for a host that decodes (an FFmpeg loop, an AviSynth clip, a pipe)
  *      and cannot hold the clip in HBM.  create with the rectangle, feed device batches in stream order as they arrive, finish to get
- *      the .lgd -- byte-identical to amtgpu_scanlogo over the same frames.  8-bit 4:2:0 like ScanLogo itself (LogoScan.hpp:813).  What
- *      the session keeps in HBM is the rectangle of every kept frame (w*h*3/2 bytes each; the reference's work file, :899-903): the
+ *      the .lgd -- byte-identical to amtgpu_scanlogo over the same frames.  4:2:0; 8-bit like the reference's ScanLogo (LogoScan.hpp:813),
+ *      or 9..12-bit through amtgpu_scanlogo_stream_create_bits.  What
+ *      the session keeps in HBM is the rectangle of every kept frame (w*h*3/2 samples each; the reference's work file, :899-903): the
  *      store starts at min(numMaxFrames, 256) frames and doubles, so numMaxFrames may be "no limit" (1 << 30).
  *      amtgpu_scanlogo_file is a client of it. ---- */
 typedef struct AmtGpuScanLogoStream AmtGpuScanLogoStream;
@@ -403,6 +418,10 @@ typedef struct AmtGpuScanLogoStream AmtGpuScanLogoStream;
  * numMaxFrames < 0 counts as 0 */
 AmtGpuScanLogoStream* amtgpu_scanlogo_stream_create(AmtGpuContext* ctx, int imgw, int imgh, int imgx, int imgy, int w, int h,
                                                     int thy, int numMaxFrames);
+/* the same for frames `bits` deep (8..12, as amtgpu_scanlogo_bits; a bad depth or thy >= 1 << bits above 8 bits is refused here).  The
+ * session knows its depth: feed, feed_rect, status and both finishes are the ones below, with uint16 planes when bits > 8 */
+AmtGpuScanLogoStream* amtgpu_scanlogo_stream_create_bits(AmtGpuContext* ctx, int imgw, int imgh, int bits, int imgx, int imgy, int w, int h,
+                                                         int thy, int numMaxFrames);
 void amtgpu_scanlogo_stream_destroy(AmtGpuScanLogoStream* s);
 /* the next nframes frames of the stream, full frames on the device (strides in bytes, pitches in elements).  Valid frames (AddFrame's
  * border verdict, :604-653) are kept in stream order until numMaxFrames are kept (:885); the frame that fills the quota may sit in
@@ -451,6 +470,11 @@ int  amtgpu_scanlogo_sharded(AmtGpuContext* ctx, const AmtGpuCollectives* coll, 
                              int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh,
                              int nframes_local, int serviceid, const char* dstpath, int imgx, int imgy, int w, int h,
                              int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb);
+/* the same for a clip `bits` deep (8..12, the same on every rank), as amtgpu_scanlogo_bits */
+int  amtgpu_scanlogo_sharded_bits(AmtGpuContext* ctx, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,
+                                  int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int bits,
+                                  int nframes_local, int serviceid, const char* dstpath, int imgx, int imgy, int w, int h,
+                                  int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb);
 
 /* The streamed ScanLogo session (amtgpu_scanlogo_stream_create above) frame-sharded: every rank has fed its own contiguous range of
  * the stream into its own session, rank 0 the first frames, each keeping at most numMaxFrames of its own.  An all-gather of the kept counts cuts every rank's store to its share
@@ -556,18 +580,26 @@ int  amtgpu_logofind_candidates_host(const int64_t* sums, int width, int height,
 /* frame-sharded detection: every rank has added its own frames; one allreduce_sum_i64 over the 2*W*H + 1 values (the frame count rides
  * along) leaves identical sums on every rank.  Synchronises. */
 int  amtgpu_logofind_allreduce(AmtGpuLogoFind* lf, const AmtGpuCollectives* coll);
-/* ScanLogo without a rectangle: detection over all nframes frames (8-bit, as ScanLogo is), then amtgpu_scanlogo with the best
+/* ScanLogo without a rectangle: detection over all nframes frames (8-bit; _auto_bits below for 9..12), then amtgpu_scanlogo with the best
  * candidate, which *found receives (may be NULL).  No candidate: returns 0 with "no logo found", *found zeroed, no file written. */
 int  amtgpu_scanlogo_auto(AmtGpuContext* ctx, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
                           int pitchY, int pitchUV, int imgw, int imgh, int nframes, int serviceid, const char* dstpath, int thy,
                           int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found);
+/* the same for a clip `bits` deep (8..12): the detection runs at that depth, then amtgpu_scanlogo_bits */
+int  amtgpu_scanlogo_auto_bits(AmtGpuContext* ctx, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
+                               int pitchY, int pitchUV, int imgw, int imgh, int bits, int nframes, int serviceid, const char* dstpath, int thy,
+                               int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found);
 /* the same over frame-sharded ranks: each adds its own frames, the sums are all-reduced (every rank finds the same rectangle), then
  * amtgpu_scanlogo_sharded.  Rank 0 writes dstpath. */
 int  amtgpu_scanlogo_auto_sharded(AmtGpuContext* ctx, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,
                                   int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int nframes_local,
                                   int serviceid, const char* dstpath, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb,
                                   const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found);
-/* amtgpu_scanlogo_file without a rectangle: the raw 'AMTR' clip is read twice -- detection over the Y planes of every frame (through
+int  amtgpu_scanlogo_auto_sharded_bits(AmtGpuContext* ctx, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,
+                                       int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int bits,
+                                       int nframes_local, int serviceid, const char* dstpath, int thy, int numMaxFrames,
+                                       AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found);
+/* amtgpu_scanlogo_file without a rectangle: the raw clip ('AMTR', or 'AMTH' for 9..12 bits) is read twice -- detection over the Y planes of every frame (through
  * the pinned upload path), then amtgpu_scanlogo_file with the best candidate */
 int  amtgpu_scanlogo_file_auto(AmtGpuContext* ctx, const char* srcpath, int serviceid, const char* workfile, const char* dstpath, int thy,
                                int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb, const AmtGpuLogoFindParams* params, AmtGpuLogoRect* found);
