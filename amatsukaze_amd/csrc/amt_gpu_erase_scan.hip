@@ -7,36 +7,13 @@
 #include <cstring>
 #include <fstream>
 #include <memory>
+#include <numeric>
 #include <sstream>
 
 #include "api_common.hpp"
 #include "logo_fit.hpp"
 
 using namespace amt;
-
-// The ABI's description of a batch (byte strides) as the kernels take it (strides in samples): the one place that divides.
-static PlaneBatch plane_batch(int bits, const void* Y, const void* U, const void* V, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV)
-{
-    const int es = bits <= 8 ? 1 : 2;
-    if (strideY % es || strideUV % es) throw std::runtime_error("frame stride not a multiple of the sample size");
-    return PlaneBatch{Y, U, V, strideY / es, strideUV / es, pitchY, pitchUV};
-}
-
-// What every ScanLogo entry point checks before it touches a plane: the depth (8: bytes; 9..12: 16-bit little-endian containers, the
-// range LogoColor::Add's int products hold), thy against the border histogram, and strides / plane bases against the sample size.
-static int scan_sample_size(int bits, int thy)
-{
-    if (bits < 8 || bits > 12) throw std::runtime_error("[ScanLogo] bits must be 8..12");
-    if (bits > 8 && thy >= (1 << bits)) throw std::runtime_error("[ScanLogo] thy must be below 1 << bits for a clip of more than 8 bits");
-    return bits <= 8 ? 1 : 2;
-}
-static PlaneBatch scan_plane_batch(int bits, const void* Y, const void* U, const void* V, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV)
-{
-    const int es = bits <= 8 ? 1 : 2;
-    if (strideY % es || strideUV % es) throw std::runtime_error("[ScanLogo] odd byte stride for 16-bit samples");
-    if ((uintptr_t)Y % es || (uintptr_t)U % es || (uintptr_t)V % es) throw std::runtime_error("[ScanLogo] plane base not aligned to the sample size");
-    return PlaneBatch{Y, U, V, strideY / es, strideUV / es, pitchY, pitchUV};
-}
 
 // ---------------------------------------------------------------------------------------------
 // AMTEraseLogo
@@ -426,41 +403,30 @@ AmtGpuLogo* amtgpu_logoscan_get_logo(AmtGpuLogoScan* s, int maxv, int clean, int
     return l;
 }
 
-// LogoAnalyzer::ScanLogo (LogoScan.hpp:1058-1079): initial logo from every flat-bordered frame (stop at
-// numMaxFrames), then twice: evaluate 20 fades per kept frame, re-accumulate only frames whose best fade
-// index is > 8, regress again with clean-up; save.
-//
-// coll != nullptr: this rank holds one contiguous shard of the stream.  What is global in the reference's three
-// sequential rounds is (a) which valid frames fall inside the numMaxFrames quota ("first N in stream order", :885) and
-// (b) the accumulators each regression reads -- both integers, so an all-gather of valid counts and an all-reduce of
-// int64 sums reproduce the single-GPU result exactly; the regression then runs redundantly on every rank.
 } // extern "C" (helpers)
 
 namespace {
 
-// A sharded run must never leave ranks behind in a collective: a rank whose own work threw (a HIP error, a bad argument, a
-// cancelled callback) keeps entering every exchange with neutral data, its status rides along, and ALL ranks throw right after
-// the exchange in which the status becomes known.
-struct ShardGuard {
-    const AmtGpuCollectives* coll = nullptr;     // nullptr / world 1: plain exceptions
-    std::string error;                           // this rank's failure, if any
-    int64_t cancel = 0;
-    bool sharded() const { return coll && coll->world > 1; }
-    template <typename F> void attempt(F&& fn)
-    {
-        if (!sharded()) { fn(); return; }
-        if (!error.empty()) return;
-        try { fn(); } catch (const std::exception& e) { error = e.what(); } catch (...) { error = "unknown error"; }
-    }
-    int64_t status() const { return (cancel ? 1 : 0) + (error.empty() ? 0 : (int64_t)1 << 32); }
-    // `summed` = sum over ranks of status(): everyone leaves together
-    void agree(int64_t summed) const
-    {
-        if (!error.empty()) throw std::runtime_error(error);
-        if (summed >> 32) throw std::runtime_error("another rank failed; the sharded run was abandoned on every rank");
-        if (summed & 0xFFFFFFFF) throw std::runtime_error("Cancel requested");
-    }
+// The frames round 0 kept, which every later step reads again: where they lie and what their border said.
+struct KeptFrames {
+    PlaneBatch planes{};              // the resident clip, or a session's store
+    ScanRect r{};                     // the scan rectangle in those planes
+    int bits = 8;
+    std::vector<int> index;           // frame index in `planes` of every kept frame
+    std::vector<int4> verdict;        // its {1, bgY, bgU, bgV}
+    int count() const { return (int)index.size(); }
+    // 3 * samples of the rectangle: the size of a scan's sums
+    size_t npx() const { return (size_t)3 * ((size_t)r.w * r.h + 2 * (size_t)r.wUV * r.hUV); }
 };
+// what the finished logo's header says about the frame and the rectangle's place in it
+struct LogoHeader { int imgw, imgh, imgx, imgy; };
+
+// logoscan_add from known verdicts: the kept frames that `use` admits (all of them without one), no border kernel
+using ::logoscan_add;
+int logoscan_add(AmtGpuLogoScan* s, const KeptFrames& k, const uint8_t* use = nullptr)
+{
+    return k.count() ? logoscan_add(s, k.planes, k.r, k.bits, k.count(), k.count(), use, nullptr, k.index.data(), k.verdict.data()) : 0;
+}
 
 // sums of all ranks -> every rank (px sums, plane sums, frame count, and the ranks' status riding along); npx = 3 * samples of the
 // scan rectangle (known even when this rank has no scan object to contribute)
@@ -476,28 +442,28 @@ void reduce_scan(AmtGpuLogoScan* s, ShardGuard& sg, size_t npx)
         for (int k = 0; k < 6; ++k) buf[npx + k] = s->sums.plane[k];
         buf[npx + 6] = s->sums.nframes;
     });
-    if (!sg.error.empty()) std::fill(buf.begin(), buf.end(), 0);
-    buf[npx + 7] = sg.status();
-    if (!sg.coll->allreduce_sum_i64(sg.coll->user, buf.data(), (int64_t)buf.size())) throw std::runtime_error("allreduce_sum_i64 failed");
-    sg.agree(buf[npx + 7]);
+    sg.allreduce(buf);
     if (!amtgpu_logoscan_set_sums(s, buf.data(), buf.data() + npx, (int)buf[npx + 6])) throw std::runtime_error(s->ctx->err);
 }
 
-// ReMakeLogo twice (LogoScan.hpp:923-1036, 1065-1071) over a device-resident clip `bits` deep (maxv wherever the 8-bit text says 255,
-// as AMTAnalyzeLogo does, :1130): `kept` lists the frames round 0 accepted (indices into the clip), whose rectangle is r; the finished
-// logo's header gets (himgw, himgh, himgx, himgy).
-template <typename Progress>
-std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtGpuLogoScan* scan0, const PlaneBatch& clip, int bits, const ScanRect& r, int thy,
-                                          const std::vector<int>& kept, const std::vector<int4>& keptVerdict, int himgw, int himgh, int himgx,
-                                          int himgy, Progress&& progress)
+// round 0's sums of a rank's share of the kept frames, summed over the ranks
+void accumulate_kept(ShardGuard& sg, AmtGpuLogoScan* scan, const KeptFrames& kept)
 {
-    const size_t npx = (size_t)3 * ((size_t)r.w * r.h + 2 * (size_t)r.wUV * r.hUV);
-    const int maxv = (1 << bits) - 1;
-    const int numFrames = (int)kept.size();
-    std::unique_ptr<AmtGpuLogo> logo(amtgpu_logoscan_get_logo(scan0, maxv, 0, himgw, himgh, himgx, himgy));
+    sg.attempt([&] { logoscan_add(scan, kept); });
+    reduce_scan(scan, sg, kept.npx());
+}
+
+// ReMakeLogo twice (LogoScan.hpp:923-1036, 1065-1071) over the kept frames (maxv wherever the 8-bit text says 255, as AMTAnalyzeLogo
+// does, :1130), starting from round 0's sums in scan0
+std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtGpuLogoScan* scan0, const KeptFrames& kept, const LogoHeader& hd, int thy)
+{
+    const ScanRect& r = kept.r;
+    const int maxv = (1 << kept.bits) - 1;
+    const int numFrames = kept.count();
+    std::unique_ptr<AmtGpuLogo> logo(amtgpu_logoscan_get_logo(scan0, maxv, 0, hd.imgw, hd.imgh, hd.imgx, hd.imgy));
     if (!logo) throw std::runtime_error(c->err);
     DevBuf<int> dMap;
-    if (numFrames) dMap.upload(kept, c->stream);
+    if (numFrames) dMap.upload(kept.index, c->stream);
     std::vector<float> fades(20);
     for (int fi = 0; fi < 20; ++fi) fades[fi] = 0.1f * fi;
     DevBuf<float> dEval((size_t)std::max(1, numFrames) * 20);
@@ -515,7 +481,7 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
             EvalEngine eng(c, std::move(specs), fades, true, 20, "logo_eval_fused_kernel.remake");
             std::vector<uint8_t> use(numFrames, 0);
             if (numFrames) {
-                eng.run(clip.Y, clip.strideY * (bits <= 8 ? 1 : 2), clip.pitchY, bits, numFrames, dEval.get(), dMap.get());       // (stride in bytes)
+                eng.run(kept.planes.Y, luma_stride_bytes(kept.planes, sample_bytes(kept.bits)), kept.planes.pitchY, kept.bits, numFrames, dEval.get(), dMap.get());
                 download_via_pinned(c, hEval.data(), dEval.get(), hEval.size() * sizeof(float));
             }
             for (int i = 0; i < numFrames; ++i) {
@@ -525,80 +491,24 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
                     if (hEval[(size_t)i * 20 + fi] < best) { best = hEval[(size_t)i * 20 + fi]; bestIdx = fi; }
                 use[i] = bestIdx > 8;                       // logo clearly present in this frame
             }
-            progress(50.0f + 25.0f * round + 12.5f, numFrames, numFrames, numFrames);
+            sg.progress(50.0f + 25.0f * round + 12.5f, numFrames, numFrames, numFrames);
             rescan.reset(logoscan_new(c, r.w, r.h, 1, 1, thy));
-            if (numFrames) logoscan_add(rescan.get(), clip, r, bits, numFrames, numFrames, use.data(), nullptr, kept.data(), keptVerdict.data());
+            logoscan_add(rescan.get(), kept, use.data());
         });
-        reduce_scan(rescan.get(), sg, npx);
-        logo.reset(amtgpu_logoscan_get_logo(rescan.get(), maxv, 1, himgw, himgh, himgx, himgy));
+        reduce_scan(rescan.get(), sg, kept.npx());
+        logo.reset(amtgpu_logoscan_get_logo(rescan.get(), maxv, 1, hd.imgw, hd.imgh, hd.imgx, hd.imgy));
         if (!logo) throw std::runtime_error(c->err);
     }
     return logo;
 }
 
-int scanlogo_impl(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
-                  int pitchY, int pitchUV, int imgw, int imgh, int bits, int nframes, int serviceid, const char* dstpath, const ScanRect& r, int thy,
-                  int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
+// what every ScanLogo ends with, once round 0's sums of the kept frames are in `scan` on every rank: the two rounds, and rank 0 saves
+void finish_logo(AmtGpuContext* c, ShardGuard& sg, AmtGpuLogoScan* scan, const KeptFrames& kept, const LogoHeader& hd, int thy, int serviceid,
+                 const char* dstpath)
 {
-    if (!c) return 0;
-    return guard(c, [&] {
-        const int es = scan_sample_size(bits, thy);          // (refused before anything is exchanged: the same on every rank)
-        PlaneBatch clip{};
-        const bool sharded = coll && coll->world > 1;
-        if (sharded && (!coll->allgather || !coll->allreduce_sum_i64 || coll->rank < 0 || coll->rank >= coll->world))
-            throw std::runtime_error("AmtGpuCollectives incomplete");
-        ShardGuard sg;
-        sg.coll = sharded ? coll : nullptr;
-        auto progress = [&](float p, int nread, int total, int ngather) {
-            if (cb && !cb(p, nread, total, ngather)) {
-                if (!sharded) throw std::runtime_error("Cancel requested");
-                sg.cancel = 1;                                  // the other ranks learn about it with the next exchange
-            }
-        };
-        const size_t npx = (size_t)3 * ((size_t)std::max(0, r.w) * std::max(0, r.h) + 2 * (size_t)(std::max(0, r.w) / 2) * (std::max(0, r.h) / 2));
-        std::unique_ptr<AmtGpuLogoScan> scan;
-        std::vector<int> kept;              // frame index (within this rank's frames) of every kept frame
-        std::vector<int4> keptVerdict;      // its {1,bgY,bgU,bgV}
-        const int chunk = 4096;
-        // round 0: the border verdicts of every frame in stream order.  One rank accepts frames as it goes and stops once numMaxFrames are
-        // kept; a shard accepts nothing yet (quota 0) and keeps every valid frame: which of them count is decided below
-        auto wanted = [&] { return sharded || (int)kept.size() < numMaxFrames; };
-        sg.attempt([&] {
-            if (r.imgx < 0 || r.imgy < 0 || r.imgx + r.w > imgw || r.imgy + r.h > imgh) throw std::runtime_error("scan rectangle outside the frame");
-            clip = scan_plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV);
-            scan.reset(logoscan_new(c, r.w, r.h, 1, 1, thy));
-            for (int f0 = 0; f0 < nframes && wanted(); f0 += chunk) {
-                const int n = std::min(chunk, nframes - f0);
-                logoscan_add(scan.get(), plane_batch_from(clip, f0, es), r, bits, n, sharded ? 0 : numMaxFrames - (int)kept.size(), nullptr, nullptr,
-                             nullptr, nullptr);
-                for (int i = 0; i < n; ++i)
-                    if (scan->lastVerdicts[i].x && wanted()) { kept.push_back(f0 + i); keptVerdict.push_back(scan->lastVerdicts[i]); }
-                progress(50.0f * (f0 + n) / std::max(1, nframes), f0 + n, 0, (int)kept.size());
-            }
-        });
-        if (sharded) {
-            // this rank's share of "the first numMaxFrames valid frames of the stream" (and how every rank is doing) ...
-            std::vector<int64_t> counts((size_t)coll->world * 2, 0);
-            const int64_t mine[2] = {sg.error.empty() ? (int64_t)kept.size() : 0, sg.status()};
-            if (!coll->allgather(coll->user, mine, counts.data(), sizeof mine)) throw std::runtime_error("allgather failed");
-            int64_t before = 0, summed = 0;
-            for (int k = 0; k < coll->world; ++k) summed += counts[2 * k + 1];
-            for (int k = 0; k < coll->rank; ++k) before += counts[2 * k];
-            sg.agree(summed);
-            const int quota = (int)std::max<int64_t>(0, std::min<int64_t>(mine[0], (int64_t)numMaxFrames - before));
-            kept.resize(quota);
-            keptVerdict.resize(quota);
-            // ... accumulated locally, summed over ranks
-            sg.attempt([&] {
-                if (quota) logoscan_add(scan.get(), clip, r, bits, quota, quota, nullptr, nullptr, kept.data(), keptVerdict.data());
-            });
-            reduce_scan(scan.get(), sg, npx);
-        }
-        const int numFrames = (int)kept.size();
-        std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, scan.get(), clip, bits, r, thy, kept, keptVerdict, imgw, imgh, r.imgx, r.imgy, progress);
-        progress(1, numFrames, numFrames, numFrames);
-        if (dstpath && (!sharded || coll->rank == 0)) save_lgd(logo->planes, dstpath, "No Name", serviceid);
-    });
+    const std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, scan, kept, hd, thy);
+    sg.progress(1, kept.count(), kept.count(), kept.count());
+    if (dstpath && sg.writes()) save_lgd(logo->planes, dstpath, "No Name", serviceid);
 }
 
 } // namespace
@@ -638,7 +548,7 @@ namespace {
 
 AmtGpuScanLogoStream* stream_new(AmtGpuContext* c, int imgw, int imgh, int bits, int imgx, int imgy, int w, int h, int thy, int numMaxFrames)
 {
-    const int es = scan_sample_size(bits, thy);
+    const int es = scan_sample_bytes(bits, thy);
     if (imgx < 0 || imgy < 0 || w > imgw - imgx || h > imgh - imgy) throw std::runtime_error("scan rectangle outside the frame");
     std::unique_ptr<AmtGpuScanLogoStream> s(new AmtGpuScanLogoStream);
     s->ctx = c;
@@ -685,7 +595,7 @@ void stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const 
     if (!dY || !dU || !dV) throw std::runtime_error("[ScanLogo] null plane");
     const ScanRect r = rect_only ? scan_rect(0, 0, s->rect.w, s->rect.h) : s->rect;
     if (pitchY < r.imgx + r.w || pitchUV < r.cx + r.wUV) throw std::runtime_error("[ScanLogo] pitch smaller than the rectangle's rows");
-    const PlaneBatch b = scan_plane_batch(s->bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV);
+    const PlaneBatch b = plane_batch(s->bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, PlaneRules::ScanLogo);
     AmtGpuContext* c = s->ctx;
     // verdicts alone (quota 0): which valid frames count is decided here, in stream order
     logoscan_add(s->scan.get(), b, r, s->bits, nframes, 0, nullptr, nullptr, nullptr, nullptr);
@@ -719,52 +629,24 @@ void stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const 
 }
 
 // MakeInitialLogo's regression and the two ReMakeLogo rounds over the store (LogoScan.hpp:845-848, 1065-1071); sharded: this rank's share of
-// the quota first, as scanlogo_impl hands it out
+// the quota first, as the resident driver hands it out
 void stream_finish(AmtGpuScanLogoStream* s, const AmtGpuCollectives* coll, int serviceid, const char* dstpath, AMTGPU_LOGO_ANALYZE_CB cb)
 {
-    AmtGpuContext* c = s->ctx;
-    const bool sharded = coll && coll->world > 1;
-    const bool usable = !sharded || (coll->allgather && coll->allreduce_sum_i64 && coll->rank >= 0 && coll->rank < coll->world);
-    ShardGuard sg;
-    sg.coll = sharded && usable ? coll : nullptr;
-    auto progress = [&](float p, int nread, int total, int ngather) {
-        if (cb && !cb(p, nread, total, ngather)) {
-            if (!sharded) throw std::runtime_error("Cancel requested");
-            sg.cancel = 1;
-        }
-    };
+    const bool usable = !coll || coll->world <= 1 || (coll->allgather && coll->allreduce_sum_i64 && coll->rank >= 0 && coll->rank < coll->world);
+    ShardGuard sg(usable ? coll : nullptr, cb);
     // (a spent session on one rank of a sharded finish must not strand the others: its refusal rides along like any other failure)
     sg.attempt([&] { if (s->spent) throw std::runtime_error("[ScanLogo] the session has been finished"); });
     s->spent = true;
     if (!usable) throw std::runtime_error("AmtGpuCollectives incomplete");
-    if (!sharded && !dstpath) throw std::runtime_error("[ScanLogo] null destination path");
-    c->bind();
-    int n = sg.error.empty() ? s->nkept() : 0;
-    if (sharded) {
-        std::vector<int64_t> counts((size_t)coll->world * 2, 0);
-        const int64_t mine[2] = {n, sg.status()};
-        if (!coll->allgather(coll->user, mine, counts.data(), sizeof mine)) throw std::runtime_error("allgather failed");
-        int64_t before = 0, summed = 0;
-        for (int k = 0; k < coll->world; ++k) summed += counts[2 * k + 1];
-        for (int k = 0; k < coll->rank; ++k) before += counts[2 * k];
-        sg.agree(summed);
-        n = (int)std::max<int64_t>(0, std::min<int64_t>(n, (int64_t)s->numMaxFrames - before));
-    }
-    const ScanRect& fr = s->rect;
-    const ScanRect r = scan_rect(0, 0, fr.w, fr.h);
-    const size_t npx = (size_t)3 * ((size_t)r.w * r.h + 2 * (size_t)r.wUV * r.hUV);
-    const PlaneBatch crops{s->storeY.get(), s->storeU.get(), s->storeV.get(), (long long)r.w * r.h, (long long)r.wUV * r.hUV, r.w, r.wUV};
-    std::vector<int> kept(n);
-    for (int i = 0; i < n; ++i) kept[i] = i;
-    const std::vector<int4> verdicts(s->keptVerdict.begin(), s->keptVerdict.begin() + n);
-    sg.attempt([&] {
-        if (n) logoscan_add(s->scan.get(), crops, r, s->bits, n, n, nullptr, nullptr, kept.data(), verdicts.data());
-    });
-    reduce_scan(s->scan.get(), sg, npx);
-    std::unique_ptr<AmtGpuLogo> logo = remake_rounds(c, sg, s->scan.get(), crops, s->bits, r, s->thy, kept, verdicts, s->imgw, s->imgh, fr.imgx, fr.imgy,
-                                                     progress);
-    progress(1, n, n, n);
-    if (dstpath && (!sharded || coll->rank == 0)) save_lgd(logo->planes, dstpath, "No Name", serviceid);
+    if (!sg.sharded() && !dstpath) throw std::runtime_error("[ScanLogo] null destination path");
+    s->ctx->bind();
+    const int n = sg.quota_share(s->nkept(), s->numMaxFrames);
+    const ScanRect r = scan_rect(0, 0, s->rect.w, s->rect.h);
+    const PlaneBatch store{s->storeY.get(), s->storeU.get(), s->storeV.get(), (long long)r.w * r.h, (long long)r.wUV * r.hUV, r.w, r.wUV};
+    KeptFrames kept{store, r, s->bits, std::vector<int>(n), std::vector<int4>(s->keptVerdict.begin(), s->keptVerdict.begin() + n)};
+    std::iota(kept.index.begin(), kept.index.end(), 0);          // the store holds the kept frames alone, in order
+    accumulate_kept(sg, s->scan.get(), kept);
+    finish_logo(s->ctx, sg, s->scan.get(), kept, LogoHeader{s->imgw, s->imgh, s->rect.imgx, s->rect.imgy}, s->thy, serviceid, dstpath);
 }
 
 void stream_report(const AmtGpuScanLogoStream* s, int64_t* nread, int* nkept, int* done)
@@ -838,8 +720,8 @@ int amtgpu_scanlogo_bits(AmtGpuContext* c, const void* dY, const void* dU, const
                          int pitchY, int pitchUV, int imgw, int imgh, int bits, int nframes, int serviceid, const char* dstpath, int imgx,
                          int imgy, int w, int h, int thy, int numMaxFrames, AMTGPU_LOGO_ANALYZE_CB cb)
 {
-    return scanlogo_impl(c, nullptr, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, bits, nframes, serviceid, dstpath,
-                         scan_rect(imgx, imgy, w, h), thy, numMaxFrames, cb);
+    return amtgpu_scanlogo_sharded_bits(c, nullptr, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, bits, nframes, serviceid, dstpath, imgx,
+                                        imgy, w, h, thy, numMaxFrames, cb);
 }
 
 int amtgpu_scanlogo(AmtGpuContext* c, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
@@ -861,35 +743,13 @@ int amtgpu_scanlogo_file(AmtGpuContext* c, const char* srcpath, int serviceid, c
 {
     (void)workfile;
     return guard(c, [&] {
-        auto progress = [&](float p, int nread, int total, int ngather) {
-            if (cb && !cb(p, nread, total, ngather)) throw std::runtime_error("Cancel requested");
-        };
-        std::ifstream f(srcpath, std::ios::binary);
-        if (!f) throw std::runtime_error(std::string("failed to open file ") + srcpath);
-        const RawClipHeader hd = amt_read_raw_clip_header(f);
-        const int W = hd.width, H = hd.height, N = hd.frames, es = hd.bits <= 8 ? 1 : 2;
-        // (sizes in bytes)
-        const size_t ysz = (size_t)W * H * es, csz = (size_t)(W / 2) * (H / 2) * es, fsz = ysz + 2 * csz;
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>(1024, (256u << 20) / fsz));
-        c->bind();
-        std::unique_ptr<AmtGpuScanLogoStream> s(stream_new(c, W, H, hd.bits, imgx, imgy, w, h, thy, numMaxFrames));
-        DevBuf<uint8_t> dChunk(fsz * chunk);
-        std::vector<uint8_t> host(fsz * chunk), planar(fsz * chunk);
-        for (int f0 = 0; f0 < N && !s->done; f0 += chunk) {
-            const int n = std::min(chunk, N - f0);
-            f.read(reinterpret_cast<char*>(host.data()), (std::streamsize)(fsz * n));
-            if (!f) throw std::runtime_error("raw clip truncated");
-            // file order is frame-interleaved (Y,U,V per frame); the device batch is plane-major: Y[n], U[n], V[n]
-            for (int i = 0; i < n; ++i) {
-                std::memcpy(planar.data() + ysz * i, host.data() + fsz * i, ysz);
-                std::memcpy(planar.data() + ysz * n + csz * i, host.data() + fsz * i + ysz, csz);
-                std::memcpy(planar.data() + ysz * n + csz * n + csz * i, host.data() + fsz * i + ysz + csz, csz);
-            }
-            if (!amtgpu_frames_upload(c, dChunk.get(), planar.data(), fsz * n) || !amtgpu_frames_upload_wait(c)) throw std::runtime_error(c->err);
-            const uint8_t *dY = dChunk.get(), *dU = dY + ysz * n, *dV = dU + csz * n;
-            stream_feed(s.get(), dY, dU, dV, (int64_t)ysz, (int64_t)csz, W, W / 2, n, false);      // (strides in bytes, pitches in samples)
-            AMT_HIP(hipStreamSynchronize(c->stream));          // the chunk buffer is refilled by the next upload
-            progress(50.0f * (f0 + n) / std::max(1, N), f0 + n, 0, s->nkept());
+        ShardGuard one(nullptr, cb);
+        RawClipReader in(c, srcpath, false);
+        const int W = in.hd.width, N = in.hd.frames;
+        std::unique_ptr<AmtGpuScanLogoStream> s(stream_new(c, W, in.hd.height, in.hd.bits, imgx, imgy, w, h, thy, numMaxFrames));
+        while (!s->done && in.next()) {
+            stream_feed(s.get(), in.dY, in.dU, in.dV, (int64_t)in.ysz, (int64_t)in.csz, W, W / 2, in.n, false);      // (strides in bytes, pitches in samples)
+            one.progress(50.0f * in.nread / std::max(1, N), in.nread, 0, s->nkept());
         }
         stream_finish(s.get(), nullptr, serviceid, dstpath, cb);
     });
@@ -902,13 +762,58 @@ int amtgpu_scanlogo_fileW(AmtGpuContext* c, const uint16_t* srcpath, int service
     return amtgpu_scanlogo_file(c, src.c_str(), serviceid, work.c_str(), dst.c_str(), imgx, imgy, w, h, thy, numMaxFrames, cb);
 }
 
+// LogoAnalyzer::ScanLogo (LogoScan.hpp:1058-1079): initial logo from every flat-bordered frame (stop at
+// numMaxFrames), then twice: evaluate 20 fades per kept frame, re-accumulate only frames whose best fade
+// index is > 8, regress again with clean-up; save.
+//
+// coll != nullptr: this rank holds one contiguous shard of the stream.  What is global in the reference's three
+// sequential rounds is (a) which valid frames fall inside the numMaxFrames quota ("first N in stream order", :885) and
+// (b) the accumulators each regression reads -- both integers, so an all-gather of valid counts and an all-reduce of
+// int64 sums reproduce the single-GPU result exactly; the regression then runs redundantly on every rank.
+//
+// Every resident entry point ends here; coll == nullptr or world 1: the whole stream, one rank.
 int amtgpu_scanlogo_sharded_bits(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,
                                  int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int imgw, int imgh, int bits, int nframes_local,
                                  int serviceid, const char* dstpath, int imgx, int imgy, int w, int h, int thy, int numMaxFrames,
                                  AMTGPU_LOGO_ANALYZE_CB cb)
 {
-    return scanlogo_impl(c, coll, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, imgw, imgh, bits, nframes_local, serviceid, dstpath,
-                         scan_rect(imgx, imgy, w, h), thy, numMaxFrames, cb);
+    if (!c) return 0;
+    return guard(c, [&] {
+        const int es = scan_sample_bytes(bits, thy);         // (refused before anything is exchanged: the same on every rank)
+        ShardGuard sg(coll, cb);
+        if (sg.sharded() && (!coll->allgather || !coll->allreduce_sum_i64 || coll->rank < 0 || coll->rank >= coll->world))
+            throw std::runtime_error("AmtGpuCollectives incomplete");
+        KeptFrames kept;                    // (indices within this rank's frames)
+        kept.r = scan_rect(imgx, imgy, w, h);
+        kept.bits = bits;
+        const ScanRect& r = kept.r;
+        std::unique_ptr<AmtGpuLogoScan> scan;
+        const int chunk = 4096;
+        // round 0: the border verdicts of every frame in stream order.  One rank accepts frames as it goes and stops once numMaxFrames are
+        // kept; a shard accepts nothing yet (quota 0) and keeps every valid frame: which of them count is decided below
+        auto wanted = [&] { return sg.sharded() || kept.count() < numMaxFrames; };
+        sg.attempt([&] {
+            if (r.imgx < 0 || r.imgy < 0 || r.imgx + r.w > imgw || r.imgy + r.h > imgh) throw std::runtime_error("scan rectangle outside the frame");
+            kept.planes = plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, PlaneRules::ScanLogo);
+            scan.reset(logoscan_new(c, r.w, r.h, 1, 1, thy));
+            for (int f0 = 0; f0 < nframes_local && wanted(); f0 += chunk) {
+                const int n = std::min(chunk, nframes_local - f0);
+                logoscan_add(scan.get(), plane_batch_from(kept.planes, f0, es), r, bits, n, sg.sharded() ? 0 : numMaxFrames - kept.count(), nullptr,
+                             nullptr, nullptr, nullptr);
+                for (int i = 0; i < n; ++i)
+                    if (scan->lastVerdicts[i].x && wanted()) { kept.index.push_back(f0 + i); kept.verdict.push_back(scan->lastVerdicts[i]); }
+                sg.progress(50.0f * (f0 + n) / std::max(1, nframes_local), f0 + n, 0, kept.count());
+            }
+        });
+        if (sg.sharded()) {
+            // this rank's share of the quota (and how every rank is doing), accumulated locally, summed over ranks
+            const int quota = sg.quota_share(kept.count(), numMaxFrames);
+            kept.index.resize(quota);
+            kept.verdict.resize(quota);
+            accumulate_kept(sg, scan.get(), kept);
+        }
+        finish_logo(c, sg, scan.get(), kept, LogoHeader{imgw, imgh, r.imgx, r.imgy}, thy, serviceid, dstpath);
+    });
 }
 
 int amtgpu_scanlogo_sharded(AmtGpuContext* c, const AmtGpuCollectives* coll, const void* dY, const void* dU, const void* dV,

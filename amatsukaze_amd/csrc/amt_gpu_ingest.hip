@@ -22,7 +22,7 @@ int amtgpu_weave_fields_batch(AmtGpuContext* c, const void* dsrcY, const void* d
         if (width <= 0 || height <= 0 || (width & 1) || (height & 3)) throw std::runtime_error("[AMTSource] width must be even and height a multiple of 4 (interlaced 4:2:0)");
         if (bits < 8 || bits > 16) throw std::runtime_error("[AMTSource] unsupported bit depth");
         if (!dsrcY || !dsrcU || (!nv12 && !dsrcV) || !dY || !dU || !dV) throw std::runtime_error("[AMTSource] null plane");
-        const int es = bits <= 8 ? 1 : 2;
+        const int es = sample_bytes(bits);
         const int wUV = width >> 1, hUV = height >> 1;
         if (src_pitchY < width || src_pitchUV < (nv12 ? width : wUV) || pitchY < width || pitchUV < wUV)
             throw std::runtime_error("[AMTSource] pitch smaller than the row");

@@ -4,7 +4,6 @@
 #include "../../include/amt_gpu.h"
 
 #include <cstring>
-#include <fstream>
 #include <memory>
 #include <string>
 #include <vector>
@@ -83,40 +82,23 @@ AmtGpuLogoRect best_rect(AmtGpuLogoFind* lf, const AmtGpuLogoFindParams* params)
     return r;
 }
 
-// the sums of all ranks on every rank; a rank that failed before the exchange still enters it (with a status word) so that nobody blocks
-void logofind_reduce(AmtGpuLogoFind* lf, const AmtGpuCollectives* coll, std::string local_error)
+// the sums of all ranks on every rank; a rank that failed before the exchange still enters it (its status rides along) so that nobody blocks
+void logofind_reduce(AmtGpuLogoFind* lf, ShardGuard& sg)
 {
-    if (!coll || coll->world <= 1) {
-        if (!local_error.empty()) throw std::runtime_error(local_error);
-        return;
-    }
-    if (!coll->allreduce_sum_i64 || coll->rank < 0 || coll->rank >= coll->world) throw std::runtime_error("AmtGpuCollectives incomplete");
+    if (!sg.sharded()) return;
+    if (!sg.coll->allreduce_sum_i64 || sg.coll->rank < 0 || sg.coll->rank >= sg.coll->world) throw std::runtime_error("AmtGpuCollectives incomplete");
     const size_t n = 2 * npx(lf);
     std::vector<int64_t> buf(n + 2, 0);
-    if (local_error.empty()) {
-        try {
-            std::vector<int64_t> h = logofind_pull(lf);
-            std::copy(h.begin(), h.end(), buf.begin());
-            buf[n] = lf->nframes;
-        } catch (const std::exception& e) { local_error = e.what(); std::fill(buf.begin(), buf.end(), 0); }
-    }
-    buf[n + 1] = local_error.empty() ? 0 : 1;
-    if (!coll->allreduce_sum_i64(coll->user, buf.data(), (int64_t)buf.size())) throw std::runtime_error("allreduce_sum_i64 failed");
-    if (!local_error.empty()) throw std::runtime_error(local_error);
-    if (buf[n + 1]) throw std::runtime_error("another rank failed; the sharded logo detection was abandoned on every rank");
+    sg.attempt([&] {
+        const std::vector<int64_t> h = logofind_pull(lf);
+        std::copy(h.begin(), h.end(), buf.begin());
+        buf[n] = lf->nframes;
+    });
+    sg.allreduce(buf);
     logofind_push(lf, buf.data(), buf[n]);
 }
 
 void zero_found(AmtGpuLogoRect* found) { if (found) std::memset(found, 0, sizeof *found); }
-
-// what amtgpu_scanlogo_*_bits refuses about the planes, before the detection reads them
-void check_scan_planes(int bits, const void* dY, int64_t strideY)
-{
-    if (bits < 8 || bits > 12) throw std::runtime_error("[ScanLogo] bits must be 8..12");
-    const int es = bits <= 8 ? 1 : 2;
-    if (strideY % es) throw std::runtime_error("[ScanLogo] odd byte stride for 16-bit samples");
-    if ((uintptr_t)dY % es) throw std::runtime_error("[ScanLogo] plane base not aligned to the sample size");
-}
 
 } // namespace
 
@@ -176,7 +158,8 @@ int amtgpu_logofind_allreduce(AmtGpuLogoFind* lf, const AmtGpuCollectives* coll)
     if (!lf) return 0;
     return guard(lf->ctx, [&] {
         if (!coll) throw std::runtime_error("[LogoFind] null collectives");
-        logofind_reduce(lf, coll, std::string());
+        ShardGuard sg(coll, nullptr, "logo detection");
+        logofind_reduce(lf, sg);
     });
 }
 
@@ -188,7 +171,8 @@ int amtgpu_scanlogo_auto_bits(AmtGpuContext* c, const void* dY, const void* dU, 
     zero_found(found);
     AmtGpuLogoRect r{};
     const int ok = guard(c, [&] {
-        check_scan_planes(bits, dY, strideY);
+        // what amtgpu_scanlogo_bits refuses about the planes, as far as the detection reads them: the luma plane alone
+        (void)plane_batch(bits, dY, nullptr, nullptr, strideY, 0, pitchY, 0, PlaneRules::ScanLogo);
         std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, bits));
         logofind_add(lf.get(), dY, strideY, pitchY, nframes);
         r = best_rect(lf.get(), params);
@@ -216,14 +200,14 @@ int amtgpu_scanlogo_auto_sharded_bits(AmtGpuContext* c, const AmtGpuCollectives*
     zero_found(found);
     AmtGpuLogoRect r{};
     const int ok = guard(c, [&] {
-        if (bits < 8 || bits > 12) throw std::runtime_error("[ScanLogo] bits must be 8..12");       // (the same on every rank)
+        (void)scan_sample_bytes(bits);       // (the depth is the same on every rank)
         std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, bits));
-        std::string err;
-        try {
-            check_scan_planes(bits, dY, strideY);
+        ShardGuard sg(coll, nullptr, "logo detection");
+        sg.attempt([&] {
+            (void)plane_batch(bits, dY, nullptr, nullptr, strideY, 0, pitchY, 0, PlaneRules::ScanLogo);
             logofind_add(lf.get(), dY, strideY, pitchY, nframes_local);
-        } catch (const std::exception& e) { err = e.what(); }
-        logofind_reduce(lf.get(), coll, err);
+        });
+        logofind_reduce(lf.get(), sg);
         r = best_rect(lf.get(), params);       // identical sums on every rank: the same answer (or the same "no logo found") everywhere
     });
     if (!ok) return 0;
@@ -249,26 +233,12 @@ int amtgpu_scanlogo_file_auto(AmtGpuContext* c, const char* srcpath, int service
     zero_found(found);
     AmtGpuLogoRect r{};
     const int ok = guard(c, [&] {
-        if (!srcpath) throw std::runtime_error("null source path");
-        std::ifstream f(srcpath, std::ios::binary);
-        if (!f) throw std::runtime_error(std::string("failed to open file ") + srcpath);
-        const RawClipHeader hd = amt_read_raw_clip_header(f);
-        const int W = hd.width, H = hd.height, N = hd.frames, es = hd.bits <= 8 ? 1 : 2;
-        // (sizes in bytes)
-        const size_t ysz = (size_t)W * H * es, csz = (size_t)(W / 2) * (H / 2) * es, fsz = ysz + 2 * csz;
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>(1024, (256u << 20) / fsz));
-        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, W, H, hd.bits));
-        DevBuf<uint8_t> dChunk(ysz * chunk);
-        std::vector<uint8_t> host(fsz * chunk), planes(ysz * chunk);
-        for (int f0 = 0; f0 < N; f0 += chunk) {
-            const int n = std::min(chunk, N - f0);
-            f.read(reinterpret_cast<char*>(host.data()), (std::streamsize)(fsz * n));
-            if (!f) throw std::runtime_error("raw clip truncated");
-            for (int i = 0; i < n; ++i) std::memcpy(planes.data() + ysz * i, host.data() + fsz * i, ysz);
-            if (!amtgpu_frames_upload(c, dChunk.get(), planes.data(), ysz * n) || !amtgpu_frames_upload_wait(c)) throw std::runtime_error(c->err);
-            logofind_add(lf.get(), dChunk.get(), (int64_t)ysz, W, n);
-            AMT_HIP(hipStreamSynchronize(c->stream));          // the chunk buffer is refilled by the next upload
-            if (cb && !cb(0.f, f0 + n, N, 0)) throw std::runtime_error("Cancel requested");
+        ShardGuard one(nullptr, cb);
+        RawClipReader in(c, srcpath, true);
+        std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, in.hd.width, in.hd.height, in.hd.bits));
+        while (in.next()) {
+            logofind_add(lf.get(), in.dY, (int64_t)in.ysz, in.hd.width, in.n);
+            one.progress(0.f, in.nread, in.hd.frames, 0);
         }
         r = best_rect(lf.get(), params);
     });

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstring>
 #include <exception>
+#include <fstream>
 #include <istream>
 #include <mutex>
 #include <stdexcept>
@@ -67,6 +68,33 @@ inline RawClipHeader amt_read_raw_clip_header(std::istream& f)
     return RawClipHeader{hdr[1], hdr[2], hdr[3], hdr[4]};
 }
 
+// Bytes per sample of a clip `bits` deep: bytes up to 8 bits, 16-bit little-endian containers above.
+inline int sample_bytes(int bits) { return bits <= 8 ? 1 : 2; }
+
+// The depths ScanLogo takes (8: bytes; 9..12: the range LogoColor::Add's int products hold) and thy against the border histogram, which
+// has 1 << bits bins; returns the bytes per sample.  Refused before a plane is touched or anything is exchanged.
+inline int scan_sample_bytes(int bits, int thy = 0)
+{
+    if (bits < 8 || bits > 12) throw std::runtime_error("[ScanLogo] bits must be 8..12");
+    if (bits > 8 && thy >= (1 << bits)) throw std::runtime_error("[ScanLogo] thy must be below 1 << bits for a clip of more than 8 bits");
+    return sample_bytes(bits);
+}
+
+// The ABI's description of a batch (byte strides) as the kernels take it (strides in samples): the one place that divides.  ScanLogo's
+// entry points also refuse the depth and a plane base off the sample size, in their own words; a caller that reads the luma plane alone
+// passes null chroma planes and a zero chroma stride.
+enum class PlaneRules { Plain, ScanLogo };
+inline amt::PlaneBatch plane_batch(int bits, const void* Y, const void* U, const void* V, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV,
+                                   PlaneRules rules = PlaneRules::Plain)
+{
+    const bool scan = rules == PlaneRules::ScanLogo;
+    const int es = scan ? scan_sample_bytes(bits) : sample_bytes(bits);
+    if (strideY % es || strideUV % es)
+        throw std::runtime_error(scan ? "[ScanLogo] odd byte stride for 16-bit samples" : "frame stride not a multiple of the sample size");
+    if (scan && ((uintptr_t)Y % es || (uintptr_t)U % es || (uintptr_t)V % es)) throw std::runtime_error("[ScanLogo] plane base not aligned to the sample size");
+    return amt::PlaneBatch{Y, U, V, strideY / es, strideUV / es, pitchY, pitchUV};
+}
+
 // run f(); on any exception keep the message on the context and return 0 (no exceptions cross the ABI)
 template <typename F> inline int guard(AmtGpuContext* c, F&& f, const char* caller = __builtin_FUNCTION())
 {
@@ -124,3 +152,110 @@ inline bool allgather_records(const AmtGpuCollectives* coll, const void* local, 
     }
     return true;
 }
+
+// A sharded run must never leave ranks behind in a collective: a rank whose own work threw (a HIP error, a bad argument, a
+// cancelled callback) keeps entering every exchange with neutral data, its status rides along, and ALL ranks throw right after
+// the exchange in which the status becomes known.  One rank alone (coll null or world 1): plain exceptions.
+struct ShardGuard {
+    const AmtGpuCollectives* coll;               // nullptr: not sharded
+    AMTGPU_LOGO_ANALYZE_CB cb;
+    const char* what;                            // what the ranks abandon together, for the message
+    std::string error;                           // this rank's failure, if any
+    int64_t cancel = 0;
+    ShardGuard(const AmtGpuCollectives* c, AMTGPU_LOGO_ANALYZE_CB cb_, const char* what_ = "run") : coll(c && c->world > 1 ? c : nullptr), cb(cb_), what(what_) {}
+    bool sharded() const { return coll != nullptr; }
+    bool writes() const { return !coll || coll->rank == 0; }       // rank 0 saves the result
+    template <typename F> void attempt(F&& fn)
+    {
+        if (!sharded()) { fn(); return; }
+        if (!error.empty()) return;
+        try { fn(); } catch (const std::exception& e) { error = e.what(); } catch (...) { error = "unknown error"; }
+    }
+    void progress(float p, int nread, int total, int ngather)
+    {
+        if (!cb || cb(p, nread, total, ngather)) return;
+        if (!sharded()) throw std::runtime_error("Cancel requested");
+        cancel = 1;                              // the other ranks learn about it with the next exchange
+    }
+    int64_t status() const { return (cancel ? 1 : 0) + (error.empty() ? 0 : (int64_t)1 << 32); }
+    // `summed` = sum over ranks of status(): everyone leaves together
+    void agree(int64_t summed) const
+    {
+        if (!error.empty()) throw std::runtime_error(error);
+        if (summed >> 32) throw std::runtime_error(std::string("another rank failed; the sharded ") + what + " was abandoned on every rank");
+        if (summed & 0xFFFFFFFF) throw std::runtime_error("Cancel requested");
+    }
+    // buf summed over the ranks in place; its last element is the guard's: the status word (a failed rank contributes zeros)
+    void allreduce(std::vector<int64_t>& buf) const
+    {
+        if (!error.empty()) std::fill(buf.begin(), buf.end(), 0);
+        buf.back() = status();
+        if (!coll->allreduce_sum_i64(coll->user, buf.data(), (int64_t)buf.size())) throw std::runtime_error("allreduce_sum_i64 failed");
+        agree(buf.back());
+    }
+    // This rank's share of "the first numMaxFrames valid frames of the stream" (LogoScan.hpp:885; rank 0 holds the first frames), of which
+    // it found nvalid: {count, status} of every rank is gathered, and the ranks before this one are served first.
+    int quota_share(int nvalid, int numMaxFrames) const
+    {
+        if (!sharded()) return nvalid;
+        std::vector<int64_t> counts((size_t)coll->world * 2, 0);
+        const int64_t mine[2] = {error.empty() ? nvalid : 0, status()};
+        if (!coll->allgather(coll->user, mine, counts.data(), sizeof mine)) throw std::runtime_error("allgather failed");
+        int64_t before = 0, summed = 0;
+        for (int k = 0; k < coll->world; ++k) summed += counts[2 * k + 1];
+        for (int k = 0; k < coll->rank; ++k) before += counts[2 * k];
+        agree(summed);
+        return (int)std::max<int64_t>(0, std::min<int64_t>(mine[0], (int64_t)numMaxFrames - before));
+    }
+};
+
+// A raw clip file (RawClipHeader above), read in chunks of min(1024, 256 MiB / frame bytes) frames: next() de-interleaves a chunk (file
+// order is Y, U, V per frame; the device batch is plane-major, Y[n] U[n] V[n], or Y[n] alone with luma_only) and uploads it through the
+// pinned ring.  The one device buffer is refilled by every chunk: next() first waits for the stream, on which the caller's work on the
+// previous chunk runs.
+struct RawClipReader {
+    AmtGpuContext* ctx;
+    std::ifstream file;
+    RawClipHeader hd{};
+    bool luma_only;
+    size_t ysz = 0, csz = 0, fsz = 0;            // bytes of a frame's luma plane, of one chroma plane, of the frame: the batch's byte strides
+    int chunk = 1, n = 0, nread = 0;             // frames per chunk, in the current one, handed out so far
+    amt::DevBuf<uint8_t> dChunk;
+    std::vector<uint8_t> host, planar;
+    const uint8_t *dY = nullptr, *dU = nullptr, *dV = nullptr;       // the current chunk (dU, dV null with luma_only)
+    RawClipReader(AmtGpuContext* c, const char* srcpath, bool luma_only_) : ctx(c), luma_only(luma_only_)
+    {
+        if (!srcpath) throw std::runtime_error("null source path");
+        file.open(srcpath, std::ios::binary);
+        if (!file) throw std::runtime_error(std::string("failed to open file ") + srcpath);
+        hd = amt_read_raw_clip_header(file);
+        const int es = sample_bytes(hd.bits);
+        ysz = (size_t)hd.width * hd.height * es; csz = (size_t)(hd.width / 2) * (hd.height / 2) * es; fsz = ysz + 2 * csz;
+        chunk = (int)std::max<size_t>(1, std::min<size_t>(1024, (256u << 20) / fsz));
+        c->bind();
+        dChunk.alloc((luma_only ? ysz : fsz) * chunk);
+        host.resize(fsz * chunk);
+        planar.resize((luma_only ? ysz : fsz) * chunk);
+    }
+    // the next chunk's planes on the device; false: the clip has been read
+    bool next()
+    {
+        if (n) AMT_HIP(hipStreamSynchronize(ctx->stream));          // the chunk buffer is refilled by the upload below
+        if (nread >= hd.frames) return false;
+        n = std::min(chunk, hd.frames - nread);
+        file.read(reinterpret_cast<char*>(host.data()), (std::streamsize)(fsz * n));
+        if (!file) throw std::runtime_error("raw clip truncated");
+        for (int i = 0; i < n; ++i) {
+            std::memcpy(planar.data() + ysz * i, host.data() + fsz * i, ysz);
+            if (luma_only) continue;
+            std::memcpy(planar.data() + ysz * n + csz * i, host.data() + fsz * i + ysz, csz);
+            std::memcpy(planar.data() + ysz * n + csz * n + csz * i, host.data() + fsz * i + ysz + csz, csz);
+        }
+        if (!amtgpu_frames_upload(ctx, dChunk.get(), planar.data(), (luma_only ? ysz : fsz) * n) || !amtgpu_frames_upload_wait(ctx)) throw std::runtime_error(ctx->err);
+        dY = dChunk.get();
+        dU = luma_only ? nullptr : dY + ysz * n;
+        dV = luma_only ? nullptr : dU + csz * n;
+        nread += n;
+        return true;
+    }
+};

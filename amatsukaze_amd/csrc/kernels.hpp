@@ -23,6 +23,8 @@ inline PlaneBatch plane_batch_from(const PlaneBatch& b, long long frames, int es
     auto at = [&](const void* p, long long stride) { return (const void*)((const uint8_t*)p + frames * stride * es); };
     return PlaneBatch{at(b.Y, b.strideY), at(b.U, b.strideUV), at(b.V, b.strideUV), b.strideY, b.strideUV, b.pitchY, b.pitchUV};
 }
+// and back to what the ABI and the evaluation engine count in: bytes between luma frames
+inline long long luma_stride_bytes(const PlaneBatch& b, int es) { return b.strideY * es; }
 // the planes Delogo writes: laid out like the PlaneBatch it reads (the same planes for the in-place call)
 struct PlanesOut { void *Y, *U, *V; };
 // a 4:2:0 rectangle of a frame: origin and size in the luma plane, and in the chroma planes

@@ -250,6 +250,18 @@ def test_errors(gpu, tmp_path):
     ctx.synchronize()
 
 
+def test_file_entry_points_refuse_a_null_source_path(gpu, tmp_path):
+    """both raw-clip entry points read through one reader, which refuses a missing path in its own words before it opens anything"""
+    from amatsukaze_amd import binding
+    lib, ctx, yes = gpu["ctx"].lib, gpu["ctx"], binding.CB(lambda *a: 1)
+    dst = tmp_path / "never.lgd"
+    assert lib.amtgpu_scanlogo_file(ctx.h, None, SID, None, str(dst).encode(), X, Y0, LW, LH, THY, QUOTA, yes) == 0
+    assert last_error(gpu) == b"null source path"
+    assert lib.amtgpu_scanlogo_file_auto(ctx.h, None, SID, None, str(dst).encode(), THY, QUOTA, yes, None, None) == 0
+    assert last_error(gpu) == b"null source path"
+    assert not dst.exists()
+
+
 def test_streamed_auto_equals_resident_auto(gpu, tmp_path):
     """the clip of test_gpu_logofind.py, detection and session both fed in batches of 50"""
     from amatsukaze_amd import DeviceClip, ScanLogoAuto, ScanLogoAutoStream

@@ -1,6 +1,7 @@
 """The streamed ScanLogo session, frame-sharded: two spawned ranks (one device and gloo when the box has a single GPU, as in
 test_gpu_sharded.py) each feed their half of the stream into a session of their own; the sharded finish must write the .lgd of ONE
-session fed the whole stream -- with a quota that ends inside rank 1's range, and with one rank 0 fills alone (rank 1's share is 0)."""
+session fed the whole stream -- with a quota that ends inside rank 1's range, and with one rank 0 fills alone (rank 1's share is 0).
+A cancelled callback or a spent session on rank 1 ends the finish on BOTH ranks, and the next sharded finish is whole again."""
 import os
 import socket
 
@@ -38,16 +39,32 @@ def _worker(rank, world, port, tmpdir, q):
         a, b = SH.shard_range(N, rank, world)
         loc = DeviceClip(*(torch.from_numpy(np.ascontiguousarray(clip[k][a:b])).to(dev) for k in "YUV"), width=W, height=H)
         res = {"rank": rank, "frames": b - a}
-        for quota in QUOTAS:
+        half = (b - a) // 2
+
+        def fed(quota):
             st = ScanLogoStream(ctx, W, H, X, Y0, LW, LH, THY, quota)
-            half = (b - a) // 2
             st.feed(DeviceClip(loc.Y[:half], loc.U[:half], loc.V[:half], W, H))
-            nkept, _ = st.feed(DeviceClip(loc.Y[half:], loc.U[half:], loc.V[half:], W, H))
-            dst = os.path.join(tmpdir, f"sharded_{quota}.lgd")
-            ok = SH.scan_logo_stream_finish_sharded(st, SID, dst if rank == 0 else None, coll)
-            res[f"ok_{quota}"] = bool(ok) and coll.error is None
-            res[f"kept_{quota}"] = nkept
-            res[f"msg_{quota}"] = ctx.lib.amtgpu_last_error(ctx.h).decode(errors="replace")
+            return st, st.feed(DeviceClip(loc.Y[half:], loc.U[half:], loc.V[half:], W, H))[0]
+
+        def finish(st, tag, cb=None):
+            dst = os.path.join(tmpdir, f"sharded_{tag}.lgd")
+            ok = SH.scan_logo_stream_finish_sharded(st, SID, dst if rank == 0 else None, coll, cb)
+            res[f"ok_{tag}"] = bool(ok) and coll.error is None
+            res[f"msg_{tag}"] = ctx.lib.amtgpu_last_error(ctx.h).decode(errors="replace")
+
+        for quota in QUOTAS:
+            st, res[f"kept_{quota}"] = fed(quota)
+            finish(st, quota)
+        # ---- rank 1's callback cancels on its first call: the cancellation rides along the next exchange and BOTH ranks leave with it ----
+        calls = []
+        finish(fed(25)[0], "cancel", lambda p, nread, total, ngather: (calls.append(p), rank == 0 or len(calls) > 1)[1])
+        finish(fed(25)[0], "after_cancel")         # nobody was left out of step: the next sharded finish is whole
+        # ---- rank 1 hands in a session it has already finished: its refusal rides along like any other failure ----
+        st = fed(25)[0]
+        if rank == 1:
+            st.finish(SID, os.path.join(tmpdir, "rank1_alone.lgd"))          # (spent whether or not its frames alone make a logo)
+        finish(st, "spent")
+        finish(fed(25)[0], "after_spent")
         q.put(res)
     except Exception as e:        # noqa: BLE001 -- reported to the parent, never retried
         import traceback
@@ -95,5 +112,11 @@ def test_sharded_finish_equals_one_session(tmp_path):
             assert x[f"ok_{quota}"], x[f"msg_{quota}"]
     for quota in QUOTAS:
         assert (tmp_path / f"sharded_{quota}.lgd").read_bytes() == want[quota], quota
+    for x in res:
+        assert not x["ok_cancel"] and x["msg_cancel"] == "Cancel requested", x
+        assert not x["ok_spent"] and x["ok_after_cancel"] and x["ok_after_spent"], x
+    assert "has been finished" in res[1]["msg_spent"] and "another rank failed" in res[0]["msg_spent"], res
+    for tag in ("after_cancel", "after_spent"):
+        assert (tmp_path / f"sharded_{tag}.lgd").read_bytes() == want[25], tag
     assert res[1]["kept_10"] == 10              # rank 1 kept frames of its own; its share of the quota rank 0 filled is 0
     assert all(p.exitcode == 0 for p in procs)

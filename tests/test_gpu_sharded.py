@@ -58,10 +58,17 @@ def _worker(rank, world, port, tmpdir, q):
                 res[f"scanlogo_{tag}"] = (bool(ok) == bool(ok1)) and (not ok1 or open(d1, "rb").read() == open(d2, "rb").read())
 
         # ---- a failure on ONE rank (here: rank 1's rectangle lies outside the frame) must end the run on BOTH, not strand rank 0 in a
-        #      collective: the status rides along every exchange (ShardGuard, amt_gpu_erase_scan.hip) ----
+        #      collective: the status rides along every exchange (ShardGuard, api_common.hpp) ----
         bad = SH.scan_logo_sharded(ctx, loc, 1041, None, X if rank == 0 else W, Y0, LW, LH, 12, 25, coll)
         res["failsafe_scanlogo_failed"] = not bad
         res["failsafe_scanlogo_msg"] = ctx.lib.amtgpu_last_error(ctx.h).decode(errors="replace")
+
+        # ---- the same for a cancellation: rank 1's callback returns 0 on its first call, BOTH ranks end with "Cancel requested" ----
+        calls = []
+        gone = SH.scan_logo_sharded(ctx, loc, 1041, None, X, Y0, LW, LH, 12, 25, coll,
+                                    cb=lambda p, nread, total, ngather: (calls.append(p), rank == 0 or len(calls) > 1)[1])
+        res["cancel_scanlogo_failed"] = not gone
+        res["cancel_scanlogo_msg"] = ctx.lib.amtgpu_last_error(ctx.h).decode(errors="replace")
 
         # ---- LogoFrame all-frames scan, sharded (ragged: 39 frames -> 20 + 19) + all-gather on every rank ----
         Y, U, V = G.frames(g, pitch_pad=32)
@@ -154,6 +161,8 @@ def test_sharded_hip_path_world2(tmp_path):
     # one rank's failure ends the sharded call on every rank, each with a message that says whose it was
     assert r0["failsafe_scanlogo_failed"] and r1["failsafe_scanlogo_failed"]
     assert "another rank failed" in r0["failsafe_scanlogo_msg"] and "outside the frame" in r1["failsafe_scanlogo_msg"]
+    for r in res:
+        assert r["cancel_scanlogo_failed"] and r["cancel_scanlogo_msg"] == "Cancel requested", r
     assert r0["failsafe_allgather_failed"] and r1["failsafe_allgather_failed"]
     assert "another rank failed" in r0["failsafe_allgather_msg"] and "outside the clip" in r1["failsafe_allgather_msg"]
     for r in res:
