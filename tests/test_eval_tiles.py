@@ -3,11 +3,11 @@ every mask pixel's 5x5 window must read the samples CalcCorrelation5x5 reads (Lo
 import os
 import subprocess
 
-import numpy as np
 import pytest
 
 import amtlib
 import amt_synth as S
+from logo_sets import REPLAY_CASES, REPLAY_IDS, logo_data, oracle_eval_logo, write_mask_positions
 
 ROOT = amtlib.ROOT
 
@@ -33,14 +33,23 @@ def test_bench_logo_masks(replay_bin, tmp_path, kind, ratio):
     hl = O.make_logo(data, 256, 128, 1440, 1080, 1120, 64)
     d = O.lib.orc_logo_deint(hl) if kind == "deint" else O.lib.orc_logo_field(hl, 0)
     O.lib.orc_logo_create_mask(d, ratio, 0)
-    info = O.logo_info(d)
-    w, h = int(info[0]), int(info[1])
-    mask = O.logo_arrays(d)[1].reshape(h, w)
-    ys, xs = np.nonzero(mask[2:h - 2, 2:w - 2])
-    pos = ((ys + 2).astype(np.uint32) << 16) | (xs + 2).astype(np.uint32)
     fn = tmp_path / "pos.bin"
-    with open(fn, "wb") as f:
-        np.array([len(pos), w, h], np.int32).tofile(f)
-        pos.astype(np.uint32).tofile(f)
+    write_mask_positions(O, d, fn)
+    r = subprocess.run([replay_bin, str(fn)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
+@pytest.mark.parametrize("entry,ratio", REPLAY_CASES, ids=REPLAY_IDS)
+def test_mixed_logo_masks(replay_bin, tmp_path, entry, ratio):
+    """the masks of every logo the mixed-list scans run (tests/logo_sets.py): widths that are no multiple of 4, a tall narrow and a
+    680-wide logo, the smallest logo the plans take and a sparse mask"""
+    O = amtlib.Oracle()
+    w, h, imgx, imgy = entry
+    d = oracle_eval_logo(O, O.make_logo(logo_data(entry), w, h, imgx + w, imgy + h, imgx, imgy), ratio)
+    fn = tmp_path / "pos.bin"
+    count, mw, mh = write_mask_positions(O, d, fn)
+    assert (mw, mh) == (w, h) and count > 0
+    if (w, h) == (6, 6):
+        assert count == 4                        # every pixel is in the mask; four have a window inside the logo
     r = subprocess.run([replay_bin, str(fn)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr

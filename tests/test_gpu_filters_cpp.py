@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import amt_synth as S
+import logo_sets as LS
 from amtlib import Oracle, _ptr
 
 pytestmark = pytest.mark.gpu
@@ -25,17 +26,36 @@ def build_exe():
 
 @pytest.mark.parametrize("bits", [8, 10])
 def test_cpp_filters_match_oracle(tmp_path, bits):
+    """the second logo of LogoFrame's list is a weaker logo on logo 1's rectangle: the rows and columns the layer uploads are that rectangle"""
+    data2, _, _ = S.make_logo(CFG["LW"], CFG["LH"], seed=0x10600002, strength=0.5)
+    run_filters_against_oracle(tmp_path, bits, data2, (CFG["LW"], CFG["LH"], CFG["IMGX"], CFG["IMGY"]))
+
+
+@pytest.mark.parametrize("bits", [8, 10])
+def test_cpp_filters_match_oracle_logos_apart(tmp_path, bits):
+    """The second logo is logo B of tests/logo_sets.py, 36 x 100 at (6, 120): the union LogoFrame::scanFrames uploads becomes rows
+    [18, 220) and columns [6, 320) -- a first column that is not 4-byte aligned at 8 bits (the gather upload and the row-ingest kernel
+    take their narrow lane width), logo 1 on the union's first rows, logo 2 on its last, both far narrower than what is resident, 43
+    frames in launches of 7.  Everything else (analysis, erase: logo 1) as in test_cpp_filters_match_oracle."""
+    w2, h2, x2, y2 = geo2 = LS.LOGO_B
+    assert (CFG["W"], CFG["H"]) == LS.SMALL_FRAME and (CFG["LW"], CFG["LH"], CFG["IMGX"], CFG["IMGY"]) == LS.LOGO_A
+    assert (min(CFG["IMGY"], y2), max(CFG["IMGY"] + CFG["LH"], y2 + h2)) == (18, 220)
+    assert (min(CFG["IMGX"], x2), max(CFG["IMGX"] + CFG["LW"], x2 + w2)) == (6, 320) and CFG["N"] % 7 == 1
+    run_filters_against_oracle(tmp_path, bits, LS.logo_data(geo2), geo2)
+
+
+def run_filters_against_oracle(tmp_path, bits, data2, geo2):
+    """data2, geo2 = (w, h, imgx, imgy): the second logo of LogoFrame's list"""
     exe = build_exe()
     cfg = CFG
     W, H, N = cfg["W"], cfg["H"], cfg["N"]
     data, alpha, alphaUV = S.make_logo(cfg["LW"], cfg["LH"])
-    data2, _, _ = S.make_logo(cfg["LW"], cfg["LH"], seed=0x10600002, strength=0.5)
     pY, pUV = W + 24, W // 2 + 12
     clip = S.make_clip_np(N, W, H, 0x5EED0007, alpha, alphaUV, cfg["IMGX"], cfg["IMGY"], bits=bits, period=cfg["period"], fade=cfg["fade"],
                           flat_every=cfg["flat"], pitchY=pY, pitchUV=pUV)
     orc = Oracle()
     lo = orc.make_logo(data, cfg["LW"], cfg["LH"], W, H, cfg["IMGX"], cfg["IMGY"])
-    lo2 = orc.make_logo(data2, cfg["LW"], cfg["LH"], W, H, cfg["IMGX"], cfg["IMGY"])
+    lo2 = orc.make_logo(data2, geo2[0], geo2[1], W, H, geo2[2], geo2[3])
     logo1, logo2 = str(tmp_path / "a.lgd"), str(tmp_path / "b.lgd")
     assert orc.lib.orc_logo_save(lo, logo1.encode(), b"A", 1) and orc.lib.orc_logo_save(lo2, logo2.encode(), b"B", 1)
     raw = tmp_path / "clip.raw"

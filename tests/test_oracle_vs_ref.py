@@ -158,6 +158,29 @@ def test_logoframe_scan_select_write(env):
     assert ev[on, 0, 0].mean() > 0.5 and np.abs(ev[on, 0, 1]).mean() < 0.2
 
 
+@pytest.mark.parametrize("ncand,logo_index", [(-1, 0), (2, 1)])
+def test_logoframe_mixed_list_with_a_missing_file(env, ncand, logo_index):
+    """Logos of different sizes and positions in one list (tests/logo_sets.py SMALL_MIXED: the clip's own logo, a tall narrow one at
+    an origin % 4 == 2, one of width % 4 == 2 on the frame's first row, one wider than 256 that ends on the last row, one in the
+    bottom-right corner) around a file that cannot be read: the oracle's records, selection and logoframe text are the reference's
+    bytes, so the oracle is a valid reference for the device scan of such lists."""
+    import logo_sets as LS
+    assert LS.SMALL_FRAME == (W, H) and LS.LOGO_A == (LW, LH, IMGX, IMGY)
+    built = LS.build(LS.SMALL_MIXED, LS.SMALL_FRAME, orc=env["orc"], lgd_dir=env["tmp"])
+    paths = [p.encode() for p in built.paths]
+    paths.insert(2, str(env["tmp"] / "missing.lgd").encode())
+    r, o = _logoframe_both(env, paths, ncand=ncand, logo_index=logo_index)
+    assert r[0].tobytes() == o[0].tobytes()
+    assert np.int32(r[1]).tobytes() == np.int32(o[1]).tobytes() and np.float32(r[2]).tobytes() == np.float32(o[2]).tobytes()
+    assert r[3] == o[3]
+    assert r[1] == 0                                       # the clip's own logo wins among all six and among the first two
+    ev = o[0].reshape(-1, 6, 2)
+    assert np.all(ev[:, 2, 0] == 0) and np.all(ev[:, 2, 1] == -1)         # the missing file (LogoScan.hpp:1551-1554)
+    for i in (0, 1, 3, 4, 5):
+        assert np.isfinite(ev[:, i]).all(), i
+        assert ev[:, i, 0].std() > 0 and ev[:, i, 1].std() > 0, i         # not constant over the frames
+
+
 def test_analyze_logo(env):
     orc, ref, clip = env["orc"], env["ref"], env["clip"]
     Y, U, V = clip["Y"], clip["U"], clip["V"]
