@@ -149,16 +149,66 @@ class DeviceClip:
         return int(self.U.stride(1))
 
 
-def weave_fields(ctx: "Context", srcY, srcU, srcV, dst: DeviceClip, top_index=None, bottom_index=None, nv12=False):
+@dataclass
+class DeviceSurfaces:
+    """Decoder surfaces in HBM (AmtGpuSurfaces): Y (N,H,pitchY) and, planar, U / V (N,H/2,pitchUV) torch tensors, or interleaved (NV12 /
+    P010) U = the UV plane (N,H/2,pitchUV >= width) with V None.  uint8 at 8 bits, int16 / uint16 containers above; msb: the sample sits
+    in the high bits of its container (P010 / P012) and is read as container >> (16 - bits)."""
+    Y: object
+    U: object
+    V: object = None
+    width: int = 0
+    height: int = 0
+    bits: int = 8
+    interleaved: bool = False
+    msb: bool = False
+
+    @property
+    def num_frames(self):
+        return int(self.Y.shape[0])
+
+    @property
+    def es(self):
+        return 1 if self.bits <= 8 else 2
+
+    def ref(self):
+        """the binding.Surfaces descriptor of these tensors (valid while they live)"""
+        for t in (self.Y, self.U, self.V):
+            if t is not None and t.element_size() != self.es:
+                raise AmtError(f"DeviceSurfaces: {self.es}-byte containers expected at {self.bits} bits, got {t.dtype}")
+        return binding.Surfaces(_p(self.Y), _p(self.U), _p(self.V) if self.V is not None else None, int(self.Y.stride(0)) * self.es,
+                                int(self.U.stride(0)) * self.es if self.U is not None else 0, int(self.Y.stride(1)),
+                                int(self.U.stride(1)) if self.U is not None else 0, self.bits, 1 if self.interleaved else 0, 1 if self.msb else 0, 0)
+
+
+def extract_rect(ctx: "Context", surfaces: DeviceSurfaces, x, y, w, h):
+    """The rectangle (x, y, w, h) of every surface as planar LSB planes (amtgpu_surfaces_extract_rect): (Y [n, h, w], U, V [n, h/2, w/2])
+    torch tensors of the surfaces' container type -- what ScanLogoStream.feed_rect and AMTEraseLogo.erase_rect take.  async"""
+    import torch
+    n = surfaces.num_frames
+    dt = surfaces.Y.dtype
+    Y = torch.empty((n, h, w), dtype=dt, device=surfaces.Y.device)
+    U = torch.empty((n, h // 2, w // 2), dtype=dt, device=surfaces.Y.device)
+    V = torch.empty_like(U)
+    es = surfaces.es
+    d = surfaces.ref()
+    ctx.check(ctx.lib.amtgpu_surfaces_extract_rect(ctx.h, C.byref(d), x, y, w, h, n, _p(Y), _p(U), _p(V), int(Y.stride(0)) * es,
+                                                   int(U.stride(0)) * es, int(Y.stride(1)), int(U.stride(1))), "extract_rect")
+    return Y, U, V
+
+
+def weave_fields(ctx: "Context", srcY, srcU, srcV, dst: DeviceClip, top_index=None, bottom_index=None, nv12=False, msb=False):
     """AMTSource::MakeFrame -> MergeField (AMTSource.hpp:291-366) on decoded pictures in HBM.
 
     srcY (P,H,pitch), srcU/srcV (P,H/2,pitch) torch tensors (srcU = the interleaved UV plane and srcV = None for NV12);
-    dst frame i = even rows of picture top_index[i], odd rows of picture bottom_index[i] (None = i)."""
+    dst frame i = even rows of picture top_index[i], odd rows of picture bottom_index[i] (None = i).
+    msb: the pictures are MSB-aligned 16-bit containers (P010 / P012), read as container >> (16 - dst.bits); dst is the usual LSB clip."""
     es = dst.es
     n = dst.num_frames
     ti = (C.c_int * n)(*[int(v) for v in top_index]) if top_index is not None else None
     bi = (C.c_int * n)(*[int(v) for v in bottom_index]) if bottom_index is not None else None
-    ctx.check(ctx.lib.amtgpu_weave_fields_batch(
+    fn = ctx.lib.amtgpu_weave_fields_batch_msb if msb else ctx.lib.amtgpu_weave_fields_batch
+    ctx.check(fn(
         ctx.h, _p(srcY), _p(srcU), _p(srcV) if srcV is not None else None, int(srcY.stride(0)) * es, int(srcU.stride(0)) * es,
         int(srcY.stride(1)), int(srcU.stride(1)), int(srcY.shape[0]), ti, bi, 1 if nv12 else 0, dst.bits, dst.width, dst.height,
         _p(dst.Y), _p(dst.U), _p(dst.V), dst.strideY, dst.strideUV, dst.pitchY, dst.pitchUV, n))
@@ -609,6 +659,11 @@ class LogoFinder:
     def add(self, clip: DeviceClip):
         self.add_device(clip.Y)
 
+    def add_surfaces(self, surfaces: DeviceSurfaces):
+        """the Y planes of decoder surfaces (NV12, P010, ...; MSB-aligned ones are summed as container >> (16 - bits)).  async"""
+        d = surfaces.ref()
+        self.ctx.check(self.ctx.lib.amtgpu_logofind_add_surfaces(self.h, C.byref(d), surfaces.num_frames))
+
     @property
     def nframes(self):
         return int(self.ctx.lib.amtgpu_logofind_nframes(self.h))
@@ -707,6 +762,14 @@ class ScanLogoStream:
         return self._fed(self.ctx.lib.amtgpu_scanlogo_stream_feed_rect, Y, U, V, int(Y.stride(0)) * es, int(U.stride(0)) * es, int(Y.stride(1)),
                          int(U.stride(1)), int(Y.shape[0]))
 
+    def feed_surfaces(self, surfaces: DeviceSurfaces):
+        """the same on decoder surfaces (NV12, P010, planar MSB ...) of the session's depth: only the rectangle is read"""
+        d = surfaces.ref()
+        nkept, done = C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.lib.amtgpu_scanlogo_stream_feed_surfaces(self.h, C.byref(d), surfaces.num_frames, C.byref(nkept), C.byref(done)),
+                       "ScanLogoStream")
+        return nkept.value, bool(done.value)
+
     def status(self):
         """{"nread": frames consumed up to and including the one that closed the stream, "nkept", "done"}"""
         nread, nkept, done = C.c_int64(), C.c_int(), C.c_int()
@@ -727,18 +790,21 @@ class ScanLogoStream:
 
 def ScanLogoAutoStream(ctx: Context, batches, width, height, serviceid, dstpath, thy, numMaxFrames, cb=None, bits=8, **params):
     """ScanLogoAuto over a clip that is streamed, not resident: `batches` is a callable that returns a fresh iterator of DeviceClip
-    batches (`bits` deep, in stream order).  Pass 1 feeds every batch to a LogoFinder; pass 2 feeds a ScanLogoStream on the best candidate and
+    or DeviceSurfaces batches (`bits` deep, in stream order; each batch is taken as what it is).  Pass 1 feeds every batch to a LogoFinder; pass 2 feeds a ScanLogoStream on the best candidate and
     stops iterating once its quota is full.  Returns the LogoCandidate; raises AmtError ("no logo found", or ScanLogo's message)."""
     finder = LogoFinder(ctx, width, height, bits)
     for clip in batches():
-        finder.add(clip)
+        if isinstance(clip, DeviceSurfaces):
+            finder.add_surfaces(clip)
+        else:
+            finder.add(clip)
     cands = finder.candidates(1, **params)
     if not cands:
         raise AmtError("no logo found")
     r = cands[0]
     stream = ScanLogoStream(ctx, width, height, r.imgx, r.imgy, r.w, r.h, thy, numMaxFrames, bits=bits)
     for clip in batches():
-        if stream.feed(clip)[1]:
+        if (stream.feed_surfaces(clip) if isinstance(clip, DeviceSurfaces) else stream.feed(clip))[1]:
             break
     ctx.check(stream.finish(serviceid, dstpath, cb), "ScanLogoStream")
     return r

@@ -34,6 +34,12 @@ class LogoRect(C.Structure):
                 ("reserved", c_i)]
 
 
+class Surfaces(C.Structure):
+    """AmtGpuSurfaces (include/amt_gpu.h)"""
+    _fields_ = [("Y", c_p), ("U", c_p), ("V", c_p), ("strideY", c_i64), ("strideUV", c_i64), ("pitchY", c_i), ("pitchUV", c_i), ("bits", c_i),
+                ("interleaved", c_i), ("msb_aligned", c_i), ("reserved", c_i)]
+
+
 class Collectives(C.Structure):
     """AmtGpuCollectives (include/amt_gpu.h)"""
     _fields_ = [("rank", c_i), ("world", c_i), ("allgather", ALLGATHER_CB), ("allreduce_sum_i64", ALLREDUCE_CB), ("user", c_p)]
@@ -80,6 +86,9 @@ SIGNATURES = {
     "amtgpu_scanlogo_fileW": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, CB]),
     "amtgpu_weave_fields_batch": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p,
                                         c_i64, c_i64, c_i, c_i, c_i]),
+    "amtgpu_weave_fields_batch_msb": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p,
+                                            c_i64, c_i64, c_i, c_i, c_i]),
+    "amtgpu_surfaces_extract_rect": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i]),
     "amtgpu_amts_load": (c_p, [c_p, c_s]),
     "amtgpu_amts_destroy": (None, [c_p]),
     "amtgpu_amts_get_info": (c_i, [c_p, c_p, c_p, c_p]),
@@ -156,6 +165,7 @@ SIGNATURES = {
     "amtgpu_logofind_create": (c_p, [c_p, c_i, c_i, c_i]),
     "amtgpu_logofind_destroy": (None, [c_p]),
     "amtgpu_logofind_add_batch": (c_i, [c_p, c_p, c_i64, c_i, c_i]),
+    "amtgpu_logofind_add_surfaces": (c_i, [c_p, c_p, c_i]),
     "amtgpu_logofind_nframes": (c_i64, [c_p]),
     "amtgpu_logofind_get_sums": (c_i, [c_p, c_p]),
     "amtgpu_logofind_set_sums": (c_i, [c_p, c_p, c_i64]),
@@ -170,6 +180,7 @@ SIGNATURES = {
     "amtgpu_scanlogo_stream_destroy": (None, [c_p]),
     "amtgpu_scanlogo_stream_feed": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_p, c_p]),
     "amtgpu_scanlogo_stream_feed_rect": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_p, c_p]),
+    "amtgpu_scanlogo_stream_feed_surfaces": (c_i, [c_p, c_p, c_i, c_p, c_p]),
     "amtgpu_scanlogo_stream_status": (c_i, [c_p, c_p, c_p, c_p]),
     "amtgpu_scanlogo_stream_finish": (c_i, [c_p, c_i, c_s, CB]),
     "amtgpu_scanlogo_stream_finish_sharded": (c_i, [c_p, c_p, c_i, c_s, CB]),

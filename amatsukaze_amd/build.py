@@ -27,6 +27,8 @@ SOURCES = [
     "ingest_kernels.hip",
     "amt_gpu_logofind.hip",
     "logofind_kernels.hip",
+    "logofind_msb_kernels.hip",
+    "surface_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

@@ -534,6 +534,9 @@ struct AmtGpuScanLogoStream {
     size_t keepCap = 0;
     DevBuf<int> dKeep;
     hipEvent_t keepUploaded = nullptr;
+    // feed_surfaces: the rectangle of a batch of decoder surfaces as planar LSB planes, tight like the store; grows to the largest batch seen
+    DevBuf<uint8_t> surfY, surfU, surfV;
+    int surfCap = 0;
     int nkept() const { return (int)keptVerdict.size(); }
     size_t slotY() const { return (size_t)rect.w * rect.h * es; }           // bytes of one kept frame's luma / chroma rectangle
     size_t slotC() const { return (size_t)rect.wUV * rect.hUV * es; }
@@ -628,6 +631,35 @@ void stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const 
     s->done = m == room;
 }
 
+// the next nframes frames of the stream as decoder surfaces: their rectangle through the session's scratch, then stream_feed's rect_only path
+void stream_feed_surfaces(AmtGpuScanLogoStream* s, const AmtGpuSurfaces* batch, int nframes)
+{
+    if (s->spent) throw std::runtime_error("[ScanLogo] the session has been finished");
+    if (nframes < 0) throw std::runtime_error("[ScanLogo] negative frame count");
+    if (nframes == 0 || s->done) return;
+    if (!batch) throw std::runtime_error("[ScanLogo] null surface descriptor");
+    if (batch->bits != s->bits) throw std::runtime_error("[ScanLogo] surfaces of another depth than the session's");
+    const ScanRect& r = s->rect;
+    if (!batch->interleaved && !batch->msb_aligned) {
+        // planar LSB planes are what feed takes
+        stream_feed(s, batch->Y, batch->U, batch->V, batch->strideY, batch->strideUV, batch->pitchY, batch->pitchUV, nframes, false);
+        return;
+    }
+    AmtGpuContext* c = s->ctx;
+    (void)surface_batch(batch, "[ScanLogo]");              // a bad descriptor is refused before the scratch is touched
+    if (s->surfCap < nframes) {
+        // (hipFree waits for the kernels that still read the old scratch)
+        s->surfCap = 0;
+        s->surfY.alloc(s->slotY() * nframes);
+        s->surfU.alloc(s->slotC() * nframes);
+        s->surfV.alloc(s->slotC() * nframes);
+        s->surfCap = nframes;
+    }
+    surfaces_extract(c, batch, "[ScanLogo]", r, nframes, PlanesOut{s->surfY.get(), s->surfU.get(), s->surfV.get()}, (int64_t)s->slotY(), (int64_t)s->slotC(),
+                     r.w, r.wUV);
+    stream_feed(s, s->surfY.get(), s->surfU.get(), s->surfV.get(), (int64_t)s->slotY(), (int64_t)s->slotC(), r.w, r.wUV, nframes, true);
+}
+
 // MakeInitialLogo's regression and the two ReMakeLogo rounds over the store (LogoScan.hpp:845-848, 1065-1071); sharded: this rank's share of
 // the quota first, as the resident driver hands it out
 void stream_finish(AmtGpuScanLogoStream* s, const AmtGpuCollectives* coll, int serviceid, const char* dstpath, AMTGPU_LOGO_ANALYZE_CB cb)
@@ -693,6 +725,15 @@ int amtgpu_scanlogo_stream_feed_rect(AmtGpuScanLogoStream* s, const void* dY, co
     if (!s) return 0;
     return guard(s->ctx, [&] {
         stream_feed(s, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, nframes, true);
+        stream_report(s, nullptr, nkept, done);
+    });
+}
+
+int amtgpu_scanlogo_stream_feed_surfaces(AmtGpuScanLogoStream* s, const AmtGpuSurfaces* batch, int nframes, int* nkept, int* done)
+{
+    if (!s) return 0;
+    return guard(s->ctx, [&] {
+        stream_feed_surfaces(s, batch, nframes);
         stream_report(s, nullptr, nkept, done);
     });
 }

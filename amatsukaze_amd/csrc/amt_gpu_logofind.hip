@@ -37,7 +37,8 @@ AmtGpuLogoFind* logofind_new(AmtGpuContext* c, int width, int height, int bits)
     return lf.release();
 }
 
-void logofind_add(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes)
+// shift > 0: the planes are MSB-aligned 16-bit containers, summed as container >> shift (= 16 - bits)
+void logofind_add(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes, int shift = 0)
 {
     if (nframes < 0) throw std::runtime_error("[LogoFind] negative frame count");
     if (nframes == 0) return;
@@ -48,8 +49,13 @@ void logofind_add(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int 
     const int sp = lf->ctx->prof_begin("logofind_kernel");
     for (long long f0 = 0; f0 < nframes; f0 += cap) {
         const int n = (int)std::min<long long>(cap, nframes - f0);
-        AMT_HIP(launch_logofind(lf->ctx->stream, lf->bits, (const uint8_t*)dY + f0 * frame_stride, frame_stride, pitch, lf->width, lf->height, n,
-                                lf->num_cus, lf->dSums.get(), lf->dSums.get() + npx(lf)));
+        const uint8_t* y0 = (const uint8_t*)dY + f0 * frame_stride;
+        if (shift)
+            AMT_HIP(launch_logofind_msb(lf->ctx->stream, lf->bits, shift, y0, frame_stride, pitch, lf->width, lf->height, n, lf->num_cus,
+                                        lf->dSums.get(), lf->dSums.get() + npx(lf)));
+        else
+            AMT_HIP(launch_logofind(lf->ctx->stream, lf->bits, y0, frame_stride, pitch, lf->width, lf->height, n, lf->num_cus, lf->dSums.get(),
+                                    lf->dSums.get() + npx(lf)));
     }
     lf->ctx->prof_end(sp);
     lf->nframes += nframes;
@@ -118,6 +124,19 @@ int amtgpu_logofind_add_batch(AmtGpuLogoFind* lf, const void* dY, int64_t frame_
 {
     if (!lf) return 0;
     return guard(lf->ctx, [&] { logofind_add(lf, dY, frame_stride, pitch, nframes); });
+}
+
+int amtgpu_logofind_add_surfaces(AmtGpuLogoFind* lf, const AmtGpuSurfaces* batch, int nframes)
+{
+    if (!lf) return 0;
+    return guard(lf->ctx, [&] {
+        if (nframes < 0) throw std::runtime_error("[LogoFind] negative frame count");
+        if (nframes == 0) return;
+        const SurfaceBatch b = surface_batch(batch, "[LogoFind]", true);
+        if (batch->bits != lf->bits) throw std::runtime_error("[LogoFind] surfaces of another depth than the finder's");
+        // a Y plane is a Y plane whatever the chroma layout; the MSB form (shift 0 at 16 bits: the plain one) reads container >> shift
+        logofind_add(lf, b.Y, b.strideY, b.pitchY, nframes, b.shift);
+    });
 }
 
 int64_t amtgpu_logofind_nframes(const AmtGpuLogoFind* lf) { return lf ? lf->nframes : -1; }

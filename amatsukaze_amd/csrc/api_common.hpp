@@ -95,6 +95,47 @@ inline amt::PlaneBatch plane_batch(int bits, const void* Y, const void* U, const
     return amt::PlaneBatch{Y, U, V, strideY / es, strideUV / es, pitchY, pitchUV};
 }
 
+// A batch of decoder surfaces as the kernels take it, or a refusal in the caller's words (`who`: "[ScanLogo]", ...): the one place that
+// reads an AmtGpuSurfaces.  luma_only: the chroma fields are not looked at (the logo finder).
+inline amt::SurfaceBatch surface_batch(const AmtGpuSurfaces* s, const char* who, bool luma_only = false)
+{
+    auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
+    if (!s) refuse("null surface descriptor");
+    if (s->bits < 8 || s->bits > 16) refuse("surface bits must be 8..16");
+    if (s->msb_aligned && s->bits == 8) refuse("MSB-aligned surfaces are 16-bit containers: bits must be 9..16");
+    if (s->reserved != 0) refuse("reserved field of the surface descriptor must be 0");
+    const int es = sample_bytes(s->bits);
+    if (!s->Y || (!luma_only && (!s->U || (!s->interleaved && !s->V)))) refuse("null surface plane");
+    if (s->strideY % es || (!luma_only && s->strideUV % es)) refuse("odd byte stride for 16-bit containers");
+    if ((uintptr_t)s->Y % es || (!luma_only && ((uintptr_t)s->U % es || (!s->interleaved && (uintptr_t)s->V % es))))
+        refuse("surface plane base not aligned to the container size");
+    amt::SurfaceBatch b{s->Y, luma_only ? nullptr : s->U, luma_only || s->interleaved ? nullptr : s->V, s->strideY, luma_only ? 0 : s->strideUV,
+                        s->pitchY, luma_only ? 0 : s->pitchUV, es, s->interleaved ? 1 : 0, s->msb_aligned ? 16 - s->bits : 0};
+    return b;
+}
+
+// The rectangle r of nframes surfaces as planar LSB planes (dst strides in bytes, pitches in samples), enqueued on the context's stream:
+// what amtgpu_surfaces_extract_rect does once its arguments are read, and what the ScanLogo session's feed_surfaces runs into its scratch.
+inline void surfaces_extract(AmtGpuContext* c, const AmtGpuSurfaces* src, const char* who, const amt::ScanRect& r, int nframes, const amt::PlanesOut& dst,
+                             int64_t dstrideY, int64_t dstrideUV, int dpitchY, int dpitchUV)
+{
+    auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
+    if (nframes < 0) refuse("negative frame count");
+    if (nframes == 0) return;
+    const amt::SurfaceBatch b = surface_batch(src, who);
+    if (r.imgx < 0 || r.imgy < 0 || r.w <= 0 || r.h <= 0 || (r.w & 1) || (r.h & 1)) refuse("rectangle must be even-sized and inside the surface");
+    if (b.pitchY < r.imgx + r.w) refuse("surface pitchY smaller than the rectangle's rows");
+    if (b.pitchUV < (b.interleaved ? 2 : 1) * (r.cx + r.wUV)) refuse("surface pitchUV smaller than the rectangle's rows");
+    if (!dst.Y || !dst.U || !dst.V) refuse("null destination plane");
+    if (dpitchY < r.w || dpitchUV < r.wUV) refuse("destination pitch smaller than the rectangle's rows");
+    if (dstrideY % b.es || dstrideUV % b.es || (uintptr_t)dst.Y % b.es || (uintptr_t)dst.U % b.es || (uintptr_t)dst.V % b.es)
+        refuse("destination not aligned to the sample size");
+    c->bind();
+    const int sp = c->prof_begin("surfaces_extract_kernel");
+    AMT_HIP(amt::launch_surfaces_extract(c->stream, b, r, nframes, dst, dstrideY, dstrideUV, dpitchY, dpitchUV));
+    c->prof_end(sp);
+}
+
 // run f(); on any exception keep the message on the context and return 0 (no exceptions cross the ABI)
 template <typename F> inline int guard(AmtGpuContext* c, F&& f, const char* caller = __builtin_FUNCTION())
 {

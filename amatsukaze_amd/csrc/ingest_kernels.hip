@@ -17,6 +17,18 @@ namespace amt {
 
 constexpr int kWeaveRows = 8;      // rows per workgroup (one wave per row, two rounds)
 
+// both 16-bit halves of w shifted right by s
+__device__ __forceinline__ uint32_t weave_pk_shr16(uint32_t w, int s)
+{
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    us2 v = __builtin_bit_cast(us2, w);
+    v >>= (unsigned short)s;
+    return __builtin_bit_cast(uint32_t, v);
+}
+
+// MSB: the pictures are MSB-aligned 16-bit containers (P010 / P012 decoder output, a.es == 2) and every sample copied is
+// container >> a.shift -- one packed shift per dword on the vector path, 16-bit elements on the element path.  Without it: the plain copy.
+template <bool MSB>
 __global__ __launch_bounds__(256)
 void weave_fields_kernel(WeaveArgs a, const int* __restrict__ top_index, const int* __restrict__ bottom_index)
 {
@@ -37,9 +49,24 @@ void weave_fields_kernel(WeaveArgs a, const int* __restrict__ top_index, const i
             const int nb = pl == 0 ? a.rowY : a.rowUV;
             if (a.vec) {
                 for (int x = lane * 16; x < nb; x += 64 * 16) {
-                    if (x + 16 <= nb) *reinterpret_cast<uint4*>(d + x) = *reinterpret_cast<const uint4*>(s + x);
-                    else for (int k = x; k < nb; ++k) d[k] = s[k];
+                    if constexpr (MSB) {
+                        if (x + 16 <= nb) {
+                            uint4 q = *reinterpret_cast<const uint4*>(s + x);
+                            q.x = weave_pk_shr16(q.x, a.shift); q.y = weave_pk_shr16(q.y, a.shift);
+                            q.z = weave_pk_shr16(q.z, a.shift); q.w = weave_pk_shr16(q.w, a.shift);
+                            *reinterpret_cast<uint4*>(d + x) = q;
+                        } else {
+                            for (int k = x; k < nb; k += 2)
+                                *reinterpret_cast<uint16_t*>(d + k) = (uint16_t)(*reinterpret_cast<const uint16_t*>(s + k) >> a.shift);
+                        }
+                    } else {
+                        if (x + 16 <= nb) *reinterpret_cast<uint4*>(d + x) = *reinterpret_cast<const uint4*>(s + x);
+                        else for (int k = x; k < nb; ++k) d[k] = s[k];
+                    }
                 }
+            } else if constexpr (MSB) {
+                for (int x = 2 * lane; x < nb; x += 128)
+                    *reinterpret_cast<uint16_t*>(d + x) = (uint16_t)(*reinterpret_cast<const uint16_t*>(s + x) >> a.shift);
             } else {
                 for (int x = lane; x < nb; x += 64) d[x] = s[x];
             }
@@ -53,7 +80,8 @@ void weave_fields_kernel(WeaveArgs a, const int* __restrict__ top_index, const i
             } else {
                 const uint16_t* s16 = reinterpret_cast<const uint16_t*>(s);
                 uint16_t* d16 = reinterpret_cast<uint16_t*>(d);
-                for (int x = lane; x < n; x += 64) d16[x] = s16[2 * x + (pl - 1)];
+                if constexpr (MSB) { for (int x = lane; x < n; x += 64) d16[x] = (uint16_t)(s16[2 * x + (pl - 1)] >> a.shift); }
+                else { for (int x = lane; x < n; x += 64) d16[x] = s16[2 * x + (pl - 1)]; }
             }
         }
     }
@@ -103,7 +131,9 @@ hipError_t launch_weave_fields(hipStream_t st, const WeaveArgs& a, const int* dt
     if (nframes <= 0) return hipSuccess;
     const int nrows = a.H + 2 * a.HUV;
     dim3 grid((unsigned)((nrows + kWeaveRows - 1) / kWeaveRows), (unsigned)nframes), block(256);
-    hipLaunchKernelGGL(weave_fields_kernel, grid, block, 0, st, a, dtop_index, dbottom_index);
+    if (a.shift && a.es != 2) return hipErrorInvalidValue;
+    if (a.shift) hipLaunchKernelGGL(weave_fields_kernel<true>, grid, block, 0, st, a, dtop_index, dbottom_index);
+    else hipLaunchKernelGGL(weave_fields_kernel<false>, grid, block, 0, st, a, dtop_index, dbottom_index);
     return hipGetLastError();
 }
 

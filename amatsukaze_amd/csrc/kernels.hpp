@@ -55,6 +55,15 @@ hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b,
 hipError_t launch_scan_keep(hipStream_t st, int es, const PlaneBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
                             long long first_slot);
 
+// ---- surface_kernels.hip ----
+// A batch of decoder surfaces (AmtGpuSurfaces, amt_gpu.h) that has passed surface_batch (api_common.hpp): strides in bytes, pitches in
+// containers of es bytes; interleaved: U is the U0 V0 U1 V1 ... plane and V unused; sample = container >> shift (0 for LSB input)
+struct SurfaceBatch { const void *Y, *U, *V; long long strideY, strideUV; int pitchY, pitchUV; int es, interleaved, shift; };
+// the rectangle r of all nframes surfaces as planar LSB samples: w x h luma at dst.Y, wUV x hUV chroma at dst.U / dst.V per frame (strides
+// in bytes, pitches in samples).  Plane bases are multiples of es.  One launch
+hipError_t launch_surfaces_extract(hipStream_t st, const SurfaceBatch& s, const ScanRect& r, int nframes, const PlanesOut& dst, long long dstrideY,
+                                   long long dstrideUV, int dpitchY, int dpitchUV);
+
 // ---- ingest_kernels.hip ----
 struct WeaveArgs {
     const uint8_t* srcY; const uint8_t* srcU; const uint8_t* srcV;   // decoded pictures (srcV unused for NV12)
@@ -66,7 +75,9 @@ struct WeaveArgs {
     int rowY, rowUV;                                                 // bytes per output row (width * es, widthUV * es)
     int H, HUV;
     int nv12, es, vec;                                               // vec: all rows 16-byte aligned
+    int shift = 0;                                                   // MSB-aligned pictures (es 2): sample = container >> shift
 };
+// a.shift != 0 launches the kernel's shifting form; the plain copy is the same code as before
 hipError_t launch_weave_fields(hipStream_t st, const WeaveArgs& a, const int* dtop_index, const int* dbottom_index, int nframes);
 // `nchunks` pieces of `chunk` bytes, src_stride apart at src (HBM, or page-locked host memory at its device address), dst_stride apart at dst
 hipError_t launch_ingest_rows(hipStream_t st, const void* src, long long src_stride, void* dst, long long dst_stride, unsigned long long chunk,
@@ -80,6 +91,9 @@ long long logofind_launch_cap(int bits);
 // nframes <= logofind_launch_cap(bits) (the caller splits); dS1 / dSM: W*H int64 each, added to
 hipError_t launch_logofind(hipStream_t st, int bits, const void* dY, long long frame_stride, int pitch_elems, int W, int H, int nframes,
                            int num_cus, unsigned long long* dS1, unsigned long long* dSM);
+// logofind_msb_kernels.hip: the same sums of container >> shift (16-bit containers; bits = the depth of the shifted samples)
+hipError_t launch_logofind_msb(hipStream_t st, int bits, int shift, const void* dY, long long frame_stride, int pitch_elems, int W, int H,
+                               int nframes, int num_cus, unsigned long long* dS1, unsigned long long* dSM);
 
 // ---- eval_fused_kernels.hip, eval_pair_kernels.hip, eval_linear_kernels.hip ----
 // tile plan of one evaluation logo resident in HBM (eval_tiles.hpp; eval_pair_kernels.hip).  slot = (band * kTileWaves + wave) * 64 + lane

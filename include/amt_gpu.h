@@ -40,7 +40,9 @@ extern "C" {
                                    *    amtgpu_analyze_monitor_stats; automatic logo detection (amtgpu_logofind_*,
                                    *    amtgpu_scanlogo_auto, _auto_sharded, _file_auto); the streamed ScanLogo session
                                    *    (amtgpu_scanlogo_stream_*); ScanLogo for 9..12-bit clips (amtgpu_scanlogo_bits, _sharded_bits,
-                                   *    _stream_create_bits, _auto_bits, _auto_sharded_bits; the 'AMTH' raw clip file) */
+                                   *    _stream_create_bits, _auto_bits, _auto_sharded_bits; the 'AMTH' raw clip file); decoder surfaces
+                                   *    (AmtGpuSurfaces: amtgpu_surfaces_extract_rect, amtgpu_scanlogo_stream_feed_surfaces,
+                                   *    amtgpu_logofind_add_surfaces, amtgpu_weave_fields_batch_msb) */
 #define AMTGPU_NUM_FADE 11            /* LogoAnalyzeFrame p/t/b[11]  (LogoScan.hpp:1100-1103) */
 #define AMTGPU_ANALYZE_FLOATS 33      /* floats per source frame in an analysis record */
 
@@ -175,6 +177,40 @@ int   amtgpu_weave_fields_batch(AmtGpuContext* ctx, const void* dsrcY, const voi
                                 const int* top_index, const int* bottom_index, int nv12, int bits, int width, int height,
                                 void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV,
                                 int nframes);
+
+/* the same for MSB-aligned pictures (P010 / P012 decoder output: 16-bit containers with the sample in the high bits; bits 9..16 only):
+ * every sample is read as container >> (16 - bits), whatever sits in the low bits is dropped, and the output is the usual planar LSB
+ * clip.  Plane bases and strides must be multiples of 2.  This is the way into LogoFrame, AMTAnalyzeLogo and AMTEraseLogo for a P010 host */
+int   amtgpu_weave_fields_batch_msb(AmtGpuContext* ctx, const void* dsrcY, const void* dsrcU, const void* dsrcV,
+                                    int64_t src_strideY, int64_t src_strideUV, int src_pitchY, int src_pitchUV, int num_pictures,
+                                    const int* top_index, const int* bottom_index, int nv12, int bits, int width, int height,
+                                    void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV,
+                                    int nframes);
+
+/* ---- decoder surfaces: what a hardware decoder or an FFmpeg hwframe hands out -- NV12 (8-bit Y plane plus one interleaved U0 V0 U1 V1 ...
+ *      plane), P010 / P012 (the same layout in 16-bit containers with the sample in the HIGH bits) -- described once and taken as they are
+ *      by the entry points that only read a part of the frame: the ScanLogo session (amtgpu_scanlogo_stream_feed_surfaces, the logo
+ *      rectangle) and the logo finder (amtgpu_logofind_add_surfaces, the Y plane).  The sample rule is a plain right shift: whatever
+ *      sits in the low 16 - bits bits of an MSB-aligned container is discarded (P010 says zero; decoders and dithering filters do not
+ *      always leave zero there).  4:2:0 only; linear (untiled, uncompressed) layouts only. ---- */
+typedef struct AmtGpuSurfaces {
+    const void* Y;               /* luma plane of the first picture (device) */
+    const void* U;               /* planar: U plane.  interleaved: the UV plane (U0 V0 U1 V1 ...) */
+    const void* V;               /* planar: V plane.  interleaved: ignored, may be NULL */
+    int64_t strideY, strideUV;   /* bytes between pictures (Y and UV of one allocation: both = the surface size) */
+    int pitchY, pitchUV;         /* container elements per row; of the UV plane when interleaved (>= 2 * chroma width) */
+    int bits;                    /* 8 (uint8 containers) or 9..16 (little-endian uint16 containers) */
+    int interleaved;             /* 0 planar, 1 NV12 / P010 layout */
+    int msb_aligned;             /* 0: sample = container.  1: sample = container >> (16 - bits); refused at bits == 8 */
+    int reserved;                /* 0 */
+} AmtGpuSurfaces;
+/* the rectangle (imgx, imgy, w, h) of nframes surfaces as planar LSB samples of depth src->bits: w x h luma at dY, w/2 x h/2 chroma
+ * (origin imgx >> 1, imgy >> 1) at dU / dV per frame, frames dstrideY / dstrideUV BYTES apart, rows dpitchY / dpitchUV SAMPLES -- what
+ * amtgpu_scanlogo_stream_feed_rect and amtgpu_erase_rect_batch take.  w, h even and positive, the rectangle inside the pitches;
+ * (0, 0, W, H) planarises whole progressive frames.  Reads nothing outside the rectangle's rows, writes nothing outside w / w/2 samples
+ * of a destination row.  nframes == 0 returns 1.  async */
+int   amtgpu_surfaces_extract_rect(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int imgx, int imgy, int w, int h, int nframes,
+                                   void* dY, void* dU, void* dV, int64_t dstrideY, int64_t dstrideUV, int dpitchY, int dpitchUV);
 
 /* ---- the stream-index file AMTSource is built from: replaces LoadAMTSource's reader (AMTSource.hpp:854-871; writer :835-852,
  *      File::writeArray framing CoreUtils.hpp:275-284, FilterSourceFrame StreamReform.hpp:145-154) and the frame-assembly rule of
@@ -435,6 +471,12 @@ int  amtgpu_scanlogo_stream_feed(AmtGpuScanLogoStream* s, const void* dY, const 
 /* the same on planes that hold ONLY the rectangle (w x h luma, w/2 x h/2 chroma per frame), as amtgpu_erase_rect_batch takes them */
 int  amtgpu_scanlogo_stream_feed_rect(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const void* dV, int64_t strideY, int64_t strideUV,
                                       int pitchY, int pitchUV, int nframes, int* nkept, int* done);
+/* the same on decoder surfaces (AmtGpuSurfaces above: NV12, P010, planar MSB ...; batch->bits must be the session's depth): the session's
+ * rectangle of all nframes surfaces goes to a scratch buffer the session owns (it grows to the largest batch seen) as planar LSB planes,
+ * then feed_rect's path runs on it -- the same verdicts, quota and store.  Only the rectangle is read: ~1/30 of the bytes a planarising
+ * weave of whole 1440 x 1080 frames moves for a 256 x 128 logo.  feed, feed_rect and feed_surfaces may be mixed within one session; the
+ * batch may be overwritten as after feed */
+int  amtgpu_scanlogo_stream_feed_surfaces(AmtGpuScanLogoStream* s, const AmtGpuSurfaces* batch, int nframes, int* nkept, int* done);
 /* *nread = the reference's readCount (:883): frames consumed up to and including the one that closed the stream; any pointer may be NULL */
 int  amtgpu_scanlogo_stream_status(const AmtGpuScanLogoStream* s, int64_t* nread, int* nkept, int* done);
 /* the initial regression and the two ReMakeLogo rounds (:923-1036) over the kept rectangles, cb driven from 50 % upward as by
@@ -565,6 +607,9 @@ void amtgpu_logofind_destroy(AmtGpuLogoFind* lf);
  * uint8 for 8 bits, uint16 containers above) to the sums.  Batches of any length: the driver splits them into launches whose 32-bit
  * partials cannot overflow.  async */
 int  amtgpu_logofind_add_batch(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes);
+/* the same from decoder surfaces (AmtGpuSurfaces: only Y, strideY, pitchY, bits and msb_aligned are read; bits must be the finder's).  The
+ * sums of MSB-aligned input are those of the shifted samples container >> (16 - bits), exact as ever.  async */
+int  amtgpu_logofind_add_surfaces(AmtGpuLogoFind* lf, const AmtGpuSurfaces* batch, int nframes);
 int64_t amtgpu_logofind_nframes(const AmtGpuLogoFind* lf);
 /* sums: 2*W*H int64 (host), S1 then SM, row-major.  get synchronises; set replaces the sums and the frame count (nframes >= 0) */
 int  amtgpu_logofind_get_sums(AmtGpuLogoFind* lf, int64_t* sums);
