@@ -544,7 +544,10 @@ int  amtgpu_scanlogo_stream_finish_sharded(AmtGpuScanLogoStream* s, const AmtGpu
 AmtGpuFrameStats* amtgpu_framestats_create(AmtGpuContext* ctx, int width, int height, int bits);
 void amtgpu_framestats_destroy(AmtGpuFrameStats* fs);
 /* dprevY: Y plane of the frame before the batch (device), or NULL -> frame 0 compares with itself.
- * dout: nframes*AMTGPU_FS_WORDS uint64 (device).  async */
+ * dout: nframes*AMTGPU_FS_WORDS uint64 (device).  async
+ * Frame n lies at dY + n*frame_stride BYTES, its rows `pitch` ELEMENTS apart; dprevY is one frame of the same pitch, anywhere.
+ * dY, dprevY, frame_stride and the pitch need to be aligned to the sample size (1 or 2 bytes), nothing more: any pitch >= width,
+ * any gap between frames.  Only height * pitch elements of each frame (and of dprevY) are ever read. */
 int  amtgpu_framestats_batch(AmtGpuFrameStats* fs, const void* dY, int64_t frame_stride, int pitch,
                              const void* dprevY, int nframes, uint64_t* dout);
 /* Frame-sharded runs of the whole-frame passes (fourth row): every rank computes the metrics of its own
@@ -605,7 +608,8 @@ AmtGpuLogoFind* amtgpu_logofind_create(AmtGpuContext* ctx, int width, int height
 void amtgpu_logofind_destroy(AmtGpuLogoFind* lf);
 /* adds the Y planes of nframes frames (device; frame n at dY + n*frame_stride bytes, pitch in ELEMENTS as everywhere in this header,
  * uint8 for 8 bits, uint16 containers above) to the sums.  Batches of any length: the driver splits them into launches whose 32-bit
- * partials cannot overflow.  async */
+ * partials cannot overflow.  dY, frame_stride and the pitch need to be aligned to the sample size, nothing more (any pitch >= width,
+ * any gap between frames); only height * pitch elements of each frame are ever read.  async */
 int  amtgpu_logofind_add_batch(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes);
 /* the same from decoder surfaces (AmtGpuSurfaces: only Y, strideY, pitchY, bits and msb_aligned are read; bits must be the finder's).  The
  * sums of MSB-aligned input are those of the shifted samples container >> (16 - bits), exact as ever.  async */
