@@ -346,6 +346,11 @@ class LogoFrame:
         n = int(Y.shape[0]) if nframes is None else nframes
         self.ctx.check(self.ctx.lib.amtgpu_logoframe_scan_batch(self.h, _p(Y), int(Y.stride(0)) * es, int(Y.stride(1)), first, n))
 
+    def scan_surfaces(self, surfaces: "DeviceSurfaces", first):
+        """scan_batch on the Y planes of decoder surfaces as they lie (NV12, P010 ...; surfaces.bits must be begin()'s depth).  async"""
+        d = surfaces.ref()
+        self.ctx.check(self.ctx.lib.amtgpu_logoframe_scan_surfaces(self.h, C.byref(d), first, surfaces.num_frames), "scan_surfaces")
+
     def scanFrames(self, clip: DeviceClip, batch: int = 4096):
         self.begin(clip.width, clip.height, clip.bits, clip.num_frames, clip.fps_num, clip.fps_den)
         for f0 in range(0, clip.num_frames, batch):
@@ -451,6 +456,15 @@ class AMTAnalyzeLogo:
         es = 1 if bits <= 8 else 2
         self.ctx.check(self.ctx.lib.amtgpu_analyze_batch(self.h, _p(Y), int(Y.stride(0)) * es, int(Y.stride(1)), bits, int(Y.shape[0]), _p(out)))
 
+    def analyze_surfaces(self, surfaces: "DeviceSurfaces", out=None):
+        """analyze_device on the Y planes of decoder surfaces as they lie (NV12, P010 ...): the device tensor [n, 33] of records.  async"""
+        import torch
+        if out is None:
+            out = torch.empty((surfaces.num_frames, 33), dtype=torch.float32, device=surfaces.Y.device)
+        d = surfaces.ref()
+        self.ctx.check(self.ctx.lib.amtgpu_analyze_surfaces(self.h, C.byref(d), surfaces.num_frames, _p(out)), "analyze_surfaces")
+        return out
+
     def analyze(self, clip: DeviceClip):
         out = np.zeros((clip.num_frames, 33), np.float32)
         self.ctx.check(self.ctx.lib.amtgpu_analyze_batch_host(self.h, _p(clip.Y), clip.strideY, clip.pitchY, clip.bits, clip.num_frames, _p(out)))
@@ -508,6 +522,29 @@ class AMTEraseLogo:
         self.ctx.check(self.ctx.lib.amtgpu_erase_batch_dfades_to(self.h, _p(clip.Y), _p(clip.U), _p(clip.V), _p(dst.Y), _p(dst.U), _p(dst.V),
                                                                  clip.strideY, clip.strideUV, clip.pitchY, clip.pitchUV, clip.bits,
                                                                  clip.num_frames, _p(d_fades)))
+
+    def erase_surfaces(self, surfaces: "DeviceSurfaces", fades=None, d_fades=None, dst: "DeviceSurfaces | None" = None):
+        """Delogo on decoder surfaces where they lie (NV12, P010 / P012, planar MSB): the logo rectangle of `surfaces` is REWRITTEN in place.
+        Exactly one of fades (host, [n, 2]) / d_fades (device, e.g. calc_fades_device's output).  dst (with d_fades only): surfaces of the
+        same layout that already hold a copy of the pictures; Delogo then reads `surfaces` and writes dst's rectangle.  async"""
+        if (fades is None) == (d_fades is None):
+            raise ValueError("erase_surfaces: exactly one of fades / d_fades")
+        if dst is not None and d_fades is None:
+            raise ValueError("erase_surfaces: dst needs d_fades")
+        n = surfaces.num_frames
+        d = surfaces.ref()
+        if d_fades is None:
+            fades = np.ascontiguousarray(fades, np.float32)
+            if fades.size != 2 * n:
+                raise ValueError("erase_surfaces: fades must hold two floats per frame")
+            self.ctx.check(self.ctx.lib.amtgpu_erase_surfaces(self.h, C.byref(d), n, _p(fades)), "erase_surfaces")
+        elif dst is None:
+            self.ctx.check(self.ctx.lib.amtgpu_erase_surfaces_dfades(self.h, C.byref(d), n, _p(d_fades)), "erase_surfaces")
+        else:
+            if dst.num_frames != n:
+                raise ValueError("erase_surfaces: source and destination batches differ in frame count")
+            dd = dst.ref()
+            self.ctx.check(self.ctx.lib.amtgpu_erase_surfaces_dfades_to(self.h, C.byref(d), C.byref(dd), n, _p(d_fades)), "erase_surfaces")
 
     def erase(self, clip: DeviceClip, fades):
         fades = np.ascontiguousarray(fades, np.float32)

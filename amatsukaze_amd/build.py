@@ -23,6 +23,7 @@ SOURCES = [
     "eval_linear_kernels.hip",
     "eval_pair_kernels.hip",
     "erase_scan_kernels.hip",
+    "erase_surface_kernels.hip",
     "stats_kernels.hip",
     "ingest_kernels.hip",
     "amt_gpu_logofind.hip",

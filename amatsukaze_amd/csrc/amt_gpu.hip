@@ -284,6 +284,7 @@ struct AmtGpuLogoFrame {
     bool hostValid = false;
     LogoSelection sel;
     bool selected = false;
+    DevBuf<uint8_t> dBand;                              // scan_surfaces: the luma band of a batch of MSB-aligned surfaces as LSB samples
 };
 
 static AmtGpuLogoFrame* logoframe_new(AmtGpuContext* c, std::vector<std::unique_ptr<LogoPlanes>> logos, float maskratio)
@@ -366,6 +367,32 @@ int amtgpu_logoframe_scan_batch(AmtGpuLogoFrame* lf, const void* dY, int64_t fra
         if (!lf->engine || nframes == 0) return;
         const int nl = (int)lf->logos.size();
         lf->engine->run(dY, frame_stride, pitch, lf->bits, nframes, lf->dResults.get() + (size_t)first * nl * 2);
+        lf->hostValid = false;
+        lf->selected = false;
+    });
+}
+
+int amtgpu_logoframe_scan_surfaces(AmtGpuLogoFrame* lf, const AmtGpuSurfaces* batch, int first, int nframes)
+{
+    return guard(lf->ctx, [&] {
+        const char* who = "[LogoFrame]";
+        auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
+        if (first < 0 || nframes < 0 || first + nframes > lf->numFrames) throw std::runtime_error("frame range outside the clip");
+        if (nframes == 0) return;
+        const SurfaceBatch b = surface_batch(batch, who, true);
+        if (batch->bits != lf->bits) refuse("surface bits differ from the depth given to amtgpu_logoframe_begin");
+        if (!lf->engine) return;
+        // the union of the rectangles of the logos that are scanned: all the engine reads
+        int row0 = 0x7FFFFFFF, row1 = 0, col0 = 0x7FFFFFFF, col1 = 0;
+        for (int i : lf->slotOfEngineLogo) {
+            const LogoPlanes& P = *lf->logos[i];
+            row0 = std::min(row0, P.imgy); row1 = std::max(row1, P.imgy + P.h);
+            col0 = std::min(col0, P.imgx); col1 = std::max(col1, P.imgx + P.w);
+        }
+        if (b.pitchY < col1) refuse("surface pitchY smaller than the rectangle's rows");
+        const LumaView v = surfaces_luma_view(lf->ctx, b, row0, row1, col0, col1, nframes, lf->dBand);
+        const int nl = (int)lf->logos.size();
+        lf->engine->run(v.Y, v.stride_bytes, v.pitch, lf->bits, nframes, lf->dResults.get() + (size_t)first * nl * 2);
         lf->hostValid = false;
         lf->selected = false;
     });
@@ -545,6 +572,7 @@ struct AmtGpuAnalyze {
     int mon_epoch = 1;                  // bumped by every re-arm: a flag stored by a batch of an earlier arming does not count
     bool mon_host_downgraded = false;   // the host has seen the flag: later batches go to EvalEngine::run() directly
     int last_all_exact = 0;             // frames of the latest batch that run() evaluated (monitored mode after a downgrade), else 0
+    DevBuf<uint8_t> dBand;              // analyze_surfaces: the luma band of a batch of MSB-aligned surfaces as LSB samples
     ~AmtGpuAnalyze() { if (hMonFlag) (void)hipHostFree(hMonFlag); }
 };
 
@@ -697,6 +725,22 @@ int amtgpu_analyze_batch(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride
     return guard(an->ctx, [&] {
         if (bits < 8 || bits > 16) throw std::runtime_error("[AMTAnalyzeLogo] Unsupported pixel format");
         analyze_run(an, dY, frame_stride, pitch, bits, nframes, dout);
+    });
+}
+
+int amtgpu_analyze_surfaces(AmtGpuAnalyze* an, const AmtGpuSurfaces* batch, int nframes, float* dout)
+{
+    return guard(an->ctx, [&] {
+        const char* who = "[AMTAnalyzeLogo]";
+        auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
+        if (nframes < 0) refuse("negative frame count");
+        if (nframes == 0) return;
+        const SurfaceBatch b = surface_batch(batch, who, true);
+        if (!dout) refuse("null output");
+        const LogoPlanes& P = an->logo;
+        if (b.pitchY < P.imgx + P.w) refuse("surface pitchY smaller than the rectangle's rows");
+        const LumaView v = surfaces_luma_view(an->ctx, b, P.imgy, P.imgy + P.h, P.imgx, P.imgx + P.w, nframes, an->dBand);
+        analyze_run(an, v.Y, v.stride_bytes, v.pitch, batch->bits, nframes, dout);
     });
 }
 

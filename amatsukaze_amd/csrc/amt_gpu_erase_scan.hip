@@ -120,6 +120,28 @@ static bool erase_wanted(const AmtGpuErase* er, int bits, int nframes)
     return nframes > 0;
 }
 
+// the batch's fades on the device: the caller's device array, or its host array through the pinned slots
+static const float2* erase_fades(AmtGpuErase* er, int nframes, const float* fades, const float* d_fades)
+{
+    if (d_fades) return reinterpret_cast<const float2*>(d_fades);
+    if (!fades) throw std::runtime_error("[AMTEraseLogo] null fades");
+    const int slot = er->fadeSlot;
+    er->fadeSlot ^= 1;
+    if (!er->fadesUploaded[slot]) AMT_HIP(hipEventCreateWithFlags(&er->fadesUploaded[slot], hipEventDisableTiming));
+    else AMT_HIP(hipEventSynchronize(er->fadesUploaded[slot]));          // the upload two batches ago
+    if (er->fadesCap[slot] < (size_t)nframes) {
+        if (er->hFades[slot]) AMT_HIP(hipHostFree(er->hFades[slot]));
+        er->hFades[slot] = nullptr;
+        AMT_HIP(hipHostMalloc((void**)&er->hFades[slot], (size_t)nframes * sizeof(float2), hipHostMallocDefault));
+        er->fadesCap[slot] = (size_t)nframes;
+        er->dFades[slot].alloc(nframes);                                   // hipFree waits for the kernels that read the old copy
+    }
+    std::memcpy(er->hFades[slot], fades, (size_t)nframes * sizeof(float2));
+    AMT_HIP(hipMemcpyAsync(er->dFades[slot].get(), er->hFades[slot], (size_t)nframes * sizeof(float2), hipMemcpyHostToDevice, er->ctx->stream));
+    AMT_HIP(hipEventRecord(er->fadesUploaded[slot], er->ctx->stream));
+    return er->dFades[slot].get();
+}
+
 // Delogo of a batch that has passed erase_wanted: reads src, writes dst (the same planes for the in-place calls)
 static void erase_launch(AmtGpuErase* er, const PlaneBatch& src, const PlanesOut& dst, int bits, int nframes, const float* fades, bool rect_only,
                          const float* d_fades = nullptr)
@@ -127,25 +149,7 @@ static void erase_launch(AmtGpuErase* er, const PlaneBatch& src, const PlanesOut
     const LogoPlanes& P = er->logo;
     if (rect_only && (src.pitchY < P.w || src.pitchUV < P.wUV())) throw std::runtime_error("[AMTEraseLogo] rectangle pitch smaller than the logo width");
     er->ctx->bind();
-    const float2* dfades = reinterpret_cast<const float2*>(d_fades);
-    if (!dfades) {
-        if (!fades) throw std::runtime_error("[AMTEraseLogo] null fades");
-        const int slot = er->fadeSlot;
-        er->fadeSlot ^= 1;
-        if (!er->fadesUploaded[slot]) AMT_HIP(hipEventCreateWithFlags(&er->fadesUploaded[slot], hipEventDisableTiming));
-        else AMT_HIP(hipEventSynchronize(er->fadesUploaded[slot]));          // the upload two batches ago
-        if (er->fadesCap[slot] < (size_t)nframes) {
-            if (er->hFades[slot]) AMT_HIP(hipHostFree(er->hFades[slot]));
-            er->hFades[slot] = nullptr;
-            AMT_HIP(hipHostMalloc((void**)&er->hFades[slot], (size_t)nframes * sizeof(float2), hipHostMallocDefault));
-            er->fadesCap[slot] = (size_t)nframes;
-            er->dFades[slot].alloc(nframes);                                   // hipFree waits for the kernels that read the old copy
-        }
-        std::memcpy(er->hFades[slot], fades, (size_t)nframes * sizeof(float2));
-        AMT_HIP(hipMemcpyAsync(er->dFades[slot].get(), er->hFades[slot], (size_t)nframes * sizeof(float2), hipMemcpyHostToDevice, er->ctx->stream));
-        AMT_HIP(hipEventRecord(er->fadesUploaded[slot], er->ctx->stream));
-        dfades = er->dFades[slot].get();
-    }
+    const float2* dfades = erase_fades(er, nframes, fades, d_fades);
     EraseGeom g;
     g.w = P.w; g.h = P.h; g.wUV = P.wUV(); g.hUV = P.hUV();
     // rectangle-only planes start at the logo's top-left sample; the chroma row parity is a property of the logo's position in
@@ -209,6 +213,63 @@ int amtgpu_erase_batch_dfades_to(AmtGpuErase* er, const void* sY, const void* sU
         if (erase_wanted(er, bits, nframes))
             erase_launch(er, plane_batch(bits, sY, sU, sV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, nullptr, false, d_fades);
     });
+}
+
+// Delogo on decoder surfaces where they lie: src is read, dst (laid out like src; the same descriptor for the in-place calls) is written.
+// Planar LSB surfaces are ordinary planes and take erase_launch; every other layout takes delogo_surfaces_kernel.
+static void erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes, const float* fades, const float* d_fades,
+                           bool device_fades)
+{
+    const char* who = "[AMTEraseLogo]";
+    auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
+    if (nframes < 0) refuse("negative frame count");
+    if (nframes == 0) return;
+    const SurfaceBatch b = surface_batch(src, who);
+    const int bits = src->bits;
+    if (!erase_wanted(er, bits, nframes)) return;
+    if (device_fades ? !d_fades : !fades) refuse(device_fades ? "null device fades" : "null fades");
+    const LogoPlanes& P = er->logo;
+    EraseGeom g;
+    g.w = P.w; g.h = P.h; g.wUV = P.wUV(); g.hUV = P.hUV();
+    g.imgx = P.imgx; g.imgy = P.imgy; g.cx = P.imgx >> P.logUVx; g.cy = P.imgy >> P.logUVy;
+    g.uvparity = (P.imgy / 2) % 2;
+    if (b.pitchY < g.imgx + g.w) refuse("surface pitchY smaller than the rectangle's rows");
+    if (b.pitchUV < (b.interleaved ? 2 : 1) * (g.cx + g.wUV)) refuse("surface pitchUV smaller than the rectangle's rows");
+    PlanesOut out{const_cast<void*>(b.Y), const_cast<void*>(b.U), const_cast<void*>(b.V)};
+    if (dst != src) {
+        const SurfaceBatch d = surface_batch(dst, who);
+        if (dst->bits != src->bits || d.interleaved != b.interleaved || d.shift != b.shift || d.pitchY != b.pitchY || d.pitchUV != b.pitchUV ||
+            d.strideY != b.strideY || d.strideUV != b.strideUV)
+            refuse("destination surfaces differ from the source's in bits, interleaved, msb_aligned, pitches or strides");
+        out = PlanesOut{const_cast<void*>(d.Y), const_cast<void*>(d.U), const_cast<void*>(d.V)};
+    }
+    if (!b.interleaved && !b.shift) {
+        erase_launch(er, PlaneBatch{b.Y, b.U, b.V, b.strideY / b.es, b.strideUV / b.es, b.pitchY, b.pitchUV}, out, bits, nframes, fades, false, d_fades);
+        return;
+    }
+    er->ctx->bind();
+    const float2* dfades = erase_fades(er, nframes, fades, d_fades);
+    const int sp = er->ctx->prof_begin("delogo_surfaces_kernel");
+    // fade 0 is the identity on every sample <= maxv; an MSB sample (container >> (16 - bits)) can never exceed it, an LSB container of a
+    // 9..15-bit surface can (erase_launch's rule)
+    const bool skip_fade0 = er->zeroIdentity && (bits == 8 || bits == 16 || b.shift != 0);
+    AMT_HIP(launch_delogo_surfaces(er->ctx->stream, bits, b, out, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
+    er->ctx->prof_end(sp);
+}
+
+int amtgpu_erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* batch, int nframes, const float* fades)
+{
+    return guard(er->ctx, [&] { erase_surfaces(er, batch, batch, nframes, fades, nullptr, false); });
+}
+
+int amtgpu_erase_surfaces_dfades(AmtGpuErase* er, const AmtGpuSurfaces* batch, int nframes, const float* d_fades)
+{
+    return guard(er->ctx, [&] { erase_surfaces(er, batch, batch, nframes, nullptr, d_fades, true); });
+}
+
+int amtgpu_erase_surfaces_dfades_to(AmtGpuErase* er, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes, const float* d_fades)
+{
+    return guard(er->ctx, [&] { erase_surfaces(er, src, dst, nframes, nullptr, d_fades, true); });
 }
 
 // CalcFade / CalcFade2 on the device (erase_scan_kernels.hip calc_fades_kernel); the host routine above stays the checker's

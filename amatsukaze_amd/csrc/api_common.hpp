@@ -136,6 +136,36 @@ inline void surfaces_extract(AmtGpuContext* c, const AmtGpuSurfaces* src, const 
     c->prof_end(sp);
 }
 
+// The Y planes of a batch of surfaces as the evaluation engines take a luma batch (EvalEngine::run, analyze_run): base of picture 0,
+// bytes between pictures, row pitch in samples.  The engines read rows [row0, row1) and columns [col0, col1) of every picture and
+// nothing else.  LSB surfaces are passed as they lie.  MSB-aligned ones: that band of every picture -- from col0 rounded down to 64
+// containers -- is copied as LSB samples (surfaces_extract_kernel with an empty chroma part) into `scratch`, which grows to the largest
+// batch seen, rows a multiple of 64 samples apart, and the view's base is where sample (0, 0) of picture 0 would lie in that layout:
+// the engines' alignment-dependent choices are those of an aligned planar clip.  The scratch is the caller's (one per object: its
+// surfaces entry points are not re-entrant).
+struct LumaView { const void* Y; int64_t stride_bytes; int pitch; };
+inline LumaView surfaces_luma_view(AmtGpuContext* c, const amt::SurfaceBatch& b, int row0, int row1, int col0, int col1, int nframes,
+                                   amt::DevBuf<uint8_t>& scratch)
+{
+    if (!b.shift) return LumaView{b.Y, b.strideY, b.pitchY};
+    const int c0 = col0 & ~63, bw = col1 - c0, rows = row1 - row0;
+    const int pitch = (bw + 63) & ~63;
+    const size_t frame_bytes = (size_t)rows * pitch * b.es;
+    // (a tail: the engines' aligned 8- and 16-byte accesses may end a few samples behind col1; where the band fills its pitch that is the
+    // next row, and behind the last row of the last picture it must still be the allocation.  The front needs none: c0 is aligned down)
+    const size_t need = frame_bytes * (size_t)nframes + 64;
+    c->bind();
+    if (scratch.size() < need) scratch.alloc(need);        // (hipFree waits for the kernels that still read the old scratch)
+    uint8_t* band = scratch.get();
+    amt::SurfaceBatch luma = b;
+    luma.U = luma.V = nullptr; luma.strideUV = 0; luma.pitchUV = 0;
+    const int sp = c->prof_begin("surfaces_extract_kernel");
+    AMT_HIP(amt::launch_surfaces_extract(c->stream, luma, amt::ScanRect{c0, row0, 0, 0, bw, rows, 0, 0}, nframes, amt::PlanesOut{band, nullptr, nullptr},
+                                         (long long)frame_bytes, 0, pitch, 0));
+    c->prof_end(sp);
+    return LumaView{band - ((size_t)row0 * pitch + c0) * b.es, (int64_t)frame_bytes, pitch};
+}
+
 // run f(); on any exception keep the message on the context and return 0 (no exceptions cross the ABI)
 template <typename F> inline int guard(AmtGpuContext* c, F&& f, const char* caller = __builtin_FUNCTION())
 {

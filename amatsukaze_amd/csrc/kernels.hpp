@@ -42,6 +42,11 @@ struct EraseGeom {
 };
 hipError_t launch_delogo(hipStream_t st, int bits, const PlaneBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g, int nframes,
                          const float2* dfades, int zero_identity);
+// erase_surface_kernels.hip: the same Delogo on decoder surfaces where they lie (interleaved and / or MSB-aligned; planar LSB surfaces are
+// ordinary planes and go to launch_delogo).  SurfaceBatch is declared below; dst is laid out like src (the same planes for the in-place call)
+struct SurfaceBatch;
+hipError_t launch_delogo_surfaces(hipStream_t st, int bits, const SurfaceBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g,
+                                  int nframes, const float2* dfades, int zero_identity);
 hipError_t launch_calc_fades(hipStream_t st, const float* danalysis, int analysis_first, int analysis_count, int num_frames, int first,
                              int nframes, const uint8_t* dstate, int half, float2* dout);
 // dout[frame] = {valid, bgY, bgU, bgV}

@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #include "kernels.hpp"
+#include "pack16.h"
 
 namespace amt {
 
@@ -40,15 +41,6 @@ struct SurfaceExtractArgs {
     int es, interleaved, shift;            // bytes per sample; chroma as U V pairs; right shift of every 16-bit container
     int pairC;                             // interleaved chroma goes pair by pair (two loads of one sample: vbC = 2 * es is then no load width)
 };
-
-// both 16-bit halves of w shifted right by s
-__device__ __forceinline__ uint32_t pk_shr16(uint32_t w, int s)
-{
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-    us2 v = __builtin_bit_cast(us2, w);
-    v >>= (unsigned short)s;
-    return __builtin_bit_cast(uint32_t, v);
-}
 
 // even / odd bytes (es 1) or half-words (es 2) of the 8 bytes {lo, hi}
 __device__ __forceinline__ uint32_t split_first(uint32_t lo, uint32_t hi, int es)

@@ -42,7 +42,8 @@ extern "C" {
                                    *    (amtgpu_scanlogo_stream_*); ScanLogo for 9..12-bit clips (amtgpu_scanlogo_bits, _sharded_bits,
                                    *    _stream_create_bits, _auto_bits, _auto_sharded_bits; the 'AMTH' raw clip file); decoder surfaces
                                    *    (AmtGpuSurfaces: amtgpu_surfaces_extract_rect, amtgpu_scanlogo_stream_feed_surfaces,
-                                   *    amtgpu_logofind_add_surfaces, amtgpu_weave_fields_batch_msb) */
+                                   *    amtgpu_logofind_add_surfaces, amtgpu_weave_fields_batch_msb; amtgpu_erase_surfaces, _dfades, _dfades_to,
+                                   *    amtgpu_analyze_surfaces, amtgpu_logoframe_scan_surfaces) */
 #define AMTGPU_NUM_FADE 11            /* LogoAnalyzeFrame p/t/b[11]  (LogoScan.hpp:1100-1103) */
 #define AMTGPU_ANALYZE_FLOATS 33      /* floats per source frame in an analysis record */
 
@@ -189,10 +190,14 @@ int   amtgpu_weave_fields_batch_msb(AmtGpuContext* ctx, const void* dsrcY, const
 
 /* ---- decoder surfaces: what a hardware decoder or an FFmpeg hwframe hands out -- NV12 (8-bit Y plane plus one interleaved U0 V0 U1 V1 ...
  *      plane), P010 / P012 (the same layout in 16-bit containers with the sample in the HIGH bits) -- described once and taken as they are
- *      by the entry points that only read a part of the frame: the ScanLogo session (amtgpu_scanlogo_stream_feed_surfaces, the logo
- *      rectangle) and the logo finder (amtgpu_logofind_add_surfaces, the Y plane).  The sample rule is a plain right shift: whatever
- *      sits in the low 16 - bits bits of an MSB-aligned container is discarded (P010 says zero; decoders and dithering filters do not
- *      always leave zero there).  4:2:0 only; linear (untiled, uncompressed) layouts only. ---- */
+ *      by the entry points that only touch a part of the frame: the ScanLogo session (amtgpu_scanlogo_stream_feed_surfaces, the logo
+ *      rectangle), the logo finder (amtgpu_logofind_add_surfaces, the Y plane), the encode-time analysis and the LogoFrame scan
+ *      (amtgpu_analyze_surfaces, amtgpu_logoframe_scan_surfaces: the logos' rows and columns of the Y plane) and the erase
+ *      (amtgpu_erase_surfaces...: the logo rectangle).  The sample rule is a plain right shift: whatever sits in the low 16 - bits bits
+ *      of an MSB-aligned container is discarded (P010 says zero; decoders and dithering filters do not always leave zero there).
+ *      The plane pointers are const because most entry points only read them; the ERASE entry points WRITE the planes the descriptor
+ *      points to (amtgpu_erase_surfaces, amtgpu_erase_surfaces_dfades, and the dst of amtgpu_erase_surfaces_dfades_to): a rewritten
+ *      MSB-aligned container is result << (16 - bits), its low bits zero.  4:2:0 only; linear (untiled, uncompressed) layouts only. ---- */
 typedef struct AmtGpuSurfaces {
     const void* Y;               /* luma plane of the first picture (device) */
     const void* U;               /* planar: U plane.  interleaved: the UV plane (U0 V0 U1 V1 ...) */
@@ -268,6 +273,11 @@ void amtgpu_logoframe_destroy(AmtGpuLogoFrame* lf);
 int  amtgpu_logoframe_begin(AmtGpuLogoFrame* lf, int width, int height, int bits, int num_frames, int fps_num, int fps_den);
 /* scan frames [first, first+nframes) of the clip from a device batch (Y plane only).  async */
 int  amtgpu_logoframe_scan_batch(AmtGpuLogoFrame* lf, const void* dY, int64_t frame_stride, int pitch, int first, int nframes);
+/* amtgpu_logoframe_scan_batch on the Y planes of a batch of surfaces; batch->bits must be the depth given to amtgpu_logoframe_begin.  async
+ * LSB surfaces are read where they lie.  Of MSB-aligned surfaces the band the scan reads (amtgpu_logoframe_get_rows x _get_columns of the
+ * logos that match the clip) is first copied as LSB samples into a scratch buffer the object owns (it grows to the largest batch seen):
+ * the surfaces entry point of one object is therefore NOT re-entrant.  nframes == 0 returns 1 */
+int  amtgpu_logoframe_scan_surfaces(AmtGpuLogoFrame* lf, const AmtGpuSurfaces* batch, int first, int nframes);
 /* results: num_frames*nlogos*{corr0,corr1} (EvalResult, LogoScan.hpp:1532-1535) */
 /* out2 = {first row, one past the last row} of the Y plane that the scan of these logos reads (the union of their rectangles) */
 int  amtgpu_logoframe_get_rows(const AmtGpuLogoFrame* lf, int* out2);
@@ -299,6 +309,11 @@ AmtGpuAnalyze* amtgpu_analyze_create_from_logo(AmtGpuContext* ctx, const AmtGpuL
 void amtgpu_analyze_destroy(AmtGpuAnalyze* an);
 /* dout: device buffer of nframes*33 floats.  async */
 int  amtgpu_analyze_batch(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride, int pitch, int bits, int nframes, float* dout);
+/* amtgpu_analyze_batch on the Y planes of a batch of surfaces (depth = batch->bits); dout: nframes*33 floats on the device.  async
+ * LSB surfaces are read where they lie.  Of MSB-aligned surfaces the rectangle's rows (columns from imgx rounded down to 64 containers)
+ * are first copied as LSB samples into a scratch buffer the object owns (it grows to the largest batch seen): the surfaces entry point of
+ * one object is therefore NOT re-entrant.  nframes == 0 returns 1 */
+int  amtgpu_analyze_surfaces(AmtGpuAnalyze* an, const AmtGpuSurfaces* batch, int nframes, float* dout);
 /* convenience: same, results copied to host (synchronises) */
 /* out4 = {imgx, imgy, w, h}: the rectangle the analysis reads (LogoScan.hpp:1132-1141) -- a host that uploads frames may ship only
  * the rows [imgy, imgy+h) of every Y plane, at their place in the frame: nothing else is read */
@@ -387,6 +402,18 @@ int  amtgpu_erase_rect_batch_dfades(AmtGpuErase* er, void* dY, void* dU, void* d
  * the copy's.  sY == dY (all three) is amtgpu_erase_batch_dfades.  async (ABI 5) */
 int  amtgpu_erase_batch_dfades_to(AmtGpuErase* er, const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV,
                                   int64_t strideY, int64_t strideUV, int pitchY, int pitchUV, int bits, int nframes, const float* d_fades);
+/* Delogo in place on a batch of decoder surfaces; fades: host array nframes*2 / device array.  The planes the descriptor points to ARE WRITTEN.  async
+ * Rewritten: the containers of the logo rectangle (interleaved chroma: containers 2*cx .. 2*(cx + w/2) - 1 of its rows), as
+ * msb_aligned ? result << (16 - bits) : result.  Not rewritten means not touched, low bits included: everything outside the rectangle, an
+ * odd last chroma row in field mode, and frames whose fades are {0, 0} when fade0_is_identity (amtgpu_erase_get_rect) holds and bits is
+ * 8 or 16 or the surfaces are MSB-aligned (an MSB sample never exceeds maxv; LSB 9..15-bit containers are computed, as in
+ * amtgpu_erase_batch).  Refused: a null descriptor, reserved != 0, bad bits, a pitch smaller than the rectangle's rows, mode != 0, null
+ * fades.  nframes == 0 returns 1 and touches nothing */
+int  amtgpu_erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* batch, int nframes, const float* fades);
+int  amtgpu_erase_surfaces_dfades(AmtGpuErase* er, const AmtGpuSurfaces* batch, int nframes, const float* d_fades);
+/* reads src, writes dst, which already holds a copy of the pictures (MakeWritable semantics of amtgpu_erase_batch_dfades_to); dst must equal src in
+ * bits, interleaved, msb_aligned, pitches and strides; src == dst (same planes) is the in-place call */
+int  amtgpu_erase_surfaces_dfades_to(AmtGpuErase* er, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes, const float* d_fades);
 /* out5 = {imgx, imgy, w, h, fade0_is_identity}: the rectangle Delogo rewrites; the last word is 1 when a frame whose two fades
  * are 0 comes back unchanged (every a*s + b*maxv of this logo is finite), i.e. the host may skip the call for such frames --
  * of an 8- or 16-bit clip: at 10 / 12 bits Delogo's min(tmp + 0.5, maxv) (LogoScan.hpp:1258) still clamps container values
