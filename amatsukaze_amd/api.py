@@ -866,6 +866,21 @@ class FrameStats:
         self.ctx.synchronize()
         return out.cpu().numpy().astype(np.uint64)
 
+    def run_device_surfaces(self, surfaces: DeviceSurfaces, out, prev: DeviceSurfaces = None):
+        """the metrics of the Y planes of decoder surfaces (NV12, P010, ...; MSB-aligned ones are read as container >> (16 - bits) inside
+        the kernel); prev: the ONE picture before the batch, of the same depth, alignment and pitch; out: (N, 8) int64 in HBM.  async"""
+        d = surfaces.ref()
+        dp = prev.ref() if prev is not None else None
+        self.ctx.check(self.ctx.lib.amtgpu_framestats_surfaces(self.h, C.byref(d), C.byref(dp) if dp is not None else None, surfaces.num_frames,
+                                                               _p(out)))
+
+    def run_surfaces(self, surfaces: DeviceSurfaces, prev: DeviceSurfaces = None):
+        import torch
+        out = torch.zeros((surfaces.num_frames, 8), dtype=torch.int64, device=surfaces.Y.device)
+        self.run_device_surfaces(surfaces, out, prev)
+        self.ctx.synchronize()
+        return out.cpu().numpy().astype(np.uint64)
+
     def scene_changes(self, metrics):
         m = np.ascontiguousarray(metrics, np.uint64)
         n = m.shape[0]

@@ -162,6 +162,8 @@ SIGNATURES = {
     "amtgpu_framestats_batch": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_i, c_p]),
     "amtgpu_framestats_allgather": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "amtgpu_framestats_sharded": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p, c_i, c_i, c_i, c_p]),
+    "amtgpu_framestats_surfaces": (c_i, [c_p, c_p, c_p, c_i, c_p]),
+    "amtgpu_framestats_sharded_surfaces": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "amtgpu_cm_scene_changes": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_p]),
     "amtgpu_kfm_cadence": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "amtgpu_kfm_write_durations": (c_i, [c_p, c_p, c_i, c_s, c_p]),

@@ -25,6 +25,7 @@ SOURCES = [
     "erase_scan_kernels.hip",
     "erase_surface_kernels.hip",
     "stats_kernels.hip",
+    "stats_msb_kernels.hip",
     "ingest_kernels.hip",
     "amt_gpu_logofind.hip",
     "logofind_kernels.hip",

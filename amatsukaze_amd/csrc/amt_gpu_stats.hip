@@ -38,6 +38,30 @@ void gather_frame_metrics(const AmtGpuCollectives* coll, const uint64_t* local, 
     if (!coll->allgather || coll->rank < 0 || coll->rank >= coll->world) throw std::runtime_error("AmtGpuCollectives incomplete");
     allgather_records(coll, local, first, nlocal, num_frames, rec * sizeof(uint64_t), out, true, local_error, "the frame metrics");
 }
+
+// What the surfaces entry points launch with: the Y planes of a batch of decoder surfaces and of the one picture before it (prev may be
+// null), checked against the object and against each other.  Chroma is never looked at.
+struct StatSurfaces { const void* Y; int64_t strideY; int pitchY; const void* prevY; int shift; };
+StatSurfaces stat_surfaces(const AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch, const AmtGpuSurfaces* prev)
+{
+    const char* who = "[FrameStats]";
+    const SurfaceBatch b = surface_batch(batch, who, true);
+    if (batch->bits != fs->bits) throw std::runtime_error("[FrameStats] surfaces of another depth than the object's");
+    if (b.pitchY < fs->width || b.strideY < 0) throw std::runtime_error("[FrameStats] surface pitchY below the width or negative stride");
+    StatSurfaces s{b.Y, b.strideY, b.pitchY, nullptr, b.shift};
+    if (prev) {
+        const SurfaceBatch p = surface_batch(prev, who, true);
+        if (prev->bits != batch->bits || (prev->msb_aligned != 0) != (batch->msb_aligned != 0) || prev->pitchY != batch->pitchY)
+            throw std::runtime_error("[FrameStats] the previous picture must have the batch's bits, msb_aligned and pitchY");
+        s.prevY = p.Y;
+    }
+    return s;
+}
+hipError_t launch_stat_surfaces(const AmtGpuFrameStats* fs, const StatSurfaces& s, int nframes, unsigned long long* dout)
+{
+    return s.shift ? launch_frame_stats_msb(fs->ctx->stream, fs->bits, s.shift, s.Y, s.strideY, s.pitchY, fs->width, fs->height, s.prevY, nframes, dout)
+                   : launch_frame_stats(fs->ctx->stream, fs->bits, s.Y, s.strideY, s.pitchY, fs->width, fs->height, s.prevY, nframes, dout);
+}
 } // namespace
 
 extern "C" {
@@ -88,6 +112,46 @@ int amtgpu_framestats_sharded(AmtGpuFrameStats* fs, const AmtGpuCollectives* col
                 const int sp = fs->ctx->prof_begin("frame_stats_kernel");
                 AMT_HIP(launch_frame_stats(fs->ctx->stream, fs->bits, dY, frame_stride, pitch, fs->width, fs->height, first > 0 ? dprevY : nullptr,
                                            nlocal, fs->dShard.get()));
+                fs->ctx->prof_end(sp);
+                local.resize(n);
+                download_via_pinned(fs->ctx, local.data(), fs->dShard.get(), n * sizeof(uint64_t));
+            }
+        } catch (const std::exception& e) { err = e.what(); }
+        gather_frame_metrics(coll, local.data(), first, nlocal, num_frames, metrics_out, err);
+    });
+}
+
+int amtgpu_framestats_surfaces(AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch, const AmtGpuSurfaces* prev, int nframes, uint64_t* dout)
+{
+    return guard(fs->ctx, [&] {
+        if (nframes < 0) throw std::runtime_error("[FrameStats] negative frame count");
+        if (nframes == 0) return;
+        const StatSurfaces s = stat_surfaces(fs, batch, prev);
+        if (!dout) throw std::runtime_error("[FrameStats] null metrics pointer");
+        fs->ctx->bind();
+        const int sp = fs->ctx->prof_begin("frame_stats_kernel");
+        AMT_HIP(launch_stat_surfaces(fs, s, nframes, (unsigned long long*)dout));
+        fs->ctx->prof_end(sp);
+    });
+}
+
+int amtgpu_framestats_sharded_surfaces(AmtGpuFrameStats* fs, const AmtGpuCollectives* coll, const AmtGpuSurfaces* batch,
+                                       const AmtGpuSurfaces* prev, int first, int nlocal, int num_frames, uint64_t* metrics_out)
+{
+    return guard(fs->ctx, [&] {
+        std::string err;
+        std::vector<uint64_t> local;
+        try {
+            if (first < 0 || nlocal < 0 || (long long)first + nlocal > num_frames) throw std::runtime_error("frame range outside the clip");
+            // the first frame of a shard is compared with the frame before it: only the shard that starts the clip has none
+            if (first > 0 && nlocal > 0 && !prev) throw std::runtime_error("[FrameStats] a shard that does not start the clip needs the picture before it (prev)");
+            if (nlocal > 0) {
+                const StatSurfaces s = stat_surfaces(fs, batch, first > 0 ? prev : nullptr);
+                fs->ctx->bind();
+                const size_t n = (size_t)nlocal * AMTGPU_FS_WORDS;
+                if (fs->dShard.size() < n) fs->dShard.alloc(n);
+                const int sp = fs->ctx->prof_begin("frame_stats_kernel");
+                AMT_HIP(launch_stat_surfaces(fs, s, nlocal, fs->dShard.get()));
                 fs->ctx->prof_end(sp);
                 local.resize(n);
                 download_via_pinned(fs->ctx, local.data(), fs->dShard.get(), n * sizeof(uint64_t));

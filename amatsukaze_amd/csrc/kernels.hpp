@@ -91,6 +91,10 @@ hipError_t launch_ingest_rows(hipStream_t st, const void* src, long long src_str
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,
                               const void* dprevY, int nframes, unsigned long long* dout);
+// stats_msb_kernels.hip: the same metrics of container >> shift (16-bit containers; bits = the depth of the shifted samples, 9..15;
+// shift = 16 - bits); the kernel form is chosen by the rules of launch_frame_stats
+hipError_t launch_frame_stats_msb(hipStream_t st, int bits, int shift, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,
+                                  const void* dprevY, int nframes, unsigned long long* dout);
 // Largest frame count of one launch_logofind: its uint32 partials hold at most 2 * maxv per frame (SM) below 2^31.
 long long logofind_launch_cap(int bits);
 // nframes <= logofind_launch_cap(bits) (the caller splits); dS1 / dSM: W*H int64 each, added to

@@ -150,6 +150,19 @@ def framestats_sharded(fs, Y, first: int, num_frames: int, coll: TorchCollective
     return out
 
 
+def framestats_sharded_surfaces(fs, surfaces, first: int, num_frames: int, coll: TorchCollectives, prev=None):
+    """amtgpu_framestats_sharded_surfaces: framestats_sharded on decoder surfaces (api.DeviceSurfaces: this rank's pictures [first, first + n)
+    as they lie, prev = the one picture before them; None on the rank that starts the clip)."""
+    from .api import _p
+    out = np.zeros((num_frames, 8), np.uint64)
+    d = surfaces.ref()
+    dp = prev.ref() if prev is not None else None
+    fs.ctx.check(fs.ctx.lib.amtgpu_framestats_sharded_surfaces(fs.h, coll.ref() if coll is not None else None, C.byref(d),
+                                                               C.byref(dp) if dp is not None else None, first, surfaces.num_frames, num_frames,
+                                                               _p(out)))
+    return out
+
+
 def scan_logo_sharded(ctx, clip_local, serviceid, dstpath, imgx, imgy, w, h, thy, numMaxFrames, coll: TorchCollectives, cb=None):
     """ScanLogo (LogoScan.hpp:1083-1098) over a stream whose frames are sharded by contiguous range: clip_local holds this
     rank's frames (clip_local.bits deep, the same on every rank).  Rank 0 writes dstpath; returns True/False like the reference's export."""

@@ -43,7 +43,8 @@ extern "C" {
                                    *    _stream_create_bits, _auto_bits, _auto_sharded_bits; the 'AMTH' raw clip file); decoder surfaces
                                    *    (AmtGpuSurfaces: amtgpu_surfaces_extract_rect, amtgpu_scanlogo_stream_feed_surfaces,
                                    *    amtgpu_logofind_add_surfaces, amtgpu_weave_fields_batch_msb; amtgpu_erase_surfaces, _dfades, _dfades_to,
-                                   *    amtgpu_analyze_surfaces, amtgpu_logoframe_scan_surfaces) */
+                                   *    amtgpu_analyze_surfaces, amtgpu_logoframe_scan_surfaces, amtgpu_framestats_surfaces,
+                                   *    amtgpu_framestats_sharded_surfaces) */
 #define AMTGPU_NUM_FADE 11            /* LogoAnalyzeFrame p/t/b[11]  (LogoScan.hpp:1100-1103) */
 #define AMTGPU_ANALYZE_FLOATS 33      /* floats per source frame in an analysis record */
 
@@ -190,10 +191,11 @@ int   amtgpu_weave_fields_batch_msb(AmtGpuContext* ctx, const void* dsrcY, const
 
 /* ---- decoder surfaces: what a hardware decoder or an FFmpeg hwframe hands out -- NV12 (8-bit Y plane plus one interleaved U0 V0 U1 V1 ...
  *      plane), P010 / P012 (the same layout in 16-bit containers with the sample in the HIGH bits) -- described once and taken as they are
- *      by the entry points that only touch a part of the frame: the ScanLogo session (amtgpu_scanlogo_stream_feed_surfaces, the logo
+ *      by every pass that reads frames in HBM: the ScanLogo session (amtgpu_scanlogo_stream_feed_surfaces, the logo
  *      rectangle), the logo finder (amtgpu_logofind_add_surfaces, the Y plane), the encode-time analysis and the LogoFrame scan
- *      (amtgpu_analyze_surfaces, amtgpu_logoframe_scan_surfaces: the logos' rows and columns of the Y plane) and the erase
- *      (amtgpu_erase_surfaces...: the logo rectangle).  The sample rule is a plain right shift: whatever sits in the low 16 - bits bits
+ *      (amtgpu_analyze_surfaces, amtgpu_logoframe_scan_surfaces: the logos' rows and columns of the Y plane), the erase
+ *      (amtgpu_erase_surfaces...: the logo rectangle) and the frame metrics (amtgpu_framestats_surfaces, _sharded_surfaces: the whole Y
+ *      plane).  The sample rule is a plain right shift: whatever sits in the low 16 - bits bits
  *      of an MSB-aligned container is discarded (P010 says zero; decoders and dithering filters do not always leave zero there).
  *      The plane pointers are const because most entry points only read them; the ERASE entry points WRITE the planes the descriptor
  *      points to (amtgpu_erase_surfaces, amtgpu_erase_surfaces_dfades, and the dst of amtgpu_erase_surfaces_dfades_to): a rewritten
@@ -591,6 +593,17 @@ int  amtgpu_framestats_allgather(AmtGpuFrameStats* fs, const AmtGpuCollectives* 
  * NULL on the rank that holds frame 0), then the exchange.  Synchronises. */
 int  amtgpu_framestats_sharded(AmtGpuFrameStats* fs, const AmtGpuCollectives* coll, const void* dY, int64_t frame_stride, int pitch,
                                const void* dprevY, int first, int nlocal, int num_frames, uint64_t* metrics_out);
+/* amtgpu_framestats_batch / _sharded on decoder surfaces (AmtGpuSurfaces above: NV12, P010 / P012, planar LSB or MSB).  Only Y, strideY,
+ * pitchY, bits and msb_aligned of a descriptor are read: the chroma layout and pointers are ignored.  batch->bits must be the depth the
+ * object was created with (8..15: 16-bit surfaces have no metrics).  MSB-aligned containers are read as container >> (16 - bits) inside the
+ * kernel, before any arithmetic -- the records are those of the planar LSB clip, whatever sits in the low bits.  prev describes the ONE
+ * picture before the batch (its Y plane; same bits, msb_aligned and pitchY as the batch), NULL -> frame 0 compares with itself.
+ * nframes == 0 returns 1 and writes nothing; negative nframes returns 0.  async */
+int  amtgpu_framestats_surfaces(AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch, const AmtGpuSurfaces* prev, int nframes, uint64_t* dout);
+/* amtgpu_framestats_sharded with the shard and the picture before it (a shard that does not start the clip needs prev) as surfaces.
+ * Synchronises; a rank-local failure travels through the exchange and all ranks return 0 together. */
+int  amtgpu_framestats_sharded_surfaces(AmtGpuFrameStats* fs, const AmtGpuCollectives* coll, const AmtGpuSurfaces* batch,
+                                        const AmtGpuSurfaces* prev, int first, int nlocal, int num_frames, uint64_t* metrics_out);
 /* host decisions from the metrics of a whole clip (nframes*8 uint64, host): scene-change list in
  * chapter_exe's "SCPos:" sense and per-frame cadence class 0=30i/60p 1=24p(3:2) 2=30p + 3:2 phase.
  * sc_out: up to cap frame numbers, returns count via *nsc.  cadence_out: nframes bytes, phase_out: nframes bytes */
