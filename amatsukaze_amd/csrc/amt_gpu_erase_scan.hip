@@ -142,9 +142,10 @@ static const float2* erase_fades(AmtGpuErase* er, int nframes, const float* fade
     return er->dFades[slot].get();
 }
 
-// Delogo of a batch that has passed erase_wanted: reads src, writes dst (the same planes for the in-place calls)
-static void erase_launch(AmtGpuErase* er, const PlaneBatch& src, const PlanesOut& dst, int bits, int nframes, const float* fades, bool rect_only,
-                         const float* d_fades = nullptr)
+// Delogo of a batch that has passed erase_wanted: reads src, writes dst (laid out like src; the same planes for the in-place calls).
+// rect_only: the planes hold the logo's rectangle and nothing else.  `span`: the profile span the call records, whichever kernel runs
+static void erase_run(AmtGpuErase* er, const char* span, int bits, const SurfaceBatch& src, const PlanesOut& dst, bool rect_only, int nframes,
+                      const float* fades, const float* d_fades)
 {
     const LogoPlanes& P = er->logo;
     if (rect_only && (src.pitchY < P.w || src.pitchUV < P.wUV())) throw std::runtime_error("[AMTEraseLogo] rectangle pitch smaller than the logo width");
@@ -157,31 +158,39 @@ static void erase_launch(AmtGpuErase* er, const PlaneBatch& src, const PlanesOut
     g.imgx = rect_only ? 0 : P.imgx; g.imgy = rect_only ? 0 : P.imgy;
     g.cx = rect_only ? 0 : P.imgx >> P.logUVx; g.cy = rect_only ? 0 : P.imgy >> P.logUVy;
     g.uvparity = (P.imgy / 2) % 2;
-    const int sp = er->ctx->prof_begin("delogo_kernel");
-    // fade 0 returns a sample unchanged only while the sample is <= maxv: min(tmp + 0.5, maxv) (LogoScan.hpp:1258) clamps a 10- or
-    // 12-bit clip's out-of-range container values.  At 8 and 16 bits every container value is in range: only there are fade-0
-    // frames skipped.
-    const bool skip_fade0 = er->zeroIdentity && (bits == 8 || bits == 16);
-    AMT_HIP(launch_delogo(er->ctx->stream, bits, src, dst, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
+    const int sp = er->ctx->prof_begin(span);
+    // fade 0 returns a sample unchanged only while the sample is <= maxv: min(tmp + 0.5, maxv) (LogoScan.hpp:1258) clamps the out-of-range
+    // container values of a 9..15-bit LSB clip.  At 8 and 16 bits every container value is in range, and an MSB sample
+    // (container >> (16 - bits)) can never exceed maxv: only there are fade-0 frames skipped.
+    const bool skip_fade0 = er->zeroIdentity && (bits == 8 || bits == 16 || src.shift != 0);
+    // planar LSB batches are delogo_kernel's, every other layout delogo_surfaces_kernel's
+    if (!src.interleaved && !src.shift)
+        AMT_HIP(launch_delogo(er->ctx->stream, bits, PlaneBatch{src.Y, src.U, src.V, src.strideY / src.es, src.strideUV / src.es, src.pitchY, src.pitchUV},
+                              dst, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
+    else
+        AMT_HIP(launch_delogo_surfaces(er->ctx->stream, bits, src, dst, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
     er->ctx->prof_end(sp);
+}
+
+// the five entry points that take planes: in place when the source planes are the destination's
+static void erase_planes(AmtGpuErase* er, const void* sY, const void* sU, const void* sV, void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV,
+                         int pitchY, int pitchUV, int bits, int nframes, const float* fades, const float* d_fades, bool rect_only)
+{
+    if (!erase_wanted(er, bits, nframes)) return;
+    const SurfaceBatch src = planar_surfaces(plane_batch(bits, sY, sU, sV, strideY, strideUV, pitchY, pitchUV), sample_bytes(bits));
+    erase_run(er, "delogo_kernel", bits, src, PlanesOut{dY, dU, dV}, rect_only, nframes, fades, d_fades);
 }
 
 int amtgpu_erase_batch(AmtGpuErase* er, void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY,
                        int pitchUV, int bits, int nframes, const float* fades)
 {
-    return guard(er->ctx, [&] {
-        if (erase_wanted(er, bits, nframes))
-            erase_launch(er, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, fades, false);
-    });
+    return guard(er->ctx, [&] { erase_planes(er, dY, dU, dV, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, fades, nullptr, false); });
 }
 
 int amtgpu_erase_rect_batch(AmtGpuErase* er, void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY,
                             int pitchUV, int bits, int nframes, const float* fades)
 {
-    return guard(er->ctx, [&] {
-        if (erase_wanted(er, bits, nframes))
-            erase_launch(er, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, fades, true);
-    });
+    return guard(er->ctx, [&] { erase_planes(er, dY, dU, dV, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, fades, nullptr, true); });
 }
 
 int amtgpu_erase_batch_dfades(AmtGpuErase* er, void* dY, void* dU, void* dV, int64_t strideY, int64_t strideUV, int pitchY,
@@ -189,8 +198,7 @@ int amtgpu_erase_batch_dfades(AmtGpuErase* er, void* dY, void* dU, void* dV, int
 {
     return guard(er->ctx, [&] {
         if (!d_fades && nframes > 0) throw std::runtime_error("[AMTEraseLogo] null device fades");
-        if (erase_wanted(er, bits, nframes))
-            erase_launch(er, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, nullptr, false, d_fades);
+        erase_planes(er, dY, dU, dV, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, nullptr, d_fades, false);
     });
 }
 
@@ -199,8 +207,7 @@ int amtgpu_erase_rect_batch_dfades(AmtGpuErase* er, void* dY, void* dU, void* dV
 {
     return guard(er->ctx, [&] {
         if (!d_fades && nframes > 0) throw std::runtime_error("[AMTEraseLogo] null device fades");
-        if (erase_wanted(er, bits, nframes))
-            erase_launch(er, plane_batch(bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, nullptr, true, d_fades);
+        erase_planes(er, dY, dU, dV, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, nullptr, d_fades, true);
     });
 }
 
@@ -210,13 +217,11 @@ int amtgpu_erase_batch_dfades_to(AmtGpuErase* er, const void* sY, const void* sU
     return guard(er->ctx, [&] {
         if (!d_fades && nframes > 0) throw std::runtime_error("[AMTEraseLogo] null device fades");
         if (nframes > 0 && (!sY || !sU || !sV || !dY || !dU || !dV)) throw std::runtime_error("[AMTEraseLogo] null plane");
-        if (erase_wanted(er, bits, nframes))
-            erase_launch(er, plane_batch(bits, sY, sU, sV, strideY, strideUV, pitchY, pitchUV), PlanesOut{dY, dU, dV}, bits, nframes, nullptr, false, d_fades);
+        erase_planes(er, sY, sU, sV, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, bits, nframes, nullptr, d_fades, false);
     });
 }
 
-// Delogo on decoder surfaces where they lie: src is read, dst (laid out like src; the same descriptor for the in-place calls) is written.
-// Planar LSB surfaces are ordinary planes and take erase_launch; every other layout takes delogo_surfaces_kernel.
+// Delogo on decoder surfaces where they lie: src is read, dst (laid out like src; the same descriptor for the in-place calls) is written
 static void erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes, const float* fades, const float* d_fades,
                            bool device_fades)
 {
@@ -229,12 +234,8 @@ static void erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* src, const Amt
     if (!erase_wanted(er, bits, nframes)) return;
     if (device_fades ? !d_fades : !fades) refuse(device_fades ? "null device fades" : "null fades");
     const LogoPlanes& P = er->logo;
-    EraseGeom g;
-    g.w = P.w; g.h = P.h; g.wUV = P.wUV(); g.hUV = P.hUV();
-    g.imgx = P.imgx; g.imgy = P.imgy; g.cx = P.imgx >> P.logUVx; g.cy = P.imgy >> P.logUVy;
-    g.uvparity = (P.imgy / 2) % 2;
-    if (b.pitchY < g.imgx + g.w) refuse("surface pitchY smaller than the rectangle's rows");
-    if (b.pitchUV < (b.interleaved ? 2 : 1) * (g.cx + g.wUV)) refuse("surface pitchUV smaller than the rectangle's rows");
+    if (b.pitchY < P.imgx + P.w) refuse("surface pitchY smaller than the rectangle's rows");
+    if (b.pitchUV < (b.interleaved ? 2 : 1) * ((P.imgx >> P.logUVx) + P.wUV())) refuse("surface pitchUV smaller than the rectangle's rows");
     PlanesOut out{const_cast<void*>(b.Y), const_cast<void*>(b.U), const_cast<void*>(b.V)};
     if (dst != src) {
         const SurfaceBatch d = surface_batch(dst, who);
@@ -243,18 +244,8 @@ static void erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* src, const Amt
             refuse("destination surfaces differ from the source's in bits, interleaved, msb_aligned, pitches or strides");
         out = PlanesOut{const_cast<void*>(d.Y), const_cast<void*>(d.U), const_cast<void*>(d.V)};
     }
-    if (!b.interleaved && !b.shift) {
-        erase_launch(er, PlaneBatch{b.Y, b.U, b.V, b.strideY / b.es, b.strideUV / b.es, b.pitchY, b.pitchUV}, out, bits, nframes, fades, false, d_fades);
-        return;
-    }
-    er->ctx->bind();
-    const float2* dfades = erase_fades(er, nframes, fades, d_fades);
-    const int sp = er->ctx->prof_begin("delogo_surfaces_kernel");
-    // fade 0 is the identity on every sample <= maxv; an MSB sample (container >> (16 - bits)) can never exceed it, an LSB container of a
-    // 9..15-bit surface can (erase_launch's rule)
-    const bool skip_fade0 = er->zeroIdentity && (bits == 8 || bits == 16 || b.shift != 0);
-    AMT_HIP(launch_delogo_surfaces(er->ctx->stream, bits, b, out, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
-    er->ctx->prof_end(sp);
+    // (a planar LSB descriptor is an ordinary plane batch and records what the plane calls record)
+    erase_run(er, !b.interleaved && !b.shift ? "delogo_kernel" : "delogo_surfaces_kernel", bits, b, out, false, nframes, fades, d_fades);
 }
 
 int amtgpu_erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* batch, int nframes, const float* fades)

@@ -9,6 +9,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "delogo_body.h"
 #include "exact_math.h"
 #include "kernels.hpp"
 
@@ -56,14 +57,6 @@ template <> struct PixQuad<uint16_t> {
 template <typename pix_t> struct PixPair;
 template <> struct PixPair<uint8_t> { typedef uint16_t type; };
 template <> struct PixPair<uint16_t> { typedef uint32_t type; };
-
-__device__ __forceinline__ float delogo_px(float s, float a, float b, float maxv, float fade)
-{
-    const float bg = unblend_bg(a, b, maxv, s);
-    const float t = fade_mix(fade, bg, s) + 0.5f;
-    const float lo = (t < 0.0f) ? 0.0f : t;            // std::max(t, 0.0f)
-    return (maxv < lo) ? maxv : lo;                    // std::min(lo, maxv)
-}
 
 template <typename pix_t>
 __global__ __launch_bounds__(kDelogoThreads)

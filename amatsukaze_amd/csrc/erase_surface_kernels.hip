@@ -5,7 +5,9 @@
 // (shift = 16 - bits for MSB-aligned input, else 0), container = result << shift on the way out (the low bits of a rewritten MSB
 // container are zero, which is what P010 specifies), and an interleaved chroma row U0 V0 U1 V1 ... is one run of 2 * wUV containers
 // whose even members take the U coefficients and whose odd members take the V coefficients -- a frame has h + hUV rows of work
-// instead of h + 2 * hUV.  Planar LSB surfaces are ordinary planes and go to delogo_kernel: there is no instantiation for them here.
+// instead of h + 2 * hUV.  Planar LSB surfaces are ordinary planes and go to delogo_kernel: the launcher refuses them.  (This kernel
+// computes them correctly -- interleaved = 0, shift = 0 -- but on a batch that fills the device its one-row-per-wave shape is 37-68 %
+// slower than delogo_kernel's: DESIGN.md section 4, profiles/delogo_unify.json.)  Both share delogo_body.h.
 //
 // Shaped like delogo_kernel: one workgroup = kSurfRows consecutive rectangle rows x up to kSurfFrames consecutive frames, the row's logo
 // coefficients (8 B per sample against 2 * es B of frame traffic) loaded once per group and kept in registers, all live frames' loads
@@ -20,80 +22,14 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#include "exact_math.h"
+#include "delogo_body.h"
 #include "kernels.hpp"
-#include "pack16.h"
 
 namespace amt {
 
 constexpr int kSurfRows = 16;          // rectangle rows per workgroup (delogo_kernel's shape)
 constexpr int kSurfThreads = 64 * kSurfRows;      // a wave per row
 constexpr int kSurfFrames = 8;         // frames a workgroup walks through with the row's coefficients in registers
-
-// N adjacent containers as one access: get = their samples, pack = the containers of N results
-template <typename C, int N> struct Run;
-template <> struct Run<uint8_t, 4> {
-    typedef uint32_t type;
-    static __device__ __forceinline__ void get(type v, int, float (&s)[4])
-    {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] = (float)((v >> (8 * k)) & 0xFFu);
-    }
-    static __device__ __forceinline__ type pack(const float (&r)[4], int)
-    {
-        return (uint32_t)(uint8_t)r[0] | ((uint32_t)(uint8_t)r[1] << 8) | ((uint32_t)(uint8_t)r[2] << 16) | ((uint32_t)(uint8_t)r[3] << 24);
-    }
-};
-template <> struct Run<uint8_t, 2> {
-    typedef uint16_t type;
-    static __device__ __forceinline__ void get(type v, int, float (&s)[2]) { s[0] = (float)(uint8_t)v; s[1] = (float)(uint8_t)(v >> 8); }
-    static __device__ __forceinline__ type pack(const float (&r)[2], int) { return (uint16_t)((uint16_t)(uint8_t)r[0] | ((uint16_t)(uint8_t)r[1] << 8)); }
-};
-template <> struct Run<uint8_t, 1> {
-    typedef uint8_t type;
-    static __device__ __forceinline__ void get(type v, int, float (&s)[1]) { s[0] = (float)v; }
-    static __device__ __forceinline__ type pack(const float (&r)[1], int) { return (uint8_t)r[0]; }
-};
-template <> struct Run<uint16_t, 4> {
-    typedef uint2 type;
-    static __device__ __forceinline__ void get(type v, int shift, float (&s)[4])
-    {
-        const uint32_t lo = pk_shr16(v.x, shift), hi = pk_shr16(v.y, shift);
-        s[0] = (float)(lo & 0xFFFFu); s[1] = (float)(lo >> 16); s[2] = (float)(hi & 0xFFFFu); s[3] = (float)(hi >> 16);
-    }
-    static __device__ __forceinline__ type pack(const float (&r)[4], int shift)
-    {
-        return make_uint2(pk_shl16((uint32_t)(uint16_t)r[0] | ((uint32_t)(uint16_t)r[1] << 16), shift),
-                          pk_shl16((uint32_t)(uint16_t)r[2] | ((uint32_t)(uint16_t)r[3] << 16), shift));
-    }
-};
-template <> struct Run<uint16_t, 2> {
-    typedef uint32_t type;
-    static __device__ __forceinline__ void get(type v, int shift, float (&s)[2])
-    {
-        const uint32_t w = pk_shr16(v, shift);
-        s[0] = (float)(w & 0xFFFFu); s[1] = (float)(w >> 16);
-    }
-    static __device__ __forceinline__ type pack(const float (&r)[2], int shift)
-    {
-        return pk_shl16((uint32_t)(uint16_t)r[0] | ((uint32_t)(uint16_t)r[1] << 16), shift);
-    }
-};
-template <> struct Run<uint16_t, 1> {
-    typedef uint16_t type;
-    static __device__ __forceinline__ void get(type v, int shift, float (&s)[1]) { s[0] = (float)(uint16_t)(v >> shift); }
-    static __device__ __forceinline__ type pack(const float (&r)[1], int shift) { return (uint16_t)((uint16_t)r[0] << shift); }
-};
-
-// AMTEraseLogo::Delogo's arithmetic for one sample (LogoScan.hpp:1253-1259): delogo_px of erase_scan_kernels.hip, restated here because
-// that file keeps its text (and delogo_kernel its instruction stream) untouched
-__device__ __forceinline__ float delogo_surface_px(float s, float a, float b, float maxv, float fade)
-{
-    const float bg = unblend_bg(a, b, maxv, s);
-    const float t = fade_mix(fade, bg, s) + 0.5f;
-    const float lo = (t < 0.0f) ? 0.0f : t;            // std::max(t, 0.0f)
-    return (maxv < lo) ? maxv : lo;                    // std::min(lo, maxv)
-}
 
 // the coefficients of containers c .. c + N - 1 of a row.  Plain rows (luma, planar chroma): A[c + k] and B[c + k] = A[boff + c + k].
 // Interleaved chroma (il): container 2x takes U's (A[x], B[x]) and container 2x + 1 takes V's, voff floats behind U's
@@ -150,7 +86,7 @@ __device__ __forceinline__ void delogo_surface_row(const C* srow, C* row, long l
             float s[N], r[N];
             R::get(v[k], shift, s);
 #pragma unroll
-            for (int j = 0; j < N; ++j) r[j] = delogo_surface_px(s[j], a[j], b[j], maxv, fd[k]);
+            for (int j = 0; j < N; ++j) r[j] = delogo_px(s[j], a[j], b[j], maxv, fd[k]);
             *reinterpret_cast<run_t*>(row + (long long)k * stride + c) = R::pack(r, shift);
         }
     }

@@ -64,6 +64,11 @@ hipError_t launch_scan_keep(hipStream_t st, int es, const PlaneBatch& b, const S
 // A batch of decoder surfaces (AmtGpuSurfaces, amt_gpu.h) that has passed surface_batch (api_common.hpp): strides in bytes, pitches in
 // containers of es bytes; interleaved: U is the U0 V0 U1 V1 ... plane and V unused; sample = container >> shift (0 for LSB input)
 struct SurfaceBatch { const void *Y, *U, *V; long long strideY, strideUV; int pitchY, pitchUV; int es, interleaved, shift; };
+// a planar LSB PlaneBatch of es-byte samples as the surfaces it is
+inline SurfaceBatch planar_surfaces(const PlaneBatch& b, int es)
+{
+    return SurfaceBatch{b.Y, b.U, b.V, b.strideY * es, b.strideUV * es, b.pitchY, b.pitchUV, es, 0, 0};
+}
 // the rectangle r of all nframes surfaces as planar LSB samples: w x h luma at dst.Y, wUV x hUV chroma at dst.U / dst.V per frame (strides
 // in bytes, pitches in samples).  Plane bases are multiples of es.  One launch
 hipError_t launch_surfaces_extract(hipStream_t st, const SurfaceBatch& s, const ScanRect& r, int nframes, const PlanesOut& dst, long long dstrideY,

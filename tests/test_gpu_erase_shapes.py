@@ -22,6 +22,7 @@ LOGOS = {
     "98x50_y16": (352, 240, 98, 50, 224, 16, 32, 16, 0),                     #   (the other chroma field parity)
     "100x34_y16": (352, 240, 100, 34, 224, 16, 32, 16, 0),                   # quad               paired (50 wide, 17 rows)
     "100x34_y18": (352, 240, 100, 34, 224, 18, 32, 16, 0),
+    "100x34_x226": (352, 240, 100, 34, 226, 16, 32, 16, 0),                  # quad, rows 2 (mod 4)  single (origin 113)
     "520x18": (720, 480, 520, 18, 160, 64, 0, 0, 0),                         # quad, 3 trips      quad (260), 2 trips
     "262x34": (720, 480, 262, 34, 64, 32, 32, 16, 0),                        # paired, 3 trips    single (131), 3 trips
     "96x48_odd_luma_pitch": (352, 240, 96, 48, 224, 18, 33, 16, 0),          # single, 2 trips    quad
