@@ -108,6 +108,24 @@ __device__ __forceinline__ unsigned wave_sum_to_lane63(unsigned v)
     return v;
 }
 
+// Which workgroup of a frame run's order workgroup `block` of `gx` is (the XCD-aware tile order, see the kernel), and the (tile, lane
+// column) of thread `gid` of that order: the kernel's map, as functions so that a host test can replay it (tests/cpp/stats_spans_replay.cpp).
+// (tried and not kept, profiles/stats_spans_notes.md: tile rows cut into 64-column spans of one wave each with the remainders packed
+// into waves of their own -- wave boundaries on 1 024-byte multiples, fewer duplicated line fetches, the same time)
+struct StatLane { int tile, col; };
+__host__ __device__ __forceinline__ int stat_workgroup(unsigned gx, unsigned block)
+{
+    const unsigned per = gx / kStatXcds;
+    return (int)((block % kStatXcds) * per + block / kStatXcds);
+}
+__host__ __device__ __forceinline__ StatLane stat_lane(int cols, int gid)
+{
+    StatLane r;
+    r.tile = gid / cols;
+    r.col = gid - r.tile * cols;
+    return r;
+}
+
 #ifdef AMT_STATS_WAVES
 #define AMT_STATS_OCC __attribute__((amdgpu_waves_per_eu(AMT_STATS_WAVES, AMT_STATS_WAVES)))
 #else
@@ -138,11 +156,10 @@ void frame_stats_kernel(const uint8_t* __restrict__ Y, long long frame_stride /*
     // CONTIGUOUS tile groups [k*per, (k+1)*per) makes vertically adjacent tiles -- which share their two halo rows --
     // neighbours on one XCD, running at the same time: the halo re-read is an L2 hit there instead of a second HBM fetch
     // (each XCD has a private L2; adjacent blockIdx.x would put every halo on a different one).
-    const int per = gridDim.x / kStatXcds;
-    const int wg = (blockIdx.x % kStatXcds) * per + blockIdx.x / kStatXcds;
-    const int gid = wg * kStatThreads + threadIdx.x;
-    const int tile = gid / cols;
-    const int xb = (gid - tile * cols) * kStatColBytes;           // byte column of this thread
+    const int wg = stat_workgroup(gridDim.x, blockIdx.x);
+    const StatLane sl = stat_lane(cols, wg * kStatThreads + (int)threadIdx.x);
+    const int tile = sl.tile;
+    const int xb = sl.col * kStatColBytes;           // byte column of this thread
     const int y0 = tile * TR;
     const int nvalid = y0 < H ? min(kStatColBytes, row_bytes - xb) : 0;      // <= 0: thread has no pixels
     const int n0 = blockIdx.y * kStatRun;
@@ -207,7 +224,7 @@ void frame_stats_kernel(const uint8_t* __restrict__ Y, long long frame_stride /*
         return a;
     };
 
-    // one frame of this thread's tile against the frame before it; wave reduction, one atomic per word per wave.  ve_prev: vert_even
+    // one frame of this thread's tile against the frame before it; wave reduction, one atomic per wave.  ve_prev: vert_even
     // of the frame before; returns vert_even of this frame
     auto compute = [&](const Chunk* cur, const Chunk* prev, int n, unsigned ve_prev) {
         unsigned acc[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -235,11 +252,16 @@ void frame_stats_kernel(const uint8_t* __restrict__ Y, long long frame_stride /*
         acc[6] = vo + ve_prev;           // VERT of the weave: odd rows look at this frame's neighbours, even rows at the previous frame's
 #pragma unroll
         for (int k = 0; k < 7; ++k) acc[k] = wave_sum_to_lane63(acc[k]);
-        if ((threadIdx.x & 63) == 63) {
+        // the seven totals out of lane 63 into lanes 0..6, which add them to the frame's record with ONE instruction: the record is 64
+        // bytes, and every wave-instruction of a global atomic leaves the L2 as a request of its own
+        const unsigned lane = threadIdx.x & 63;
+        unsigned mine = 0;
 #pragma unroll
-            for (int k = 0; k < 7; ++k)
-                if (acc[k]) atomicAdd(&out[(long long)n * kStatWords + k], (unsigned long long)acc[k]);
+        for (int k = 0; k < 7; ++k) {
+            const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)acc[k], 63);
+            mine = lane == (unsigned)k ? total : mine;
         }
+        if (lane < 7) atomicAdd(&out[(long long)n * kStatWords + lane], (unsigned long long)mine);
         return ve;
     };
     const uint8_t* const before = n0 > 0 ? Y + (long long)(n0 - 1) * frame_stride : (prevY ? prevY : Y);
