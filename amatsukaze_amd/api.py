@@ -222,6 +222,7 @@ class AmtsFile:
             "decoderMpeg2", "decoderH264", "decoderHevc")
 
     def __init__(self, path, ctx: "Context" = None):
+        self.ctx = ctx
         self.lib = ctx.lib if ctx else binding.load()
         self.h = self.lib.amtgpu_amts_load(ctx.h if ctx else None, str(path).encode())
         if not self.h:
@@ -257,6 +258,29 @@ class AmtsFile:
         if not self.lib.amtgpu_amts_weave_plan(self.h, _p(pts), len(pts), _p(top), _p(bot)):
             raise AmtError("amtgpu_amts_weave_plan failed")
         return top, bot
+
+    def _fail(self, what):
+        return AmtError(what + (": " + self.lib.amtgpu_last_error(self.ctx.h).decode(errors="replace") if self.ctx else ""))
+
+    def audio_info(self):
+        """(samples_per_frame, num_samples) of the 16-bit stereo timeline AMTSource presents (MakeVideoInfo): (0, 0) without audio frames"""
+        spf, ns = C.c_int(), C.c_int64()
+        self.lib.amtgpu_amts_audio_info(self.h, C.byref(spf), C.byref(ns))
+        return spf.value, ns.value
+
+    def audio_frames(self):
+        n = self.num_audio_frames
+        out = dict(frameIndex=np.zeros(n, np.int32), waveOffset=np.zeros(n, np.int64), waveLength=np.zeros(n, np.int32))
+        self.lib.amtgpu_amts_get_audio_frames(self.h, _p(out["frameIndex"]), _p(out["waveOffset"]), _p(out["waveLength"]))
+        return out
+
+    def read_audio(self, start, count, wavepath=None):
+        """AMTSource::GetAudio: `count` sample-frames from `start` on as a (count, 2) int16 array, read from wavepath (None: the file's
+        own audiopath); zeros for audio frames without a wave and behind the last audio frame"""
+        out = np.zeros((max(0, int(count)), 2), np.int16)
+        if not self.lib.amtgpu_amts_read_audio(self.h, str(wavepath).encode() if wavepath is not None else None, int(start), int(count), _p(out)):
+            raise self._fail("amtgpu_amts_read_audio failed")
+        return out
 
     def __del__(self):
         try:
@@ -903,3 +927,97 @@ class FrameStats:
                 self.ctx.lib.amtgpu_framestats_destroy(self.h)
         except Exception:
             pass
+
+
+class AudioLevels:
+    """Per-video-frame audio levels: (N, 4) uint64 records {PEAK, SUMABS, SUMSQ, COUNT} of interleaved int16 PCM.
+    Video frame n owns sample-frames [frame_start(n), frame_start(n + 1)) below num_samples."""
+
+    PEAK, SUMABS, SUMSQ, COUNT = 0, 1, 2, 3
+
+    def __init__(self, ctx: Context, sample_rate, channels, fps_num, fps_den, num_samples):
+        self.ctx, self.sample_rate, self.channels, self.fps_num, self.fps_den = ctx, sample_rate, channels, fps_num, fps_den
+        self.num_samples = int(num_samples)
+        self.h = ctx.lib.amtgpu_audiolevels_create(ctx.h, sample_rate, channels, fps_num, fps_den, self.num_samples)
+        ctx.check(self.h, "AudioLevels")
+
+    def frame_start(self, n):
+        return int(self.ctx.lib.amtgpu_audiolevels_frame_start(self.h, int(n)))
+
+    def num_frames(self):
+        """video frames that own at least one sample-frame"""
+        n = self.num_samples * self.fps_num // (self.sample_rate * self.fps_den)
+        while self.frame_start(n) < self.num_samples:
+            n += 1
+        while n > 0 and self.frame_start(n - 1) >= self.num_samples:
+            n -= 1
+        return n
+
+    def run_device(self, pcm, pcm_first, first_frame, nframes, out=None):
+        """pcm: torch int16 tensor in HBM whose elements are sample-frames pcm_first .. of the timeline, interleaved (any shape; it must be
+        contiguous); out: (nframes, 4) int64 in HBM, made when None.  async"""
+        import torch
+        if pcm.dtype != torch.int16 or not pcm.is_contiguous():
+            raise AmtError("AudioLevels: pcm must be a contiguous int16 tensor")
+        if out is None:
+            out = torch.zeros((nframes, 4), dtype=torch.int64, device=pcm.device)
+        self.ctx.check(self.ctx.lib.amtgpu_audiolevels_batch(self.h, _p(pcm), int(pcm_first), pcm.numel() // self.channels, int(first_frame),
+                                                            int(nframes), _p(out)), "AudioLevels")
+        return out
+
+    def run(self, pcm_numpy, first_frame=0, nframes=None):
+        """pcm_numpy: the whole timeline from sample-frame 0 on, int16, (samples, channels) or flat interleaved"""
+        import torch
+        host = np.ascontiguousarray(pcm_numpy, np.int16).reshape(-1)
+        pcm = torch.from_numpy(host if host.flags.writeable else host.copy()).cuda(self.ctx.device)
+        if nframes is None:
+            nframes = self.num_frames() - first_frame
+        out = self.run_device(pcm, 0, first_frame, nframes)
+        self.ctx.synchronize()
+        return out.cpu().numpy().astype(np.uint64)
+
+    def run_amts(self, amts: AmtsFile, wavepath=None, first_frame=0, nframes=None):
+        """the records of the audio an amts file describes (AmtsFile.read_audio's samples), read, uploaded and reduced in chunks"""
+        if nframes is None:
+            nframes = self.num_frames() - first_frame
+        out = np.zeros((nframes, 4), np.uint64)
+        self.ctx.check(self.ctx.lib.amtgpu_audiolevels_amts(self.h, amts.h, str(wavepath).encode() if wavepath is not None else None,
+                                                           int(first_frame), int(nframes), _p(out)), "AudioLevels")
+        return out
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.ctx.lib.amtgpu_audiolevels_destroy(self.h)
+        except Exception:
+            pass
+
+
+def mute_sections(levels, mute_level=50, min_frames=10):
+    """[(start, end)] inclusive runs of at least min_frames video frames whose PEAK is at most mute_level (or that own no samples)"""
+    lv = np.ascontiguousarray(levels, np.uint64).reshape(-1, 4)
+    n = lv.shape[0]
+    lib = binding.load()
+    cap = n // max(1, int(min_frames)) + 1
+    st, en = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    k = C.c_int()
+    if not lib.amtgpu_cm_mute_sections(_p(lv), n, int(mute_level), int(min_frames), _p(st), _p(en), cap, C.byref(k)):
+        raise AmtError("amtgpu_cm_mute_sections failed (min_frames must be at least 1)")
+    return [(int(a), int(b)) for a, b in zip(st[:k.value], en[:k.value])]
+
+
+def write_chapter_exe(path, scene_changes, nframes, mute=None, only_muted=False):
+    """chapter_exe's output file (CMAnalyze::readSceneChanges' input, passed on to join_logo_scp): SCPos lines, and with mute
+    [(start, end)] (mute_sections) the "mute" lines in front of the scene changes they hold; only_muted drops every other scene change"""
+    lib = binding.load()
+    sc = np.ascontiguousarray(scene_changes, np.int32).reshape(-1)
+    if mute is None:
+        if only_muted:
+            raise AmtError("write_chapter_exe: only_muted needs the mute sections")
+        ok = lib.amtgpu_cm_write_chapter_exe(_p(sc), len(sc), int(nframes), str(path).encode())
+    else:
+        m = np.ascontiguousarray(mute, np.int32).reshape(-1, 2)
+        st, en = np.ascontiguousarray(m[:, 0]), np.ascontiguousarray(m[:, 1])
+        ok = lib.amtgpu_cm_write_chapter_exe_mute(_p(sc), len(sc), _p(st), _p(en), len(st), int(nframes), 1 if only_muted else 0, str(path).encode())
+    if not ok:
+        raise AmtError(f"write_chapter_exe({path}): refused (scene changes or sections unsorted, overlapping or outside the clip) or not writable")

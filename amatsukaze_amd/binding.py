@@ -95,6 +95,9 @@ SIGNATURES = {
     "amtgpu_amts_get_paths": (c_i, [c_p, c_p, c_i, c_p, c_i]),
     "amtgpu_amts_get_frames": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p]),
     "amtgpu_amts_weave_plan": (c_i, [c_p, c_p, c_i, c_p, c_p]),
+    "amtgpu_amts_audio_info": (c_i, [c_p, c_p, c_p]),
+    "amtgpu_amts_get_audio_frames": (c_i, [c_p, c_p, c_p, c_p]),
+    "amtgpu_amts_read_audio": (c_i, [c_p, c_s, c_i64, c_i64, c_p]),
     "amtgpu_logo_load": (c_p, [c_p, c_s]),
     "amtgpu_logo_from_planes": (c_p, [c_p] + [c_i] * 8 + [c_p]),
     "amtgpu_logo_save": (c_i, [c_p, c_p, c_s, c_s, c_i]),
@@ -169,6 +172,13 @@ SIGNATURES = {
     "amtgpu_kfm_write_durations": (c_i, [c_p, c_p, c_i, c_s, c_p]),
     "amtgpu_kfm_write_timecode": (c_i, [c_p, c_p, c_i, c_i, c_i, c_s, c_p]),
     "amtgpu_cm_write_chapter_exe": (c_i, [c_p, c_i, c_i, c_s]),
+    "amtgpu_audiolevels_create": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i64]),
+    "amtgpu_audiolevels_destroy": (None, [c_p]),
+    "amtgpu_audiolevels_frame_start": (c_i64, [c_p, c_i64]),
+    "amtgpu_audiolevels_batch": (c_i, [c_p, c_p, c_i64, c_i64, c_i, c_i, c_p]),
+    "amtgpu_audiolevels_amts": (c_i, [c_p, c_p, c_s, c_i, c_i, c_p]),
+    "amtgpu_cm_mute_sections": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
+    "amtgpu_cm_write_chapter_exe_mute": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_s]),
     "amtgpu_logofind_create": (c_p, [c_p, c_i, c_i, c_i]),
     "amtgpu_logofind_destroy": (None, [c_p]),
     "amtgpu_logofind_add_batch": (c_i, [c_p, c_p, c_i64, c_i, c_i]),

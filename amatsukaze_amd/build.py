@@ -31,6 +31,8 @@ SOURCES = [
     "logofind_kernels.hip",
     "logofind_msb_kernels.hip",
     "surface_kernels.hip",
+    "amt_gpu_audio.hip",
+    "audio_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

@@ -216,8 +216,8 @@ int amtgpu_kfm_write_timecode(const uint8_t* cadence, const uint8_t* phase, int 
 }
 
 // chapter_exe's output as CMAnalyze::readSceneChanges parses it (CMAnalyze.hpp:411-439): everything up to a line that
-// starts with "----" is header; then "SCPos: <frame>" lines (and "mute<k>: <a> - <b>" lines, which this build never
-// writes: audio silence detection is out of scope).  The raw file also goes to join_logo_scp (:346-347).
+// starts with "----" is header; then "SCPos: <frame>" lines (and "mute<k>: <a> - <b>" lines, which this call does not
+// write: amtgpu_cm_write_chapter_exe_mute, amt_gpu_audio.hip, writes the file with them).  The raw file also goes to join_logo_scp (:346-347).
 int amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path)
 {
     FILE* fp = std::fopen(path, "w");

@@ -18,6 +18,8 @@
 // The plan: AMTSource::OnFrameOutput (:482-566) matches every decoded picture to the frame list by its 33-bit PTS; a frame whose
 // halfDelay is set is woven from the PREVIOUS picture's top field and this picture's bottom field (MakeFrame(prev, cur)), any other
 // frame from one picture -- exactly the (top_index, bottom_index) pairs amtgpu_weave_fields_batch takes.
+// The audio timeline: MakeVideoInfo's samples-per-frame rule (:239-250) and GetAudio's assembly of 16-bit stereo sample-frames out of
+// the wave file (:782-817), restated in amtgpu_amts_audio_info / amtgpu_amts_read_audio below.
 #include "build_knobs.h"
 #include "../../include/amt_gpu.h"
 
@@ -33,6 +35,7 @@
 #include "api_common.hpp"
 
 struct AmtGpuAmtsFile {
+    AmtGpuContext* ctx = nullptr;       // where amtgpu_amts_read_audio leaves its message (may be null)
     std::u16string srcpath, audiopath;
     int32_t vfmt[9] = {0};              // format, width, height, displayWidth, displayHeight, sarWidth, sarHeight, frameRateNum, frameRateDenom
     uint8_t color[3] = {0};
@@ -71,7 +74,67 @@ template <typename T> T at(const uint8_t* base, size_t off) { T v; std::memcpy(&
 
 std::string utf8(const std::u16string& s) { return amt_utf8_from_utf16(reinterpret_cast<const uint16_t*>(s.data()), s.size()); }
 
+constexpr int kAudioSampleBytes = 4;          // GetAudio hard-codes 16-bit stereo (AMTSource.hpp:788), whatever AudioFormat.channels says
+
+// MakeVideoInfo (AMTSource.hpp:239-247): 1024, replaced by waveLength / 4 of the first audio frame that has a wave
+int64_t samples_per_audio_frame(const AmtGpuAmtsFile* a)
+{
+    if (a->audio.empty()) return 0;
+    for (const AmtGpuAmtsFile::Audio& f : a->audio)
+        if (f.waveLength != 0) return f.waveLength / kAudioSampleBytes;
+    return 1024;
+}
+
+struct FileCloser { void operator()(FILE* f) const { if (f) std::fclose(f); } };
+
 } // namespace
+
+// AMTSource::GetAudio (AMTSource.hpp:782-817): audio frame k owns sample-frames [k spf, (k + 1) spf) of the timeline and supplies them
+// from waveOffset on -- spf * 4 bytes whatever its waveLength says -- or as zeros when its waveLength is 0; behind the last audio frame
+// everything is zero.  The reference seeks and reads once per audio frame; here pieces that follow each other in the file AND in `out`
+// leave as one read.
+void amt_amts_read_audio(const AmtGpuAmtsFile* a, const char* wavepath, int64_t start, int64_t count, int16_t* out)
+{
+    if (!a) throw std::runtime_error("[AmtsAudio] null amts file");
+    if (start < 0 || count < 0) throw std::runtime_error("[AmtsAudio] negative start or count");
+    if (a->audio.empty()) throw std::runtime_error("[AmtsAudio] the clip has no audio frames");
+    const int64_t spf = samples_per_audio_frame(a);
+    if (spf <= 0) throw std::runtime_error("[AmtsAudio] the first audio frame with a wave is shorter than one sample-frame");
+    if (count == 0) return;
+    if (!out) throw std::runtime_error("[AmtsAudio] null output buffer");
+    const std::string path = wavepath ? std::string(wavepath) : utf8(a->audiopath);
+    std::unique_ptr<FILE, FileCloser> file(std::fopen(path.c_str(), "rb"));
+    if (!file) throw std::runtime_error("[AmtsAudio] failed to open file " + path);
+
+    uint8_t* ptr = reinterpret_cast<uint8_t*>(out);
+    // the pending read: `bytes` from file offset `off` to `dst`
+    int64_t off = 0, bytes = 0;
+    uint8_t* dst = nullptr;
+    auto flush = [&] {
+        if (!bytes) return;
+        if (off < 0 || fseeko(file.get(), (off_t)off, SEEK_SET) != 0) throw std::runtime_error("[AmtsAudio] cannot seek in " + path);
+        if (std::fread(dst, 1, (size_t)bytes, file.get()) != (size_t)bytes) throw std::runtime_error("[AmtsAudio] short read from " + path);
+        bytes = 0;
+    };
+    const int64_t naudio = (int64_t)a->audio.size();
+    int64_t left = count;
+    for (int64_t k = start / spf, offset = start % spf; left > 0 && k < naudio; ++k, offset = 0) {
+        const int64_t n = std::min((spf - offset) * kAudioSampleBytes, left * kAudioSampleBytes);      // bytes this frame fills
+        const AmtGpuAmtsFile::Audio& f = a->audio[(size_t)k];
+        if (f.waveLength != 0) {
+            const int64_t from = f.waveOffset + offset * kAudioSampleBytes;
+            if (bytes && (from != off + bytes || ptr != dst + bytes)) flush();
+            if (!bytes) { off = from; dst = ptr; }
+            bytes += n;
+        } else {
+            std::memset(ptr, 0, (size_t)n);
+        }
+        ptr += n;
+        left -= n / kAudioSampleBytes;
+    }
+    flush();
+    if (left > 0) std::memset(ptr, 0, (size_t)left * kAudioSampleBytes);
+}
 
 extern "C" {
 
@@ -84,6 +147,7 @@ AmtGpuAmtsFile* amtgpu_amts_load(AmtGpuContext* c, const char* path)
         std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
         Reader r(bytes);
         std::unique_ptr<AmtGpuAmtsFile> a(new AmtGpuAmtsFile);
+        a->ctx = c;
         for (std::u16string* s : {&a->srcpath, &a->audiopath}) {
             const int64_t n = r.count(2);
             const uint8_t* p = r.take((size_t)n * 2);
@@ -155,6 +219,32 @@ int amtgpu_amts_get_frames(const AmtGpuAmtsFile* a, int64_t* framePTS, int64_t* 
         if (cmType) cmType[i] = a->frames[i].cmType;
     }
     return 1;
+}
+
+int amtgpu_amts_audio_info(const AmtGpuAmtsFile* a, int* samples_per_frame, int64_t* num_samples)
+{
+    if (!a) return 0;
+    const int64_t spf = samples_per_audio_frame(a);
+    if (samples_per_frame) *samples_per_frame = (int)spf;
+    if (num_samples) *num_samples = spf * (int64_t)a->audio.size();
+    return 1;
+}
+
+int amtgpu_amts_get_audio_frames(const AmtGpuAmtsFile* a, int* frameIndex, int64_t* waveOffset, int* waveLength)
+{
+    if (!a) return 0;
+    for (size_t i = 0; i < a->audio.size(); ++i) {
+        if (frameIndex) frameIndex[i] = a->audio[i].frameIndex;
+        if (waveOffset) waveOffset[i] = a->audio[i].waveOffset;
+        if (waveLength) waveLength[i] = a->audio[i].waveLength;
+    }
+    return 1;
+}
+
+int amtgpu_amts_read_audio(const AmtGpuAmtsFile* a, const char* wavepath, int64_t start, int64_t count, int16_t* out)
+{
+    if (!a) return 0;
+    return guard(a->ctx, [&] { amt_amts_read_audio(a, wavepath, start, count, out); });
 }
 
 // AMTSource::OnFrameOutput (AMTSource.hpp:482-566) over a sequence of decoded pictures in output order

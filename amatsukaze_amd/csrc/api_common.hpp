@@ -166,6 +166,9 @@ inline LumaView surfaces_luma_view(AmtGpuContext* c, const amt::SurfaceBatch& b,
     return LumaView{band - ((size_t)row0 * pitch + c0) * b.es, (int64_t)frame_bytes, pitch};
 }
 
+// amtgpu_amts_read_audio (amts_file.cpp) for callers inside the library: throws instead of leaving a message on the file's context
+void amt_amts_read_audio(const AmtGpuAmtsFile* a, const char* wavepath, int64_t start, int64_t count, int16_t* out);
+
 // run f(); on any exception keep the message on the context and return 0 (no exceptions cross the ABI)
 template <typename F> inline int guard(AmtGpuContext* c, F&& f, const char* caller = __builtin_FUNCTION())
 {

@@ -109,6 +109,17 @@ hipError_t launch_logofind(hipStream_t st, int bits, const void* dY, long long f
 hipError_t launch_logofind_msb(hipStream_t st, int bits, int shift, const void* dY, long long frame_stride, int pitch_elems, int W, int H,
                                int nframes, int num_cus, unsigned long long* dS1, unsigned long long* dSM);
 
+// ---- audio_kernels.hip ----
+// The audio timeline of a clip: video frame n owns sample-frames [b(n), b(n + 1)) below num_samples, b(n) = n * step_num / fps_num floored
+// (step_num = sample_rate * fps_den); `channels` interleaved int16 elements per sample-frame
+struct AudioTimeline { long long num_samples, step_num, fps_num; int channels; };
+constexpr int kAudioLevelWords = 4;      // AMTGPU_AL_WORDS
+// records of video frames [first_frame, first_frame + nframes) into dout (4 uint64 each); dpcm holds the timeline from sample-frame
+// pcm_first on and covers every span of the range that is not empty (the caller has checked, and that (first_frame + nframes) * step_num
+// fits 63 bits); 2-byte aligned, nothing more.  One launch; none when nframes <= 0
+hipError_t launch_audio_levels(hipStream_t st, const int16_t* dpcm, long long pcm_first, const AudioTimeline& t, long long first_frame,
+                               int nframes, unsigned long long* dout);
+
 // ---- eval_fused_kernels.hip, eval_pair_kernels.hip, eval_linear_kernels.hip ----
 // tile plan of one evaluation logo resident in HBM (eval_tiles.hpp; eval_pair_kernels.hip).  slot = (band * kTileWaves + wave) * 64 + lane
 struct TileLogoDev {

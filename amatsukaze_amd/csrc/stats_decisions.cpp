@@ -144,4 +144,18 @@ std::vector<int> cadence_durations(const uint8_t* cadence, const uint8_t* phase,
     return d;
 }
 
+std::vector<std::pair<int, int>> mute_sections(const uint64_t* levels, int nframes, int mute_level, int min_frames)
+{
+    std::vector<std::pair<int, int>> out;
+    int run = 0;          // silent frames that end at n - 1
+    for (int n = 0; n <= nframes; ++n) {
+        const uint64_t* r = levels + (size_t)n * 4;
+        const bool silent = n < nframes && (r[3] == 0 || (mute_level >= 0 && r[0] <= (uint64_t)mute_level));
+        if (silent) { ++run; continue; }
+        if (run >= min_frames) out.emplace_back(n - run, n - 1);
+        run = 0;
+    }
+    return out;
+}
+
 } // namespace amt

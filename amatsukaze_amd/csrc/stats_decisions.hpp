@@ -4,6 +4,7 @@
 // (FilteredSource.hpp:265-269,637-676).  Integer arithmetic only.
 #pragma once
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 namespace amt {
@@ -14,5 +15,9 @@ std::vector<int> scene_changes(const uint64_t* metrics, int nframes, int width, 
 void classify_cadence(const uint64_t* metrics, int nframes, int width, int height, uint8_t* cadence, uint8_t* phase);
 // durations in 60p ticks of the clip AMTDecimate wraps: 60i frame -> 1,1; 30p -> 2; a full 3:2 cycle -> 2,3,2,3
 std::vector<int> cadence_durations(const uint8_t* cadence, const uint8_t* phase, int nframes);
+// Mute sections from the audio levels (4 uint64 per video frame: AMTGPU_AL_*; self-specified): a frame is silent
+// when its PEAK is at most mute_level or it owns no samples at all (COUNT 0); a section is a maximal run of at least min_frames silent
+// frames, inclusive [first, last]
+std::vector<std::pair<int, int>> mute_sections(const uint64_t* levels, int nframes, int mute_level, int min_frames);
 
 } // namespace amt

@@ -237,6 +237,19 @@ int  amtgpu_amts_get_frames(const AmtGpuAmtsFile* a, int64_t* framePTS, int64_t*
  * comes from picture top_index[i] and the bottom field from bottom_index[i] (both -1: the frame cannot be made from this sequence,
  * e.g. a half-delayed frame right after a discontinuity) -- the arrays amtgpu_weave_fields_batch takes. */
 int  amtgpu_amts_weave_plan(const AmtGpuAmtsFile* a, const int64_t* picture_pts, int npictures, int* top_index, int* bottom_index);
+/* The clip's audio timeline as AMTSource presents it (MakeVideoInfo, AMTSource.hpp:239-250): 16-bit stereo sample-frames of 4 bytes,
+ * samples_per_frame = 1024, replaced by waveLength / 4 of the first audio frame whose waveLength != 0, and
+ * num_samples = samples_per_frame * num_audio_frames.  Both are 0 for a clip without audio frames. */
+int  amtgpu_amts_audio_info(const AmtGpuAmtsFile* a, int* samples_per_frame, int64_t* num_samples);
+/* columns of the FilterAudioFrame list (num_audio_frames entries each; any pointer may be NULL) */
+int  amtgpu_amts_get_audio_frames(const AmtGpuAmtsFile* a, int* frameIndex, int64_t* waveOffset, int* waveLength);
+/* AMTSource::GetAudio (AMTSource.hpp:782-817): `count` sample-frames from `start` on into out (count * 4 bytes: 16-bit stereo, whatever
+ * AudioFormat.channels says).  Audio frame k supplies sample-frames [k spf, (k + 1) spf) from waveOffset on -- spf * 4 bytes, not limited
+ * by its waveLength -- or zeros when its waveLength is 0; everything behind the last audio frame is zero.  wavepath NULL: the file's own
+ * audiopath.  Audio frames that follow each other in the wave file are read with one read.  0, with a message on the context the file
+ * was loaded with: negative start or count, a clip without audio frames, a file that cannot be opened, a short read.  count == 0
+ * returns 1 and touches neither `out` nor the wave file. */
+int  amtgpu_amts_read_audio(const AmtGpuAmtsFile* a, const char* wavepath, int64_t start, int64_t count, int16_t* out);
 
 /* ---- logo model: replaces LogoData::Load / Save (AMTLogo.hpp:239-279), LogoFile_* getters
  *      (LogoGUISupport.hpp:254-275) ---- */
@@ -617,8 +630,49 @@ int  amtgpu_kfm_write_durations(const uint8_t* cadence, const uint8_t* phase, in
 int  amtgpu_kfm_write_timecode(const uint8_t* cadence, const uint8_t* phase, int nframes, int fps_num, int fps_den, const char* path,
                                int* nout);
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
- * lines; no "mute" lines (audio is out of scope) */
+ * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
+
+/* ---- per-video-frame audio levels, mute sections and chapter_exe's "mute" lines (self-specified, "parity unpinned": chapter_exe's
+ *      source is not in the reference tree).  PCM is interleaved little-endian int16, `channels` (1..8) elements
+ *      per sample-frame.  Video frame n owns sample-frames [b(n), b(n + 1)), b(n) = floor(n * sample_rate * fps_den / fps_num) in int64
+ *      (the VideoInfo::AudioSamplesFromFrames contract); positions >= num_samples do not exist: they add nothing and are not counted.
+ *      Per frame 4 x uint64, exact integers, independent of how the stream is cut into calls. ---- */
+typedef struct AmtGpuAudioLevels AmtGpuAudioLevels;
+#define AMTGPU_AL_WORDS  4      /* uint64 each */
+#define AMTGPU_AL_PEAK   0      /* max |s| over the span; |-32768| = 32768 */
+#define AMTGPU_AL_SUMABS 1      /* sum |s| */
+#define AMTGPU_AL_SUMSQ  2      /* sum s*s */
+#define AMTGPU_AL_COUNT  3      /* int16 elements of the span that lie inside the timeline */
+/* NULL with a message on ctx: sample_rate, fps_num or fps_den not positive, channels outside 1..8, negative num_samples */
+AmtGpuAudioLevels* amtgpu_audiolevels_create(AmtGpuContext* ctx, int sample_rate, int channels, int fps_num, int fps_den, int64_t num_samples);
+void    amtgpu_audiolevels_destroy(AmtGpuAudioLevels* al);
+/* b(frame); -1 for a negative frame or a position beyond 63 bits */
+int64_t amtgpu_audiolevels_frame_start(const AmtGpuAudioLevels* al, int64_t frame);
+/* Records of video frames [first_frame, first_frame + nframes) into d_out (device, nframes * AMTGPU_AL_WORDS uint64).  d_pcm (device)
+ * holds sample-frames [pcm_first, pcm_first + pcm_count) of the timeline and must cover
+ * [b(first_frame), min(b(first_frame + nframes), num_samples)), else the call is refused; nothing outside that part of d_pcm is read.
+ * d_pcm needs 2-byte alignment and nothing more.  nframes == 0 returns 1 and writes nothing.  async */
+int     amtgpu_audiolevels_batch(AmtGpuAudioLevels* al, const int16_t* d_pcm, int64_t pcm_first, int64_t pcm_count,
+                                 int first_frame, int nframes, uint64_t* d_out);
+/* The same records for the audio of an amts file into h_out (HOST): the wave file is read through amtgpu_amts_read_audio in chunks of a
+ * few thousand video frames, uploaded through the pinned staging ring and reduced chunk by chunk.  The object must have been created
+ * with channels == 2 (the reference's assembly is 16-bit stereo).  Synchronises */
+int     amtgpu_audiolevels_amts(AmtGpuAudioLevels* al, const AmtGpuAmtsFile* a, const char* wavepath,
+                                int first_frame, int nframes, uint64_t* h_out);
+/* Mute sections from the records of a whole clip (host): a frame is silent iff PEAK <= mute_level or COUNT == 0; a section is a maximal
+ * run of at least min_frames (>= 1) silent frames, reported as inclusive [start_out[i], end_out[i]].  *nmute = the total; returns 1 iff
+ * the total is at most cap (the first cap sections are written either way), as amtgpu_cm_scene_changes does */
+int amtgpu_cm_mute_sections(const uint64_t* levels, int nframes, int mute_level, int min_frames,
+                            int* start_out, int* end_out, int cap, int* nmute);
+/* amtgpu_cm_write_chapter_exe's file with the format's other half: after the header and the "----" line, in ascending frame order, one
+ * "mute%2d: %d - %d" line per section (numbered from 1) in front of every scene change >= its start, and the "\tSCPos: %d %d" lines.  A
+ * scene change belongs to a section when start <= sc <= end + 1 (a cut on the first sounding frame is the section's).  only_muted == 0:
+ * every scene change is written -- CMAnalyze::readSceneChanges builds the list it builds from amtgpu_cm_write_chapter_exe's file;
+ * only_muted != 0: scene changes that belong to no section are dropped.  0: scene changes not ascending, sections not ascending,
+ * overlapping, with start > end or reaching outside [0, nframes), or a file that cannot be written */
+int amtgpu_cm_write_chapter_exe_mute(const int* scene_changes, int nsc, const int* mute_start, const int* mute_end, int nmute,
+                                     int nframes, int only_muted, const char* path);
 
 /* ---- automatic logo detection (self-specified, "parity unpinned": no reference arithmetic).  The reference
  *      needs a rectangle drawn by hand before ScanLogo (LogoScan.hpp:1083-1098); these entry points find it from the clip.
