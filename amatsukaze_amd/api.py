@@ -1021,3 +1021,46 @@ def write_chapter_exe(path, scene_changes, nframes, mute=None, only_muted=False)
         ok = lib.amtgpu_cm_write_chapter_exe_mute(_p(sc), len(sc), _p(st), _p(en), len(st), int(nframes), 1 if only_muted else 0, str(path).encode())
     if not ok:
         raise AmtError(f"write_chapter_exe({path}): refused (scene changes or sections unsorted, overlapping or outside the clip) or not writable")
+
+
+RENDER_WEAVE, RENDER_BOB_TOP, RENDER_BOB_BOTTOM = 0, 1, 2
+RENDER_FRAME = np.dtype([("kind", np.int32), ("top", np.int32), ("bottom", np.int32), ("ticks", np.int32)])      # AmtGpuRenderFrame
+
+
+def kfm_render_plan(cadence, phase):
+    """The pictures that go with the cadence decisions (self-specified): one RENDER_FRAME record per output frame,
+    in the order of the durations file and with its ticks -- WEAVE(top, bottom) for film and progressive frames, BOB_TOP(n) then
+    BOB_BOTTOM(n) for a 60i frame.  Source frame numbers are absolute."""
+    cad = np.ascontiguousarray(cadence, np.uint8).reshape(-1)
+    ph = np.ascontiguousarray(phase, np.uint8).reshape(-1)
+    if len(cad) != len(ph):
+        raise AmtError("kfm_render_plan: cadence and phase differ in length")
+    lib = binding.load()
+    out = np.zeros(2 * len(cad), RENDER_FRAME)
+    k = C.c_int()
+    if not lib.amtgpu_kfm_render_plan(_p(cad), _p(ph), len(cad), _p(out), len(out), C.byref(k)):
+        raise AmtError("amtgpu_kfm_render_plan failed")
+    return out[:k.value].copy()
+
+
+def _surfaces_ref(clip):
+    if isinstance(clip, DeviceSurfaces):
+        return clip.ref()
+    return DeviceSurfaces(clip.Y, clip.U, clip.V, clip.width, clip.height, clip.bits).ref()
+
+
+def kfm_render(ctx: Context, src: "DeviceSurfaces | DeviceClip", plan, dst: "DeviceSurfaces | DeviceClip", src_first=0, clip_frames=None, thresh=-1):
+    """Renders the plan's output frames (kfm_render_plan, or any RENDER_FRAME array) into dst's first len(plan) frames: woven film
+    frames and bob-deinterlaced fields.  src holds frames [src_first, src_first + src.num_frames) of a clip of
+    clip_frames frames (default: the batch ends the clip); planar LSB planes only.  thresh >= 0: a missing row takes the average of its
+    two temporal neighbours where they differ by at most thresh (container units), which needs frame n - 1 / n + 1 in the batch; the
+    default -1 is the pure line-average bob.  Synchronises"""
+    pl = np.ascontiguousarray(plan, RENDER_FRAME).reshape(-1)
+    nsrc = src.num_frames
+    if clip_frames is None:
+        clip_frames = src_first + nsrc
+    if len(pl) > dst.num_frames:
+        raise AmtError(f"kfm_render: the plan has {len(pl)} output frames, dst holds {dst.num_frames}")
+    s, d = _surfaces_ref(src), _surfaces_ref(dst)
+    ctx.check(ctx.lib.amtgpu_kfm_render(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), _p(pl), len(pl),
+                                        int(thresh), C.byref(d)), "kfm_render")

@@ -40,6 +40,11 @@ class Surfaces(C.Structure):
                 ("interleaved", c_i), ("msb_aligned", c_i), ("reserved", c_i)]
 
 
+class RenderFrame(C.Structure):
+    """AmtGpuRenderFrame (include/amt_gpu.h)"""
+    _fields_ = [("kind", C.c_int32), ("top", C.c_int32), ("bottom", C.c_int32), ("ticks", C.c_int32)]
+
+
 class Collectives(C.Structure):
     """AmtGpuCollectives (include/amt_gpu.h)"""
     _fields_ = [("rank", c_i), ("world", c_i), ("allgather", ALLGATHER_CB), ("allreduce_sum_i64", ALLREDUCE_CB), ("user", c_p)]
@@ -171,6 +176,8 @@ SIGNATURES = {
     "amtgpu_kfm_cadence": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "amtgpu_kfm_write_durations": (c_i, [c_p, c_p, c_i, c_s, c_p]),
     "amtgpu_kfm_write_timecode": (c_i, [c_p, c_p, c_i, c_i, c_i, c_s, c_p]),
+    "amtgpu_kfm_render_plan": (c_i, [c_p, c_p, c_i, c_p, c_i, c_p]),
+    "amtgpu_kfm_render": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
     "amtgpu_cm_write_chapter_exe": (c_i, [c_p, c_i, c_i, c_s]),
     "amtgpu_audiolevels_create": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i64]),
     "amtgpu_audiolevels_destroy": (None, [c_p]),

@@ -33,6 +33,8 @@ SOURCES = [
     "surface_kernels.hip",
     "amt_gpu_audio.hip",
     "audio_kernels.hip",
+    "amt_gpu_render.hip",
+    "render_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

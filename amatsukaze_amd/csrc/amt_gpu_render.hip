@@ -1,0 +1,125 @@
+// amt_gpu_render.hip -- C ABI part 5: the pictures that go with the cadence decisions (self-specified, "parity unpinned"; DESIGN.md
+// section 6d): the render plan from cadence / phase, and the weave / bob renderer over source frames resident in HBM.
+#include "build_knobs.h"
+#include "../../include/amt_gpu.h"
+
+#include <string>
+#include <vector>
+
+#include "api_common.hpp"
+#include "stats_decisions.hpp"
+
+using namespace amt;
+
+static_assert(sizeof(AmtGpuRenderFrame) == sizeof(RenderFrame) && sizeof(RenderFrame) == 16, "the plan entry of the ABI is the planner's");
+static_assert(AMTGPU_RENDER_WEAVE == kRenderWeave && AMTGPU_RENDER_BOB_TOP == kRenderBobTop && AMTGPU_RENDER_BOB_BOTTOM == kRenderBobBottom,
+              "the kinds of the ABI are the planner's");
+
+namespace {
+const char* const kWho = "[KFMRender]";
+
+[[noreturn]] void refuse(const std::string& what) { throw std::runtime_error(std::string(kWho) + " " + what); }
+
+// planar LSB surfaces of `bits`, rows of at least width (width / 2) containers
+SurfaceBatch render_surfaces(const AmtGpuSurfaces* s, const char* which, int width)
+{
+    const SurfaceBatch b = surface_batch(s, kWho);
+    if (b.interleaved || b.shift)
+        refuse(std::string(which) + ": interleaved (NV12 / P010) and MSB-aligned surfaces are not rendered yet: planar LSB planes only");
+    if (b.strideY < 0 || b.strideUV < 0) refuse(std::string(which) + ": negative frame stride");
+    if (b.pitchY < width || b.pitchUV < width / 2) refuse(std::string(which) + ": pitch smaller than the row");
+    return b;
+}
+
+// [first byte, one past the last byte) that n frames of a plane span
+struct Span { uintptr_t lo, hi; };
+Span plane_span(const void* p, long long stride, int pitch_bytes, int row_bytes, int rows, int n)
+{
+    const uintptr_t lo = (uintptr_t)p;
+    return Span{lo, lo + (uintptr_t)(n - 1) * (uintptr_t)stride + (uintptr_t)(rows - 1) * (uintptr_t)pitch_bytes + (uintptr_t)row_bytes};
+}
+} // namespace
+
+extern "C" {
+
+int amtgpu_kfm_render_plan(const uint8_t* cadence, const uint8_t* phase, int nframes, AmtGpuRenderFrame* out, int cap, int* nout)
+{
+    try {
+        if (nframes < 0 || (nframes > 0 && (!cadence || !phase))) return 0;
+        const std::vector<RenderFrame> p = cadence_render_plan(cadence, phase, nframes);
+        if (nout) *nout = (int)p.size();
+        if ((int)p.size() > cap) return 0;
+        if (!p.empty() && !out) return 0;
+        for (size_t i = 0; i < p.size(); ++i) out[i] = AmtGpuRenderFrame{p[i].kind, p[i].top, p[i].bottom, p[i].ticks};
+        return 1;
+    } catch (...) { return 0; }
+}
+
+int amtgpu_kfm_render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
+                      const AmtGpuRenderFrame* plan, int nout, int thresh, const AmtGpuSurfaces* dst)
+{
+    if (!c) return 0;
+    return guard(c, [&] {
+        if (nout < 0) refuse("negative output frame count");
+        if (nout == 0) return;
+        if (!plan) refuse("null plan");
+        if (width <= 0 || height < 4 || (width & 1) || (height & 1)) refuse("width and height must be even and height at least 4 (4:2:0 field pairs)");
+        const SurfaceBatch s = render_surfaces(src, "source", width), d = render_surfaces(dst, "destination", width);
+        if (src->bits != dst->bits) refuse("source and destination differ in bits");
+        if (src_first < 0 || nsrc <= 0 || (long long)src_first + nsrc > clip_frames) refuse("the source batch does not lie inside the clip");
+        const int es = s.es, wUV = width >> 1, hUV = height >> 1;
+        const int maxv = es == 1 ? 255 : 65535;
+
+        std::vector<RenderEntry> entries((size_t)nout);
+        auto local = [&](long long n, int i, const char* what) {
+            if (n < src_first || n >= (long long)src_first + nsrc)
+                refuse("plan entry " + std::to_string(i) + ": " + what + " " + std::to_string(n) + " is outside the batch [" + std::to_string(src_first) + ", " +
+                       std::to_string(src_first + nsrc) + ")");
+            return (int)(n - src_first);
+        };
+        for (int i = 0; i < nout; ++i) {
+            const AmtGpuRenderFrame& f = plan[i];
+            if (f.kind < AMTGPU_RENDER_WEAVE || f.kind > AMTGPU_RENDER_BOB_BOTTOM) refuse("plan entry " + std::to_string(i) + ": kind outside 0..2");
+            if (f.kind != AMTGPU_RENDER_WEAVE && f.top != f.bottom) refuse("plan entry " + std::to_string(i) + ": a BOB entry needs top == bottom");
+            RenderEntry& e = entries[(size_t)i];
+            e.kind = f.kind;
+            e.top = local(f.top, i, "top frame");
+            e.bottom = local(f.bottom, i, "bottom frame");
+            e.other = e.top;
+            if (thresh >= 0 && f.kind == AMTGPU_RENDER_BOB_TOP && f.top >= 1) e.other = local((long long)f.top - 1, i, "the temporal neighbour");
+            if (thresh >= 0 && f.kind == AMTGPU_RENDER_BOB_BOTTOM && (long long)f.top + 1 < clip_frames) e.other = local((long long)f.top + 1, i, "the temporal neighbour");
+        }
+
+        RenderArgs a;
+        a.srcY = (const uint8_t*)s.Y; a.srcU = (const uint8_t*)s.U; a.srcV = (const uint8_t*)s.V;
+        a.dstY = (uint8_t*)d.Y; a.dstU = (uint8_t*)d.U; a.dstV = (uint8_t*)d.V;
+        a.src_strideY = s.strideY; a.src_strideUV = s.strideUV; a.dst_strideY = d.strideY; a.dst_strideUV = d.strideUV;
+        a.src_pitchY = s.pitchY * es; a.src_pitchUV = s.pitchUV * es; a.dst_pitchY = d.pitchY * es; a.dst_pitchUV = d.pitchUV * es;
+        a.rowY = width * es; a.rowUV = wUV * es;
+        a.H = height; a.HUV = hUV;
+        a.es = es;
+        a.thresh = thresh < 0 ? -1 : std::min(thresh, maxv);
+        // destination frames must not overlap each other, and no destination plane's span may touch a source plane's
+        if (nout > 1 && (a.dst_strideY < (long long)(height - 1) * a.dst_pitchY + a.rowY || a.dst_strideUV < (long long)(hUV - 1) * a.dst_pitchUV + a.rowUV))
+            refuse("destination frames overlap each other");
+        const Span sspan[3] = {plane_span(a.srcY, a.src_strideY, a.src_pitchY, a.rowY, height, nsrc), plane_span(a.srcU, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc),
+                               plane_span(a.srcV, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc)};
+        const Span dspan[3] = {plane_span(a.dstY, a.dst_strideY, a.dst_pitchY, a.rowY, height, nout), plane_span(a.dstU, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout),
+                               plane_span(a.dstV, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout)};
+        for (const Span& x : sspan)
+            for (const Span& y : dspan)
+                if (x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place rendering)");
+        auto al16 = [](const void* p, long long stride, int pitch) { return (uintptr_t)p % 16 == 0 && stride % 16 == 0 && pitch % 16 == 0; };
+        a.vec = al16(a.srcY, a.src_strideY, a.src_pitchY) && al16(a.srcU, a.src_strideUV, a.src_pitchUV) && al16(a.srcV, a.src_strideUV, a.src_pitchUV) &&
+                al16(a.dstY, a.dst_strideY, a.dst_pitchY) && al16(a.dstU, a.dst_strideUV, a.dst_pitchUV) && al16(a.dstV, a.dst_strideUV, a.dst_pitchUV);
+        c->bind();
+        DevBuf<RenderEntry> dplan;
+        dplan.upload(entries, c->stream);
+        const int sp_ = c->prof_begin("kfm_render_kernel");
+        AMT_HIP(launch_kfm_render(c->stream, a, dplan.get(), nout));
+        c->prof_end(sp_);
+        AMT_HIP(hipStreamSynchronize(c->stream));          // the plan's device copy dies with this call
+    });
+}
+
+} // extern "C"

@@ -93,6 +93,24 @@ hipError_t launch_weave_fields(hipStream_t st, const WeaveArgs& a, const int* dt
 hipError_t launch_ingest_rows(hipStream_t st, const void* src, long long src_stride, void* dst, long long dst_stride, unsigned long long chunk,
                               long long nchunks);
 
+// ---- render_kernels.hip ----
+// One output frame of the cadence renderer as the kernel reads it, batch-local picture numbers: kind 0 weaves even
+// rows of `top` with odd rows of `bottom`; kinds 1 / 2 (top == bottom == n) keep the even / odd rows of n and interpolate the others, with
+// `other` the picture that holds the missing rows' second temporal neighbour (n - 1 for kind 1, n + 1 for kind 2; n itself at the clip's
+// ends and wherever thresh < 0, so that nothing else is ever addressed)
+struct RenderEntry { int kind, top, bottom, other; };
+struct RenderArgs {
+    const uint8_t *srcY, *srcU, *srcV; uint8_t *dstY, *dstU, *dstV;
+    long long src_strideY, src_strideUV, dst_strideY, dst_strideUV;  // bytes between pictures
+    int src_pitchY, src_pitchUV, dst_pitchY, dst_pitchUV;            // bytes between rows
+    int rowY, rowUV;                                                 // bytes per row that are samples (width * es, width / 2 * es)
+    int H, HUV;
+    int es, vec;                                                     // vec: every base, stride and pitch is a multiple of 16 bytes
+    int thresh;                                                      // < 0: no temporal neighbour is read; else clamped to the container's range
+};
+// nout output frames from dplan (device, nout entries).  One launch; none when nout <= 0
+hipError_t launch_kfm_render(hipStream_t st, const RenderArgs& a, const RenderEntry* dplan, int nout);
+
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,
                               const void* dprevY, int nframes, unsigned long long* dout);

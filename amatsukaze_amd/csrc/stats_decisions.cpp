@@ -144,6 +144,29 @@ std::vector<int> cadence_durations(const uint8_t* cadence, const uint8_t* phase,
     return d;
 }
 
+// the walk of cadence_durations, entry for entry
+std::vector<RenderFrame> cadence_render_plan(const uint8_t* cadence, const uint8_t* phase, int nframes)
+{
+    std::vector<RenderFrame> p;
+    for (int n = 0; n < nframes;) {
+        if (cadence[n] == kCadence24p && phase[n] == 0 && n + 5 <= nframes) {
+            bool whole = true;
+            for (int k = 1; k < 5; ++k) whole = whole && cadence[n + k] == kCadence24p && phase[n + k] == k;
+            if (whole) {
+                // C C P P x: frames n and n+1 hold their own film picture, the third picture's top field lies in n+3 and its bottom
+                // field in n+2, the fourth is n+4
+                p.insert(p.end(), {{kRenderWeave, n, n, 2}, {kRenderWeave, n + 1, n + 1, 3}, {kRenderWeave, n + 3, n + 2, 2}, {kRenderWeave, n + 4, n + 4, 3}});
+                n += 5;
+                continue;
+            }
+        }
+        if (cadence[n] == kCadence60i) { p.push_back({kRenderBobTop, n, n, 1}); p.push_back({kRenderBobBottom, n, n, 1}); }
+        else p.push_back({kRenderWeave, n, n, 2});
+        ++n;
+    }
+    return p;
+}
+
 std::vector<std::pair<int, int>> mute_sections(const uint64_t* levels, int nframes, int mute_level, int min_frames)
 {
     std::vector<std::pair<int, int>> out;

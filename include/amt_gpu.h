@@ -629,6 +629,38 @@ int  amtgpu_kfm_write_durations(const uint8_t* cadence, const uint8_t* phase, in
  * start time in ms per output frame, "# total: <seconds>".  fps_num/fps_den = the SOURCE frame rate (30000/1001). */
 int  amtgpu_kfm_write_timecode(const uint8_t* cadence, const uint8_t* phase, int nframes, int fps_num, int fps_den, const char* path,
                                int* nout);
+/* ---- the pictures of the cadence decisions (self-specified, "parity unpinned": KFMDeint, which renders them in the reference, is not in
+ *      the reference tree).  The render plan names, per OUTPUT frame and in the order of the durations file, which
+ *      source frames it is made of; amtgpu_kfm_render makes the frames.  The rendered clip is already the decimated one: it needs no
+ *      AMTDecimate, its timestamps are amtgpu_kfm_write_timecode's and `ticks` is the durations file.  Top field first. ---- */
+typedef struct AmtGpuRenderFrame { int32_t kind, top, bottom, ticks; } AmtGpuRenderFrame;   /* absolute source frame numbers */
+#define AMTGPU_RENDER_WEAVE      0   /* even rows from frame `top`, odd rows from frame `bottom` */
+#define AMTGPU_RENDER_BOB_TOP    1   /* top == bottom == n: even rows of n kept, odd rows interpolated */
+#define AMTGPU_RENDER_BOB_BOTTOM 2   /* top == bottom == n: odd rows of n kept, even rows interpolated */
+/* One entry per output frame, walking the clip as amtgpu_kfm_write_durations does (ticks equal its lines entry for entry): a complete
+ * 3:2 cycle at n (phases 0..4, all 24p, n + 5 <= nframes) -> WEAVE(n, n) 2, WEAVE(n+1, n+1) 3, WEAVE(top n+3, bottom n+2) 2, WEAVE(n+4, n+4) 3;
+ * a 60i frame n -> BOB_TOP(n) 1, BOB_BOTTOM(n) 1; anything else (30p, 24p outside a complete cycle) -> WEAVE(n, n) 2, the frame as it is.
+ * *nout = the entries needed; returns 0 when cap is smaller (nothing is written then), 1 otherwise; nframes == 0 returns 1, *nout = 0 */
+int  amtgpu_kfm_render_plan(const uint8_t* cadence, const uint8_t* phase, int nframes, AmtGpuRenderFrame* out, int cap, int* nout);
+/* Renders plan[0 .. nout) into dst's frames 0 .. nout - 1.  src holds source frames [src_first, src_first + nsrc) of a clip of clip_frames
+ * frames; width x height is the luma size (both even, height >= 4; chroma planes are width / 2 x height / 2); plan is a HOST array.  Both
+ * descriptors must be planar and LSB (interleaved == 0, msb_aligned == 0) with equal bits, 8 or 9..16: NV12 / P010 descriptors are
+ * refused with a message (the struct is taken so that they can be added without a new signature).
+ * A missing row y of a BOB entry of frame n, in each plane at its own height, from containers as stored (no masking to bits):
+ *   up = P_n[y-1], dn = P_n[y+1] (a neighbour outside the plane takes the other one's value), spatial = (up + dn + 1) >> 1;
+ *   BOB_TOP: a = P_(n-1)[y], b = P_n[y] (n == 0: a = b);  BOB_BOTTOM: a = P_n[y], b = P_(n+1)[y] (n == clip_frames - 1: b = a);
+ *   output = thresh >= 0 && |a - b| <= thresh ? (a + b + 1) >> 1 : spatial.
+ * thresh is in container units and shared by the three planes; thresh < 0 is a pure line-average bob that reads no neighbour frame.  No
+ * default is recommended: no real footage has been measured.
+ * Returns 0 with a message on ctx, and launches nothing: width or height odd, height < 4; a pitch below the row; kind outside 0..2; a
+ * BOB entry with top != bottom; a frame number outside the batch; thresh >= 0 and a temporal neighbour (n - 1 for BOB_TOP with n >= 1,
+ * n + 1 for BOB_BOTTOM with n + 1 < clip_frames) outside the batch; destination frames that overlap each other; a destination plane
+ * whose byte range (first byte of frame 0 .. last byte of frame nout - 1) overlaps a source plane's.  nout == 0 returns 1.
+ * The bytes written depend on the clip and the plan alone: a clip rendered in several calls, each batch with its one-frame halo, gives
+ * the bytes of one call.  Reads nothing outside width (width / 2) samples of a source row, writes nothing outside them in a destination
+ * row.  Synchronises: the plan is copied to the device for the one launch and the copy is freed before the call returns */
+int  amtgpu_kfm_render(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
+                       const AmtGpuRenderFrame* plan, int nout, int thresh, const AmtGpuSurfaces* dst);
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
