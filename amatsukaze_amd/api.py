@@ -1052,9 +1052,11 @@ def _surfaces_ref(clip):
 def kfm_render(ctx: Context, src: "DeviceSurfaces | DeviceClip", plan, dst: "DeviceSurfaces | DeviceClip", src_first=0, clip_frames=None, thresh=-1):
     """Renders the plan's output frames (kfm_render_plan, or any RENDER_FRAME array) into dst's first len(plan) frames: woven film
     frames and bob-deinterlaced fields.  src holds frames [src_first, src_first + src.num_frames) of a clip of
-    clip_frames frames (default: the batch ends the clip); planar LSB planes only.  thresh >= 0: a missing row takes the average of its
-    two temporal neighbours where they differ by at most thresh (container units), which needs frame n - 1 / n + 1 in the batch; the
-    default -1 is the pure line-average bob.  Synchronises"""
+    clip_frames frames (default: the batch ends the clip).  src and dst are planar clips or decoder surfaces IN KIND -- equal bits,
+    interleaved and msb: NV12 in, NV12 out; P010 in, P010 out (V = None when interleaved); no layout is converted.  thresh >= 0: a
+    missing row takes the average of its two temporal neighbours where they differ by at most thresh, which needs frame n - 1 / n + 1
+    in the batch; the default -1 is the pure line-average bob.  thresh counts container units, or samples (container >> (16 - bits))
+    when msb: interpolated rows are then computed on samples and stored with zero low bits, copied rows keep theirs.  Synchronises"""
     pl = np.ascontiguousarray(plan, RENDER_FRAME).reshape(-1)
     nsrc = src.num_frames
     if clip_frames is None:

@@ -35,6 +35,7 @@ SOURCES = [
     "audio_kernels.hip",
     "amt_gpu_render.hip",
     "render_kernels.hip",
+    "render_surface_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

@@ -1,5 +1,6 @@
 // amt_gpu_render.hip -- C ABI part 5: the pictures that go with the cadence decisions (self-specified, "parity unpinned"; DESIGN.md
-// section 6d): the render plan from cadence / phase, and the weave / bob renderer over source frames resident in HBM.
+// section 6d): the render plan from cadence / phase, and the weave / bob renderer over source frames resident in HBM -- planes or
+// decoder surfaces (NV12, P010 / P012, planar MSB), source and destination in kind.
 #include "build_knobs.h"
 #include "../../include/amt_gpu.h"
 
@@ -20,14 +21,12 @@ const char* const kWho = "[KFMRender]";
 
 [[noreturn]] void refuse(const std::string& what) { throw std::runtime_error(std::string(kWho) + " " + what); }
 
-// planar LSB surfaces of `bits`, rows of at least width (width / 2) containers
+// surfaces of `bits` in any layout, rows of at least width containers (chroma: width / 2 planar, 2 * (width / 2) interleaved)
 SurfaceBatch render_surfaces(const AmtGpuSurfaces* s, const char* which, int width)
 {
     const SurfaceBatch b = surface_batch(s, kWho);
-    if (b.interleaved || b.shift)
-        refuse(std::string(which) + ": interleaved (NV12 / P010) and MSB-aligned surfaces are not rendered yet: planar LSB planes only");
     if (b.strideY < 0 || b.strideUV < 0) refuse(std::string(which) + ": negative frame stride");
-    if (b.pitchY < width || b.pitchUV < width / 2) refuse(std::string(which) + ": pitch smaller than the row");
+    if (b.pitchY < width || b.pitchUV < (b.interleaved ? width : width / 2)) refuse(std::string(which) + ": pitch smaller than the row");
     return b;
 }
 
@@ -66,9 +65,12 @@ int amtgpu_kfm_render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first
         if (width <= 0 || height < 4 || (width & 1) || (height & 1)) refuse("width and height must be even and height at least 4 (4:2:0 field pairs)");
         const SurfaceBatch s = render_surfaces(src, "source", width), d = render_surfaces(dst, "destination", width);
         if (src->bits != dst->bits) refuse("source and destination differ in bits");
+        if (s.interleaved != d.interleaved || s.shift != d.shift)
+            refuse("source and destination are not in kind (equal bits, interleaved and MSB shift): the renderer converts no layouts");
         if (src_first < 0 || nsrc <= 0 || (long long)src_first + nsrc > clip_frames) refuse("the source batch does not lie inside the clip");
         const int es = s.es, wUV = width >> 1, hUV = height >> 1;
-        const int maxv = es == 1 ? 255 : 65535;
+        const int maxv = s.shift ? (1 << src->bits) - 1 : es == 1 ? 255 : 65535;        // of a sample: MSB-aligned ones are compared shifted
+        const int nplanes = s.interleaved ? 2 : 3;                                       // Y, then U and V or the one UV plane
 
         std::vector<RenderEntry> entries((size_t)nout);
         auto local = [&](long long n, int i, const char* what) {
@@ -95,7 +97,7 @@ int amtgpu_kfm_render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first
         a.dstY = (uint8_t*)d.Y; a.dstU = (uint8_t*)d.U; a.dstV = (uint8_t*)d.V;
         a.src_strideY = s.strideY; a.src_strideUV = s.strideUV; a.dst_strideY = d.strideY; a.dst_strideUV = d.strideUV;
         a.src_pitchY = s.pitchY * es; a.src_pitchUV = s.pitchUV * es; a.dst_pitchY = d.pitchY * es; a.dst_pitchUV = d.pitchUV * es;
-        a.rowY = width * es; a.rowUV = wUV * es;
+        a.rowY = width * es; a.rowUV = (s.interleaved ? 2 * wUV : wUV) * es;
         a.H = height; a.HUV = hUV;
         a.es = es;
         a.thresh = thresh < 0 ? -1 : std::min(thresh, maxv);
@@ -106,17 +108,19 @@ int amtgpu_kfm_render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first
                                plane_span(a.srcV, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc)};
         const Span dspan[3] = {plane_span(a.dstY, a.dst_strideY, a.dst_pitchY, a.rowY, height, nout), plane_span(a.dstU, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout),
                                plane_span(a.dstV, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout)};
-        for (const Span& x : sspan)
-            for (const Span& y : dspan)
-                if (x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place rendering)");
+        for (int i = 0; i < nplanes; ++i)
+            for (int j = 0; j < nplanes; ++j)
+                if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place rendering)");
+        // (an interleaved batch has null V planes, which count as aligned: surface_batch drops whatever the descriptor holds there)
         auto al16 = [](const void* p, long long stride, int pitch) { return (uintptr_t)p % 16 == 0 && stride % 16 == 0 && pitch % 16 == 0; };
         a.vec = al16(a.srcY, a.src_strideY, a.src_pitchY) && al16(a.srcU, a.src_strideUV, a.src_pitchUV) && al16(a.srcV, a.src_strideUV, a.src_pitchUV) &&
                 al16(a.dstY, a.dst_strideY, a.dst_pitchY) && al16(a.dstU, a.dst_strideUV, a.dst_pitchUV) && al16(a.dstV, a.dst_strideUV, a.dst_pitchUV);
         c->bind();
         DevBuf<RenderEntry> dplan;
         dplan.upload(entries, c->stream);
-        const int sp_ = c->prof_begin("kfm_render_kernel");
-        AMT_HIP(launch_kfm_render(c->stream, a, dplan.get(), nout));
+        const bool planes = !s.interleaved && !s.shift;                                  // planar LSB: the plain kernel, as before
+        const int sp_ = c->prof_begin(planes ? "kfm_render_kernel" : "kfm_render_surfaces_kernel");
+        AMT_HIP(planes ? launch_kfm_render(c->stream, a, dplan.get(), nout) : launch_kfm_render_surfaces(c->stream, a, s.interleaved, s.shift, dplan.get(), nout));
         c->prof_end(sp_);
         AMT_HIP(hipStreamSynchronize(c->stream));          // the plan's device copy dies with this call
     });

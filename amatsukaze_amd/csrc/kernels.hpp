@@ -110,6 +110,10 @@ struct RenderArgs {
 };
 // nout output frames from dplan (device, nout entries).  One launch; none when nout <= 0
 hipError_t launch_kfm_render(hipStream_t st, const RenderArgs& a, const RenderEntry* dplan, int nout);
+// render_surface_kernels.hip: the same frames on decoder surfaces, source and destination in kind (planar LSB surfaces are ordinary planes
+// and go to launch_kfm_render).  interleaved: srcU / dstU are the UV planes, a.rowUV their width * es bytes, srcV / dstV unused.
+// shift != 0 (es 2): MSB-aligned containers; interpolated samples are container >> shift, stored << shift, and a.thresh counts samples
+hipError_t launch_kfm_render_surfaces(hipStream_t st, const RenderArgs& a, int interleaved, int shift, const RenderEntry* dplan, int nout);
 
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,

@@ -194,12 +194,15 @@ int   amtgpu_weave_fields_batch_msb(AmtGpuContext* ctx, const void* dsrcY, const
  *      by every pass that reads frames in HBM: the ScanLogo session (amtgpu_scanlogo_stream_feed_surfaces, the logo
  *      rectangle), the logo finder (amtgpu_logofind_add_surfaces, the Y plane), the encode-time analysis and the LogoFrame scan
  *      (amtgpu_analyze_surfaces, amtgpu_logoframe_scan_surfaces: the logos' rows and columns of the Y plane), the erase
- *      (amtgpu_erase_surfaces...: the logo rectangle) and the frame metrics (amtgpu_framestats_surfaces, _sharded_surfaces: the whole Y
- *      plane).  The sample rule is a plain right shift: whatever sits in the low 16 - bits bits
+ *      (amtgpu_erase_surfaces...: the logo rectangle), the frame metrics (amtgpu_framestats_surfaces, _sharded_surfaces: the whole Y
+ *      plane) and the cadence renderer (amtgpu_kfm_render: whole surfaces in, whole surfaces of the same kind out).  The sample rule is
+ *      a plain right shift: whatever sits in the low 16 - bits bits
  *      of an MSB-aligned container is discarded (P010 says zero; decoders and dithering filters do not always leave zero there).
  *      The plane pointers are const because most entry points only read them; the ERASE entry points WRITE the planes the descriptor
- *      points to (amtgpu_erase_surfaces, amtgpu_erase_surfaces_dfades, and the dst of amtgpu_erase_surfaces_dfades_to): a rewritten
- *      MSB-aligned container is result << (16 - bits), its low bits zero.  4:2:0 only; linear (untiled, uncompressed) layouts only. ---- */
+ *      points to (amtgpu_erase_surfaces, amtgpu_erase_surfaces_dfades, and the dst of amtgpu_erase_surfaces_dfades_to), and
+ *      amtgpu_kfm_render writes its dst: a COMPUTED MSB-aligned container is result << (16 - bits), its low bits zero, and a container
+ *      that is only moved (a row the renderer copies, everything Delogo leaves alone) keeps its low bits.  4:2:0 only; linear (untiled,
+ *      uncompressed) layouts only. ---- */
 typedef struct AmtGpuSurfaces {
     const void* Y;               /* luma plane of the first picture (device) */
     const void* U;               /* planar: U plane.  interleaved: the UV plane (U0 V0 U1 V1 ...) */
@@ -643,22 +646,34 @@ typedef struct AmtGpuRenderFrame { int32_t kind, top, bottom, ticks; } AmtGpuRen
  * *nout = the entries needed; returns 0 when cap is smaller (nothing is written then), 1 otherwise; nframes == 0 returns 1, *nout = 0 */
 int  amtgpu_kfm_render_plan(const uint8_t* cadence, const uint8_t* phase, int nframes, AmtGpuRenderFrame* out, int cap, int* nout);
 /* Renders plan[0 .. nout) into dst's frames 0 .. nout - 1.  src holds source frames [src_first, src_first + nsrc) of a clip of clip_frames
- * frames; width x height is the luma size (both even, height >= 4; chroma planes are width / 2 x height / 2); plan is a HOST array.  Both
- * descriptors must be planar and LSB (interleaved == 0, msb_aligned == 0) with equal bits, 8 or 9..16: NV12 / P010 descriptors are
- * refused with a message (the struct is taken so that they can be added without a new signature).
- * A missing row y of a BOB entry of frame n, in each plane at its own height, from containers as stored (no masking to bits):
+ * frames; width x height is the luma size (both even, height >= 4; chroma planes are width / 2 x height / 2); plan is a HOST array.
+ * src and dst must be IN KIND: equal bits (8 or 9..16), equal interleaved, and an equal shift s = msb_aligned ? 16 - bits : 0.  Planes in,
+ * planes out; NV12 in, NV12 out; P010 / P012 in, the same out; planar MSB in, planar MSB out.  The call converts no layouts (NV12 ->
+ * planes, planes -> NV12, MSB -> LSB are refused; amtgpu_weave_fields_batch[_msb] planarises).
+ * A missing row y of a BOB entry of frame n, in each plane at its own height:
  *   up = P_n[y-1], dn = P_n[y+1] (a neighbour outside the plane takes the other one's value), spatial = (up + dn + 1) >> 1;
  *   BOB_TOP: a = P_(n-1)[y], b = P_n[y] (n == 0: a = b);  BOB_BOTTOM: a = P_n[y], b = P_(n+1)[y] (n == clip_frames - 1: b = a);
  *   output = thresh >= 0 && |a - b| <= thresh ? (a + b + 1) >> 1 : spatial.
- * thresh is in container units and shared by the three planes; thresh < 0 is a pure line-average bob that reads no neighbour frame.  No
- * default is recommended: no real footage has been measured.
- * Returns 0 with a message on ctx, and launches nothing: width or height odd, height < 4; a pitch below the row; kind outside 0..2; a
- * BOB entry with top != bottom; a frame number outside the batch; thresh >= 0 and a temporal neighbour (n - 1 for BOB_TOP with n >= 1,
- * n + 1 for BOB_BOTTOM with n + 1 < clip_frames) outside the batch; destination frames that overlap each other; a destination plane
- * whose byte range (first byte of frame 0 .. last byte of frame nout - 1) overlaps a source plane's.  nout == 0 returns 1.
+ * thresh is shared by the planes; thresh < 0 is a pure line-average bob that reads no neighbour frame.  No default is recommended: no
+ * real footage has been measured.
+ * LSB containers (s == 0): up, dn, a, b are the containers as stored, no masking to bits; thresh is in container units.
+ * MSB-aligned containers (s > 0): a COPIED row (every row of a WEAVE, the kept rows of a BOB) is the source row's containers as stored,
+ * low bits included.  An INTERPOLATED container is computed on samples: up, dn, a, b are container >> s, thresh is in sample units
+ * (clamped to (1 << bits) - 1), both means round at the sample's unit, and the stored container is output << s with zero low bits.  So
+ * dst >> s is the planar LSB render of src >> s in every container.
+ * Interleaved chroma: U is one UV plane of height / 2 rows of `width` containers, pitchUV >= width; V is ignored and may be NULL.  The
+ * rule is vertical and temporal only, so each U and each V container meets its own plane's column: the result is the interleave of the
+ * planar result.  Y and UV of one allocation (strideY == strideUV == the surface size) is the normal case.
+ * Returns 0 with a message on ctx, and launches nothing: descriptors not in kind; width or height odd, height < 4; a pitch below the row
+ * (pitchUV < width when interleaved, < width / 2 when planar); kind outside 0..2; a BOB entry with top != bottom; a frame number outside
+ * the batch; thresh >= 0 and a temporal neighbour (n - 1 for BOB_TOP with n >= 1, n + 1 for BOB_BOTTOM with n + 1 < clip_frames) outside
+ * the batch; destination frames that overlap each other in a plane; a destination plane whose byte range (first byte of frame 0 .. last
+ * byte of frame nout - 1) overlaps a source plane's -- over the planes there are: Y and UV (rows of width containers) when interleaved,
+ * Y, U and V otherwise.  nout == 0 returns 1.
  * The bytes written depend on the clip and the plan alone: a clip rendered in several calls, each batch with its one-frame halo, gives
- * the bytes of one call.  Reads nothing outside width (width / 2) samples of a source row, writes nothing outside them in a destination
- * row.  Synchronises: the plan is copied to the device for the one launch and the copy is freed before the call returns */
+ * the bytes of one call.  Reads nothing outside a row's width (width / 2 in planar chroma) containers of a source row, writes nothing
+ * outside them in a destination row.  Synchronises: the plan is copied to the device for the one launch and the copy is freed before the
+ * call returns */
 int  amtgpu_kfm_render(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
                        const AmtGpuRenderFrame* plan, int nout, int thresh, const AmtGpuSurfaces* dst);
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
