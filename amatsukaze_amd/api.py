@@ -1025,6 +1025,7 @@ def write_chapter_exe(path, scene_changes, nframes, mute=None, only_muted=False)
 
 RENDER_WEAVE, RENDER_BOB_TOP, RENDER_BOB_BOTTOM = 0, 1, 2
 RENDER_FRAME = np.dtype([("kind", np.int32), ("top", np.int32), ("bottom", np.int32), ("ticks", np.int32)])      # AmtGpuRenderFrame
+DEINT_LINE, DEINT_ADAPTIVE = 0, 1                                                                                # AMTGPU_DEINT_*
 
 
 def kfm_render_plan(cadence, phase):
@@ -1049,14 +1050,20 @@ def _surfaces_ref(clip):
     return DeviceSurfaces(clip.Y, clip.U, clip.V, clip.width, clip.height, clip.bits).ref()
 
 
-def kfm_render(ctx: Context, src: "DeviceSurfaces | DeviceClip", plan, dst: "DeviceSurfaces | DeviceClip", src_first=0, clip_frames=None, thresh=-1):
+def kfm_render(ctx: Context, src: "DeviceSurfaces | DeviceClip", plan, dst: "DeviceSurfaces | DeviceClip", src_first=0, clip_frames=None, thresh=-1,
+               deint="line"):
     """Renders the plan's output frames (kfm_render_plan, or any RENDER_FRAME array) into dst's first len(plan) frames: woven film
     frames and bob-deinterlaced fields.  src holds frames [src_first, src_first + src.num_frames) of a clip of
     clip_frames frames (default: the batch ends the clip).  src and dst are planar clips or decoder surfaces IN KIND -- equal bits,
     interleaved and msb: NV12 in, NV12 out; P010 in, P010 out (V = None when interleaved); no layout is converted.  thresh >= 0: a
     missing row takes the average of its two temporal neighbours where they differ by at most thresh, which needs frame n - 1 / n + 1
     in the batch; the default -1 is the pure line-average bob.  thresh counts container units, or samples (container >> (16 - bits))
-    when msb: interpolated rows are then computed on samples and stored with zero low bits, copied rows keep theirs.  Synchronises"""
+    when msb: interpolated rows are then computed on samples and stored with zero low bits, copied rows keep theirs.
+    deint="adaptive" fills the missing rows of the 60i frames with the edge-directed, motion-adaptive rule instead (amtgpu_kfm_render_deint;
+    DESIGN.md section 6d): still areas weave, moving areas interpolate along the edge.  It has no threshold (thresh must stay -1), reads
+    frames n - 1 and n + 1 of every bob entry wherever the clip has them, and takes planar LSB clips only.  Synchronises"""
+    if deint not in ("line", "adaptive"):
+        raise AmtError(f"kfm_render: deint is 'line' or 'adaptive', not {deint!r}")
     pl = np.ascontiguousarray(plan, RENDER_FRAME).reshape(-1)
     nsrc = src.num_frames
     if clip_frames is None:
@@ -1064,5 +1071,9 @@ def kfm_render(ctx: Context, src: "DeviceSurfaces | DeviceClip", plan, dst: "Dev
     if len(pl) > dst.num_frames:
         raise AmtError(f"kfm_render: the plan has {len(pl)} output frames, dst holds {dst.num_frames}")
     s, d = _surfaces_ref(src), _surfaces_ref(dst)
+    if deint == "adaptive":
+        ctx.check(ctx.lib.amtgpu_kfm_render_deint(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), _p(pl), len(pl),
+                                                  DEINT_ADAPTIVE, int(thresh), C.byref(d)), "kfm_render")
+        return
     ctx.check(ctx.lib.amtgpu_kfm_render(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), _p(pl), len(pl),
                                         int(thresh), C.byref(d)), "kfm_render")

@@ -36,6 +36,7 @@ SOURCES = [
     "amt_gpu_render.hip",
     "render_kernels.hip",
     "render_surface_kernels.hip",
+    "render_adaptive_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

@@ -37,6 +37,101 @@ Span plane_span(const void* p, long long stride, int pitch_bytes, int row_bytes,
     const uintptr_t lo = (uintptr_t)p;
     return Span{lo, lo + (uintptr_t)(n - 1) * (uintptr_t)stride + (uintptr_t)(rows - 1) * (uintptr_t)pitch_bytes + (uintptr_t)row_bytes};
 }
+
+// both entry points: deint LINE is amtgpu_kfm_render, ADAPTIVE the edge-directed, motion-adaptive rule on planes
+void render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height, const AmtGpuRenderFrame* plan, int nout,
+            int deint, int thresh, const AmtGpuSurfaces* dst)
+{
+    if (deint != AMTGPU_DEINT_LINE && deint != AMTGPU_DEINT_ADAPTIVE) refuse("deint " + std::to_string(deint) + " is neither AMTGPU_DEINT_LINE nor AMTGPU_DEINT_ADAPTIVE");
+    const bool adaptive = deint == AMTGPU_DEINT_ADAPTIVE;
+    if (adaptive && thresh != -1) refuse("the adaptive rule has no threshold: thresh must be -1");
+    if (nout < 0) refuse("negative output frame count");
+    if (nout == 0) return;
+    if (!plan) refuse("null plan");
+    if (width <= 0 || height < 4 || (width & 1) || (height & 1)) refuse("width and height must be even and height at least 4 (4:2:0 field pairs)");
+    const SurfaceBatch s = render_surfaces(src, "source", width), d = render_surfaces(dst, "destination", width);
+    if (src->bits != dst->bits) refuse("source and destination differ in bits");
+    if (s.interleaved != d.interleaved || s.shift != d.shift)
+        refuse("source and destination are not in kind (equal bits, interleaved and MSB shift): the renderer converts no layouts");
+    if (adaptive && (s.interleaved || s.shift)) refuse("the adaptive rule takes planes only (planar, LSB-aligned): interleaved and MSB-aligned surfaces are refused");
+    if (src_first < 0 || nsrc <= 0 || (long long)src_first + nsrc > clip_frames) refuse("the source batch does not lie inside the clip");
+    const int es = s.es, wUV = width >> 1, hUV = height >> 1;
+    const int maxv = s.shift ? (1 << src->bits) - 1 : es == 1 ? 255 : 65535;        // of a sample: MSB-aligned ones are compared shifted
+    const int nplanes = s.interleaved ? 2 : 3;                                       // Y, then U and V or the one UV plane
+
+    std::vector<RenderEntry> entries((size_t)(adaptive ? 0 : nout));
+    std::vector<RenderAdaptiveEntry> aentries((size_t)(adaptive ? nout : 0));
+    auto local = [&](long long n, int i, const char* what) {
+        if (n < src_first || n >= (long long)src_first + nsrc)
+            refuse("plan entry " + std::to_string(i) + ": " + what + " " + std::to_string(n) + " is outside the batch [" + std::to_string(src_first) + ", " +
+                   std::to_string(src_first + nsrc) + ")");
+        return (int)(n - src_first);
+    };
+    for (int i = 0; i < nout; ++i) {
+        const AmtGpuRenderFrame& f = plan[i];
+        if (f.kind < AMTGPU_RENDER_WEAVE || f.kind > AMTGPU_RENDER_BOB_BOTTOM) refuse("plan entry " + std::to_string(i) + ": kind outside 0..2");
+        if (f.kind != AMTGPU_RENDER_WEAVE && f.top != f.bottom) refuse("plan entry " + std::to_string(i) + ": a BOB entry needs top == bottom");
+        if (adaptive) {
+            // both bobs read both neighbours of n, wherever the clip has them
+            RenderAdaptiveEntry& e = aentries[(size_t)i];
+            e.kind = f.kind;
+            e.top = local(f.top, i, "top frame");
+            e.bottom = local(f.bottom, i, "bottom frame");
+            e.prev = e.next = e.top;
+            if (f.kind != AMTGPU_RENDER_WEAVE && f.top >= 1) e.prev = local((long long)f.top - 1, i, "the neighbour frame");
+            if (f.kind != AMTGPU_RENDER_WEAVE && (long long)f.top + 1 < clip_frames) e.next = local((long long)f.top + 1, i, "the neighbour frame");
+            continue;
+        }
+        RenderEntry& e = entries[(size_t)i];
+        e.kind = f.kind;
+        e.top = local(f.top, i, "top frame");
+        e.bottom = local(f.bottom, i, "bottom frame");
+        e.other = e.top;
+        if (thresh >= 0 && f.kind == AMTGPU_RENDER_BOB_TOP && f.top >= 1) e.other = local((long long)f.top - 1, i, "the temporal neighbour");
+        if (thresh >= 0 && f.kind == AMTGPU_RENDER_BOB_BOTTOM && (long long)f.top + 1 < clip_frames) e.other = local((long long)f.top + 1, i, "the temporal neighbour");
+    }
+
+    RenderArgs a;
+    a.srcY = (const uint8_t*)s.Y; a.srcU = (const uint8_t*)s.U; a.srcV = (const uint8_t*)s.V;
+    a.dstY = (uint8_t*)d.Y; a.dstU = (uint8_t*)d.U; a.dstV = (uint8_t*)d.V;
+    a.src_strideY = s.strideY; a.src_strideUV = s.strideUV; a.dst_strideY = d.strideY; a.dst_strideUV = d.strideUV;
+    a.src_pitchY = s.pitchY * es; a.src_pitchUV = s.pitchUV * es; a.dst_pitchY = d.pitchY * es; a.dst_pitchUV = d.pitchUV * es;
+    a.rowY = width * es; a.rowUV = (s.interleaved ? 2 * wUV : wUV) * es;
+    a.H = height; a.HUV = hUV;
+    a.es = es;
+    a.thresh = thresh < 0 ? -1 : std::min(thresh, maxv);
+    // destination frames must not overlap each other, and no destination plane's span may touch a source plane's
+    if (nout > 1 && (a.dst_strideY < (long long)(height - 1) * a.dst_pitchY + a.rowY || a.dst_strideUV < (long long)(hUV - 1) * a.dst_pitchUV + a.rowUV))
+        refuse("destination frames overlap each other");
+    const Span sspan[3] = {plane_span(a.srcY, a.src_strideY, a.src_pitchY, a.rowY, height, nsrc), plane_span(a.srcU, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc),
+                           plane_span(a.srcV, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc)};
+    const Span dspan[3] = {plane_span(a.dstY, a.dst_strideY, a.dst_pitchY, a.rowY, height, nout), plane_span(a.dstU, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout),
+                           plane_span(a.dstV, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout)};
+    for (int i = 0; i < nplanes; ++i)
+        for (int j = 0; j < nplanes; ++j)
+            if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place rendering)");
+    // (an interleaved batch has null V planes, which count as aligned: surface_batch drops whatever the descriptor holds there)
+    auto al16 = [](const void* p, long long stride, int pitch) { return (uintptr_t)p % 16 == 0 && stride % 16 == 0 && pitch % 16 == 0; };
+    a.vec = al16(a.srcY, a.src_strideY, a.src_pitchY) && al16(a.srcU, a.src_strideUV, a.src_pitchUV) && al16(a.srcV, a.src_strideUV, a.src_pitchUV) &&
+            al16(a.dstY, a.dst_strideY, a.dst_pitchY) && al16(a.dstU, a.dst_strideUV, a.dst_pitchUV) && al16(a.dstV, a.dst_strideUV, a.dst_pitchUV);
+    c->bind();
+    if (adaptive) {
+        DevBuf<RenderAdaptiveEntry> dplan;
+        dplan.upload(aentries, c->stream);
+        const int sp_ = c->prof_begin("kfm_render_adaptive_kernel");
+        AMT_HIP(launch_kfm_render_adaptive(c->stream, a, dplan.get(), nout));
+        c->prof_end(sp_);
+        AMT_HIP(hipStreamSynchronize(c->stream));      // the plan's device copy dies with this call
+        return;
+    }
+    DevBuf<RenderEntry> dplan;
+    dplan.upload(entries, c->stream);
+    const bool planes = !s.interleaved && !s.shift;                                  // planar LSB: the plain kernel, as before
+    const int sp_ = c->prof_begin(planes ? "kfm_render_kernel" : "kfm_render_surfaces_kernel");
+    AMT_HIP(planes ? launch_kfm_render(c->stream, a, dplan.get(), nout) : launch_kfm_render_surfaces(c->stream, a, s.interleaved, s.shift, dplan.get(), nout));
+    c->prof_end(sp_);
+    AMT_HIP(hipStreamSynchronize(c->stream));          // the plan's device copy dies with this call
+}
 } // namespace
 
 extern "C" {
@@ -58,72 +153,14 @@ int amtgpu_kfm_render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first
                       const AmtGpuRenderFrame* plan, int nout, int thresh, const AmtGpuSurfaces* dst)
 {
     if (!c) return 0;
-    return guard(c, [&] {
-        if (nout < 0) refuse("negative output frame count");
-        if (nout == 0) return;
-        if (!plan) refuse("null plan");
-        if (width <= 0 || height < 4 || (width & 1) || (height & 1)) refuse("width and height must be even and height at least 4 (4:2:0 field pairs)");
-        const SurfaceBatch s = render_surfaces(src, "source", width), d = render_surfaces(dst, "destination", width);
-        if (src->bits != dst->bits) refuse("source and destination differ in bits");
-        if (s.interleaved != d.interleaved || s.shift != d.shift)
-            refuse("source and destination are not in kind (equal bits, interleaved and MSB shift): the renderer converts no layouts");
-        if (src_first < 0 || nsrc <= 0 || (long long)src_first + nsrc > clip_frames) refuse("the source batch does not lie inside the clip");
-        const int es = s.es, wUV = width >> 1, hUV = height >> 1;
-        const int maxv = s.shift ? (1 << src->bits) - 1 : es == 1 ? 255 : 65535;        // of a sample: MSB-aligned ones are compared shifted
-        const int nplanes = s.interleaved ? 2 : 3;                                       // Y, then U and V or the one UV plane
+    return guard(c, [&] { render(c, src, src_first, nsrc, clip_frames, width, height, plan, nout, AMTGPU_DEINT_LINE, thresh, dst); });
+}
 
-        std::vector<RenderEntry> entries((size_t)nout);
-        auto local = [&](long long n, int i, const char* what) {
-            if (n < src_first || n >= (long long)src_first + nsrc)
-                refuse("plan entry " + std::to_string(i) + ": " + what + " " + std::to_string(n) + " is outside the batch [" + std::to_string(src_first) + ", " +
-                       std::to_string(src_first + nsrc) + ")");
-            return (int)(n - src_first);
-        };
-        for (int i = 0; i < nout; ++i) {
-            const AmtGpuRenderFrame& f = plan[i];
-            if (f.kind < AMTGPU_RENDER_WEAVE || f.kind > AMTGPU_RENDER_BOB_BOTTOM) refuse("plan entry " + std::to_string(i) + ": kind outside 0..2");
-            if (f.kind != AMTGPU_RENDER_WEAVE && f.top != f.bottom) refuse("plan entry " + std::to_string(i) + ": a BOB entry needs top == bottom");
-            RenderEntry& e = entries[(size_t)i];
-            e.kind = f.kind;
-            e.top = local(f.top, i, "top frame");
-            e.bottom = local(f.bottom, i, "bottom frame");
-            e.other = e.top;
-            if (thresh >= 0 && f.kind == AMTGPU_RENDER_BOB_TOP && f.top >= 1) e.other = local((long long)f.top - 1, i, "the temporal neighbour");
-            if (thresh >= 0 && f.kind == AMTGPU_RENDER_BOB_BOTTOM && (long long)f.top + 1 < clip_frames) e.other = local((long long)f.top + 1, i, "the temporal neighbour");
-        }
-
-        RenderArgs a;
-        a.srcY = (const uint8_t*)s.Y; a.srcU = (const uint8_t*)s.U; a.srcV = (const uint8_t*)s.V;
-        a.dstY = (uint8_t*)d.Y; a.dstU = (uint8_t*)d.U; a.dstV = (uint8_t*)d.V;
-        a.src_strideY = s.strideY; a.src_strideUV = s.strideUV; a.dst_strideY = d.strideY; a.dst_strideUV = d.strideUV;
-        a.src_pitchY = s.pitchY * es; a.src_pitchUV = s.pitchUV * es; a.dst_pitchY = d.pitchY * es; a.dst_pitchUV = d.pitchUV * es;
-        a.rowY = width * es; a.rowUV = (s.interleaved ? 2 * wUV : wUV) * es;
-        a.H = height; a.HUV = hUV;
-        a.es = es;
-        a.thresh = thresh < 0 ? -1 : std::min(thresh, maxv);
-        // destination frames must not overlap each other, and no destination plane's span may touch a source plane's
-        if (nout > 1 && (a.dst_strideY < (long long)(height - 1) * a.dst_pitchY + a.rowY || a.dst_strideUV < (long long)(hUV - 1) * a.dst_pitchUV + a.rowUV))
-            refuse("destination frames overlap each other");
-        const Span sspan[3] = {plane_span(a.srcY, a.src_strideY, a.src_pitchY, a.rowY, height, nsrc), plane_span(a.srcU, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc),
-                               plane_span(a.srcV, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc)};
-        const Span dspan[3] = {plane_span(a.dstY, a.dst_strideY, a.dst_pitchY, a.rowY, height, nout), plane_span(a.dstU, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout),
-                               plane_span(a.dstV, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout)};
-        for (int i = 0; i < nplanes; ++i)
-            for (int j = 0; j < nplanes; ++j)
-                if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place rendering)");
-        // (an interleaved batch has null V planes, which count as aligned: surface_batch drops whatever the descriptor holds there)
-        auto al16 = [](const void* p, long long stride, int pitch) { return (uintptr_t)p % 16 == 0 && stride % 16 == 0 && pitch % 16 == 0; };
-        a.vec = al16(a.srcY, a.src_strideY, a.src_pitchY) && al16(a.srcU, a.src_strideUV, a.src_pitchUV) && al16(a.srcV, a.src_strideUV, a.src_pitchUV) &&
-                al16(a.dstY, a.dst_strideY, a.dst_pitchY) && al16(a.dstU, a.dst_strideUV, a.dst_pitchUV) && al16(a.dstV, a.dst_strideUV, a.dst_pitchUV);
-        c->bind();
-        DevBuf<RenderEntry> dplan;
-        dplan.upload(entries, c->stream);
-        const bool planes = !s.interleaved && !s.shift;                                  // planar LSB: the plain kernel, as before
-        const int sp_ = c->prof_begin(planes ? "kfm_render_kernel" : "kfm_render_surfaces_kernel");
-        AMT_HIP(planes ? launch_kfm_render(c->stream, a, dplan.get(), nout) : launch_kfm_render_surfaces(c->stream, a, s.interleaved, s.shift, dplan.get(), nout));
-        c->prof_end(sp_);
-        AMT_HIP(hipStreamSynchronize(c->stream));          // the plan's device copy dies with this call
-    });
+int amtgpu_kfm_render_deint(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
+                            const AmtGpuRenderFrame* plan, int nout, int deint, int thresh, const AmtGpuSurfaces* dst)
+{
+    if (!c) return 0;
+    return guard(c, [&] { render(c, src, src_first, nsrc, clip_frames, width, height, plan, nout, deint, thresh, dst); });
 }
 
 } // extern "C"

@@ -114,6 +114,11 @@ hipError_t launch_kfm_render(hipStream_t st, const RenderArgs& a, const RenderEn
 // and go to launch_kfm_render).  interleaved: srcU / dstU are the UV planes, a.rowUV their width * es bytes, srcV / dstV unused.
 // shift != 0 (es 2): MSB-aligned containers; interpolated samples are container >> shift, stored << shift, and a.thresh counts samples
 hipError_t launch_kfm_render_surfaces(hipStream_t st, const RenderArgs& a, int interleaved, int shift, const RenderEntry* dplan, int nout);
+// render_adaptive_kernels.hip: the same frames on planar LSB planes with the bobs' missing rows from the edge-directed, motion-adaptive
+// rule.  A bob entry reads both neighbours of n: prev / next are n - 1 / n + 1, batch-local, and n itself where the
+// clip has none (and in WEAVE entries), so that nothing else is ever addressed.  a.thresh is not read
+struct RenderAdaptiveEntry { int kind, top, bottom, prev, next; };
+hipError_t launch_kfm_render_adaptive(hipStream_t st, const RenderArgs& a, const RenderAdaptiveEntry* dplan, int nout);
 
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,

@@ -676,6 +676,33 @@ int  amtgpu_kfm_render_plan(const uint8_t* cadence, const uint8_t* phase, int nf
  * call returns */
 int  amtgpu_kfm_render(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
                        const AmtGpuRenderFrame* plan, int nout, int thresh, const AmtGpuSurfaces* dst);
+/* amtgpu_kfm_render with a choice of the rule that fills a BOB entry's missing rows.  WEAVE entries and the kept rows of a bob are copied
+ * exactly as amtgpu_kfm_render copies them under either rule.
+ * deint == AMTGPU_DEINT_LINE is amtgpu_kfm_render argument for argument: the same path, the same bytes, surfaces included.
+ * deint == AMTGPU_DEINT_ADAPTIVE is an edge-directed, motion-adaptive bob: integer, exact, no threshold.  Each plane
+ * by its own width w and height h, containers as stored (no masking to bits), signed integers, >> on non-negative values only.  With
+ * C = frame n, P = frame n - 1 (n == 0: C), N = frame n + 1 (n == clip_frames - 1: C), (A, B) = (P, C) for BOB_TOP and (C, N) for
+ * BOB_BOTTOM, rows y1m = y-1 >= 0 ? y-1 : y+1, y1p = y+1 < h ? y+1 : y-1, y2m = y-2 >= 0 ? y-2 : y, y2p = y+2 < h ? y+2 : y, columns
+ * X(k) = min(max(x + k, 0), w - 1), U = C[y1m], D = C[y1p], a missing row y is per pixel
+ *   c = U[x]; e = D[x]; d = (A[y][x] + B[y][x]) >> 1
+ *   diff = max(|A[y][x] - B[y][x]| >> 1, (|P[y1m][x] - c| + |P[y1p][x] - e|) >> 1, (|N[y1m][x] - c| + |N[y1p][x] - e|) >> 1)
+ *   pred = (c + e) >> 1; score = |U[X(-1)] - D[X(-1)]| + |c - e| + |U[X(1)] - D[X(1)]| - 1
+ *   for j = -1, -2 and then for j = +1, +2 (+-2 only where +-1 was taken), against the running score:
+ *     s = |U[X(j-1)] - D[X(-j-1)]| + |U[X(j)] - D[X(-j)]| + |U[X(j+1)] - D[X(-j+1)]|;  s < score: score = s, pred = (U[X(j)] + D[X(-j)]) >> 1
+ *   b = (A[y2m][x] + B[y2m][x]) >> 1; f = (A[y2p][x] + B[y2p][x]) >> 1
+ *   diff = max(diff, min(d - e, d - c, max(b - c, f - e)), -max(d - e, d - c, min(b - c, f - e)))
+ *   output = pred clamped into [d - diff, d + diff]   (always inside the container's range: there is no further clamp)
+ * Still areas weave (the band closes around the temporal mean d), moving areas interpolate along the edge.  No real footage has been
+ * judged: the rule is argued from its construction and a diagonal known answer, not from measured picture quality.
+ * ADAPTIVE takes every refusal of amtgpu_kfm_render, and refuses as well: thresh != -1; a deint that is neither constant; a BOB entry
+ * whose frame n - 1 (n >= 1) or n + 1 (n + 1 < clip_frames) is outside the batch -- both bobs read both neighbours; and any pair that is
+ * not planar and LSB-aligned: NV12 / P010 / P012 and planar MSB surfaces under the adaptive rule are not built yet.
+ * The bytes depend on the clip and the plan alone: batches with one frame of halo on either side give the bytes of one call.
+ * Synchronises, and the plan's device copy lives for the one launch, as amtgpu_kfm_render */
+#define AMTGPU_DEINT_LINE     0   /* the rule of amtgpu_kfm_render: line average, temporal mean within thresh */
+#define AMTGPU_DEINT_ADAPTIVE 1   /* edge-directed, motion-adaptive; thresh must be -1 */
+int  amtgpu_kfm_render_deint(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
+                             const AmtGpuRenderFrame* plan, int nout, int deint, int thresh, const AmtGpuSurfaces* dst);
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
