@@ -77,7 +77,8 @@ def needs_build(srcs) -> bool:
 
 
 def build_variant(name: str, defines, extra_flags=(), file_flags=None) -> str:
-    """An instrumented copy of the library (tools/phase_timing.py): amatsukaze_amd/libamt_gpu_<name>.so
+    """An instrumented copy of the library -- shape knobs or AMT_TRACE_CALLS, the names csrc/build_knobs.h allows (tools/ab_lin.sh,
+    tools/flags_bench.py): amatsukaze_amd/libamt_gpu_<name>.so
     file_flags: {source file: [flags]} on top of EXTRA_FLAGS, for experiments with one translation unit's compiler options"""
     file_flags = file_flags or {}
     out = os.path.join(HERE, f"libamt_gpu_{name}.so")

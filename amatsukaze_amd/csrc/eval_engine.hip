@@ -4,8 +4,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 int AmtGpuContext::prof_id(const char* name)
@@ -77,9 +75,6 @@ EvalEngine::EvalEngine(AmtGpuContext* ctx, std::vector<EvalLogoSpec> specs, std:
       prof_name_(prof_name)
 {
     ctx_->bind();
-#ifdef AMT_EXPERIMENT
-    if (const char* e = std::getenv("AMTGPU_G")) group_frames_ = std::atoi(e);       // instrumented builds only
-#endif
     constexpr int kPlaneCapMax = kEvalThreads * kEvalStage;                            // floats per LDS plane
     const int nl = (int)specs_.size();
     std::vector<EvalLogoDev> hl(nl);
@@ -180,14 +175,6 @@ EvalEngine::EvalEngine(AmtGpuContext* ctx, std::vector<EvalLogoSpec> specs, std:
         D.out_off = S.out_off;
         D.lp = lp;
     }
-#ifdef AMT_EXPERIMENT
-    if (std::getenv("AMTGPU_VERBOSE")) {
-        for (int i = 0; i < nl; ++i)
-            fprintf(stderr, "[amtgpu] eval logo %d: %dx%d count=%d bands=%d lp=%d\n", i, hl[i].w, hl[i].h, hl[i].count, hl[i].nbands, hl[i].lp);
-        for (const EvalBand& B : bands_)
-            fprintf(stderr, "[amtgpu]   band logo=%d slots=%d npix=%d y0=%d nrows=%d x0=%d bw=%d lp=%d\n", B.logo, B.nslots, B.npix, B.y0, B.nrows, B.x0, B.bw, B.lp);
-    }
-#endif
     d_logos_.upload(hl, ctx_->stream);
     d_bands_.upload(bands_, ctx_->stream);
     d_fades_.upload(fades_, ctx_->stream);
@@ -247,9 +234,6 @@ bool EvalEngine::pair_eligible()
 {
     if (pair_state_ >= 0) return pair_state_ == 1;
     pair_state_ = 0;
-#ifdef AMT_EXPERIMENT
-    if (std::getenv("AMTGPU_NO_PAIR")) return false;       // instrumented builds: time the generic kernel on the scan
-#endif
     if (fades_.size() != 2 || fades_[0] != 0.0f || fades_[1] != 1.0f || specs_.empty()) return false;
     for (const EvalLogoSpec& S : specs_) {
         const int w = S.planes.w, h = S.planes.h;

@@ -28,7 +28,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <algorithm>
-#include <cstdlib>
 
 #include "eval_plan.h"
 #include "kernels.hpp"
@@ -76,14 +75,8 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
                           const float* __restrict__ fades, int nfades, int fade0,
                           const pix_t* __restrict__ Y, const int* __restrict__ frame_map, long long frame_stride, int pitch,
                           float maxv, int nframes, int G, int ngroups, float* __restrict__ out, int out_frame_stride,
-                          int take_abs, int plane_cap, int sc_pitch, int dbg_in, int bid, int scatter)
+                          int take_abs, int plane_cap, int sc_pitch, int bid, int scatter)
 {
-#ifdef AMT_EXPERIMENT
-    const int dbg = dbg_in;      // timing ablations of instrumented builds only (amatsukaze_amd/build.py build_variant)
-#else
-    constexpr int dbg = 0;
-    (void)dbg_in;
-#endif
     extern __shared__ float lds[];
     float* const planes = lds;                       // [FPI][S: source pixels | BG: a*s + b*maxv][plane_cap]  the band's rows
     float* const sc = lds + 2 * FPI * plane_cap;     // [FPI][nfades][sc_pitch]  per-pixel terms of the current (band, frames)
@@ -106,13 +99,6 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
     if (tid < G * nfades) accs[tid] = 0.0f;          // G * nfades <= 256 (host)
     const int fade_bits = __builtin_bit_cast(int, fades[fade0 + min(lane, nfades - 1)]);   // lane f holds fade f (nfades <= 64)
 
-#ifdef AMT_FUSED_TIMING
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tprev = clock64();
-#define AMT_TICK(k) do { const long long t_ = clock64(); tacc[k] += t_ - tprev; tprev = t_; } while (0)
-#else
-#define AMT_TICK(k) do { } while (0)
-#endif
     int it = 0;                                      // (band, frame) iterations done
     int prev_npix = 0, prev_g = 0, prev_rows = 0;    // the iteration waiting to be summed: its band's pixels, first frame, score rows
     for (int bi = 0; bi < L.nbands; ++bi) {
@@ -130,10 +116,6 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
 #pragma unroll
         for (int t = 0; t < 25; ++t) K[t] = gld<f2>(gK, ((unsigned)t * spad + slot) * 8u);
         const unsigned m1 = min(m0 + 1u, (unsigned)L.count - 1u);
-#ifdef AMT_FUSED_TIMING
-        if (K[24].x == 123456.0f) tacc[7] += 1;      // force the tap loads to land before the tick
-#endif
-        AMT_TICK(0);
 
         for (int g = 0; g < gcount; g += FPI, ++it) {
             const int nfr = min(FPI, gcount - g);
@@ -152,7 +134,7 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
             // score rows below -- stages nothing, so that the sum runs beside the staging loads' latency.
             const int sumwave = (it + kFusedWaves - 1) & (kFusedWaves - 1);
             const int worker = (wave - sumwave + kFusedWaves - 1) & (kFusedWaves - 1);       // 0..2 stage, 3 = sumwave
-            for (int rg = worker * kStageRows; rg < ((dbg & 2) || worker == kFusedWaves - 1 ? 0 : B.nrows); rg += kStageRows * (kFusedWaves - 1)) {
+            for (int rg = worker * kStageRows; rg < (worker == kFusedWaves - 1 ? 0 : B.nrows); rg += kStageRows * (kFusedWaves - 1)) {
                 const int y = B.y0 + rg;                                     // logo row of the group's first row
                 for (int xg = bx0; xg < bx1; xg += 256) {
                     const int x = xg + 4 * lane;
@@ -227,16 +209,13 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
                     }
                 }
             }
-            AMT_TICK(1);
             // ---- 2. one wave adds the previous iteration's per-pixel terms in raster order (the others wait at B1, their
             //         SIMDs run other workgroups' fade loops meanwhile) ----
-            if (!(dbg & 1) && it > 0 && wave == sumwave && lane < prev_rows) {
+            if (it > 0 && wave == sumwave && lane < prev_rows) {
                 float* a = accs + prev_g * nfades + lane;            // row fr*nfades + f belongs to frame prev_g + fr
                 *a = ordered_row_sum(sc + lane * sc_pitch, prev_npix, *a);
             }
-            AMT_TICK(2);
             __syncthreads();                         // B1: planes complete, score rows free again
-            AMT_TICK(3);
 #pragma unroll
             for (int fr = 0; fr < FPI; ++fr) {
             if (fr >= nfr) break;
@@ -257,10 +236,6 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
                     BG[3 * r + 2] = f2{pb[0], pb[5]};
                 }
             }
-#ifdef AMT_FUSED_TIMING
-            if (act && S[14].x == 123456.0f) tacc[7] += 1;
-#endif
-            AMT_TICK(4);
             // ---- 5. fade loop: registers only.  Two register sets alternate so that the scale gather issued by
             //      evaluation f is consumed after evaluation f+1's math (a full iteration of latency cover, no copies) ----
             if (act) {
@@ -306,18 +281,17 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
                     if (npx > 1) row[1] = score_term(R.y, s1.x, s1.y);
                     __builtin_amdgcn_sched_barrier(0);
                 };
-                const int nfe = (dbg & 4) ? 0 : nfades;
-                if (nfe > 0) {
+                if (nfades > 0) {
                     f2 RA, a0, a1, RB, b0, b1;
                     eval(0, RA, a0, a1);
                     int f = 1;
-                    for (; f + 1 < nfe; f += 2) {
+                    for (; f + 1 < nfades; f += 2) {
                         eval(f, RB, b0, b1);
                         consume(f - 1, RA, a0, a1);
                         eval(f + 1, RA, a0, a1);
                         consume(f, RB, b0, b1);
                     }
-                    if (f < nfe) {
+                    if (f < nfades) {
                         eval(f, RB, b0, b1);
                         consume(f - 1, RA, a0, a1);
                         consume(f, RB, b0, b1);
@@ -328,9 +302,7 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
             }
             }
             prev_npix = B.npix; prev_g = g; prev_rows = nfr * nfades;
-            AMT_TICK(5);
             __syncthreads();                         // B0: score rows complete, windows consumed
-            AMT_TICK(6);
         }
     }
     // ---- last iteration's sum, then the results ----
@@ -341,12 +313,6 @@ void logo_eval_fused_body(const EvalLogoDev* __restrict__ logos, const EvalBand*
         }
     }
     __syncthreads();
-#ifdef AMT_FUSED_TIMING
-    if (lane == 0 && blockIdx.x == gridDim.x / 2) {
-        long long* tb = reinterpret_cast<long long*>(out + (long long)nframes * out_frame_stride);   // host reserves room
-        for (int k = 0; k < 8; ++k) tb[wave * 8 + k] = tacc[k];
-    }
-#endif
     if (tid < gcount * nfades) {
         const int g = tid / nfades, f = tid - g * nfades;
         float r = accs[tid] / L.blackScore;
@@ -365,12 +331,12 @@ __global__ __launch_bounds__(kEvalThreads) __attribute__((amdgpu_waves_per_eu(AM
 void logo_eval_fused_kernel(const EvalLogoDev* __restrict__ logos, const EvalBand* __restrict__ bands, const float* __restrict__ fades,
                             int nfades, int fade0, const pix_t* __restrict__ Y, const int* __restrict__ frame_map,
                             long long frame_stride, int pitch, float maxv, int nframes, int G, int ngroups, float* __restrict__ out,
-                            int out_frame_stride, int take_abs, int plane_cap, int sc_pitch, int dbg, const int* __restrict__ nframes_dev,
+                            int out_frame_stride, int take_abs, int plane_cap, int sc_pitch, const int* __restrict__ nframes_dev,
                             int scatter, int nlogos, int fade_chunk)
 {
     if (!nframes_dev) {
         logo_eval_fused_body<pix_t, FPI>(logos, bands, fades, nfades, fade0, Y, frame_map, frame_stride, pitch, maxv, nframes, G, ngroups, out,
-                                         out_frame_stride, take_abs, plane_cap, sc_pitch, dbg, (int)blockIdx.x, scatter);
+                                         out_frame_stride, take_abs, plane_cap, sc_pitch, (int)blockIdx.x, scatter);
         return;
     }
     // listed re-evaluation (decision guard of the linear mode): the number of frames present sits on the device and is usually a
@@ -384,7 +350,7 @@ void logo_eval_fused_kernel(const EvalLogoDev* __restrict__ logos, const EvalBan
         const int pair = b / nchunks, f0 = (b - pair * nchunks) * fade_chunk;
         const int nf = fade_chunk > 0 ? min(fade_chunk, nfades - f0) : nfades;
         logo_eval_fused_body<pix_t, FPI>(logos, bands, fades, nf, fade0 + f0, Y, frame_map, frame_stride, pitch, maxv, present, G, groups, out,
-                                         out_frame_stride, take_abs, plane_cap, sc_pitch, dbg, pair, scatter);
+                                         out_frame_stride, take_abs, plane_cap, sc_pitch, pair, scatter);
         __syncthreads();
     }
 }
@@ -402,16 +368,6 @@ hipError_t launch_logo_eval_fused(hipStream_t st, int bits, const EvalLogoDev* d
     if (nframes <= 0 || nlogos <= 0 || nfades <= 0) return hipSuccess;
     if (scatter && !dframe_map) return hipErrorInvalidValue;
     if (nfades > kEvalMaxFades || G * nfades > kEvalThreads || plane_cap > kEvalThreads * kEvalStage) return hipErrorInvalidValue;
-    // Instrumented builds only (-DAMT_EXPERIMENT, build.py build_variant): AMTGPU_DBG bit 0 skips the sum, 1 the staging,
-    // 2 the fade loop (timing ablations, WRONG results); AMTGPU_LDSPAD inflates the LDS request to lower the occupancy;
-    // AMTGPU_FPI=1 forces one frame per iteration.  The release library reads no environment variable here.
-#ifdef AMT_EXPERIMENT
-    static const int dbg = std::getenv("AMTGPU_DBG") ? std::atoi(std::getenv("AMTGPU_DBG")) : 0;
-    static const int ldspad = std::getenv("AMTGPU_LDSPAD") ? std::atoi(std::getenv("AMTGPU_LDSPAD")) : 0;
-    static const int fpi_env = std::getenv("AMTGPU_FPI") ? std::atoi(std::getenv("AMTGPU_FPI")) : 0;
-#else
-    constexpr int dbg = 0, ldspad = 0, fpi_env = 0;
-#endif
     const int ngroups = (nframes + G - 1) / G;
     const float maxv = (float)((1 << bits) - 1);
     const int sc_pitch = kEvalBandPixels + kEvalScorePad;
@@ -420,13 +376,13 @@ hipError_t launch_logo_eval_fused(hipStream_t st, int bits, const EvalLogoDev* d
     const int nchunks = fade_chunk > 0 ? (nfades + fade_chunk - 1) / fade_chunk : 1;
     dim3 grid(dnframes ? (unsigned)std::min<long long>((long long)ngroups * nlogos * nchunks, 1024) : (unsigned)((long long)ngroups * nlogos));
     // two frames per iteration while the planes and score rows of both fit half a CU's LDS (two workgroups per CU)
-    int fpi = fpi_env > 0 ? std::min(2, fpi_env) : 2;
+    int fpi = 2;
     if (G < 2 || fused_lds_bytes(plane_cap, nfades, sc_pitch, G, 2) > 80 * 1024 - 512) fpi = 1;
-    const size_t lds = fused_lds_bytes(plane_cap, nfades, sc_pitch, G, fpi) + (size_t)ldspad;
+    const size_t lds = fused_lds_bytes(plane_cap, nfades, sc_pitch, G, fpi);
 #define AMT_LAUNCH(T, F)                                                                                                          \
     hipLaunchKernelGGL((logo_eval_fused_kernel<T, F>), grid, dim3(kEvalThreads), lds, st, dlogos, dbands, dfades, nfades, fade0,         \
                        (const T*)dY, dframe_map, frame_stride_elems, pitch, maxv, nframes, G, ngroups, dout, out_frame_stride, take_abs, \
-                       plane_cap, sc_pitch, dbg, dnframes, scatter, nlogos, fade_chunk)
+                       plane_cap, sc_pitch, dnframes, scatter, nlogos, fade_chunk)
     if (fpi == 2) { if (bits <= 8) AMT_LAUNCH(uint8_t, 2); else AMT_LAUNCH(uint16_t, 2); }
     else { if (bits <= 8) AMT_LAUNCH(uint8_t, 1); else AMT_LAUNCH(uint16_t, 1); }
 #undef AMT_LAUNCH

@@ -386,13 +386,6 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
     const float yscale = 0.125f;                                                     // mean (gray levels) -> bins
     const float ydq = A.ydq, ywin = A.ywin;
 
-#ifdef AMT_LIN_TIMING
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tprev = clock64();
-#define AMT_LTICK(k) do { const long long t_ = clock64(); tacc[k] += t_ - tprev; tprev = t_; } while (0)
-#else
-#define AMT_LTICK(k) do { } while (0)
-#endif
     // the fades, wave-uniform: scalar register PAIRS {fade 2j, fade 2j + 1} (operands of the packed multiply-adds) and the last one
     static_assert(NF % 2 == 1, "the fades are walked in pairs plus the last one");
     constexpr int NP = (NF - 1) / 2;
@@ -460,20 +453,14 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
     }
     if (i0 < ntl) for (;;) {
         const f2 PQ = px.PQ;                                       // (B' below overwrites the pixel; the terms are this pixel's)
-        AMT_LTICK(0);
         // ---- A. ONE window evaluation for both operands: R = {corr(s), corr(bg)}, M = {mean(s), mean(bg)} ----
         // (the taps' {k, k} broadcasts live in the multiply-adds' op_sel: eval_tile_stage.h pk_fma_tap)
         f2 R, M;
         {
             unsigned wrow[5];
             px.rows(plane_base, wrow);
-#ifdef AMT_LIN_NO_EVAL                                          // (ablations of the instrumented builds: wrong results, timing only)
-            R = px.Kp[0]; M = px.Kp[1] + f2{100.0f, 120.0f};
-#else
             window_eval_streamed<sizeof(pix_t) == 1>(wrow, px.Kp, M, R);         // idle lanes read the tile's first window: finite values, zero taps
-#endif
         }
-        AMT_LTICK(2);
         // ---- B. bins, as floats: y = position of the interpolated mean in bins (+ the window's half-width), floor(y) its bin, fract(y)
         //      its distance from the bin edge below.  The bin select is discontinuous (LogoScan.hpp:304): for a mean within bin_eps of an
         //      edge -- about 3e-4 of all (pixel, fade) pairs -- the mean is evaluated exactly as the reference does and ITS bin is taken ----
@@ -504,7 +491,6 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
         // does (from the frame itself), its bin, and -- where that differs -- the difference of the two terms as a correction to the
         // frame's sum.  (Rounds 2-5 re-evaluated the mean on the spot, for one or two lanes while sixty-two waited: 14 % of the kernel
         // and, through the registers its window took, the reason the loop could not carry more.)
-#ifndef AMT_LIN_NO_FIXUP
         {
             const bool near_edge = px.act() && emin < ywin;
             if (__builtin_amdgcn_ballot_w64(near_edge) != 0) {         // wave-uniform
@@ -523,8 +509,6 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
                 }
             }
         }
-#endif
-        AMT_LTICK(3);
         // ---- B'. a new tile next: its pixel and taps are requested BEFORE the raw samples -- vector-memory loads return in order, and
         //      the taps are what the next iteration needs first ----
         const bool new_tile = i1 < ntl && i1 != i0;
@@ -543,7 +527,6 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
         //      DPP steps; lane 0 of the quad adds the sums to the quad's running sums of the frame in LDS (48 bytes per quad: 16 partial
         //      sums per fade, added up at the very end).  A lane's cells are its own and LDS operations of a wave complete in order: no
         //      barrier, no atomics. ----
-#ifndef AMT_LIN_NO_FLUSH
         {
             typedef __attribute__((address_space(3))) f4* lds_quad;
             const float R0 = R.x, dR = R.y - R.x;
@@ -596,18 +579,13 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
                 cell[0] = cell[0] + mine;
             }
         }
-#endif
-        AMT_LTICK(4);
         if (new_tile) px.landed();
-        AMT_LTICK(5);
         // ---- C. the next iteration's tile into the plane, the raw samples of the one after.  The request is issued on EVERY trip round the
         //      loop (past the wave's last iteration it repeats the previous one): the compiler counts the loads in flight per path, and a
         //      path without the six requests behind the taps would turn its wait for the taps at the loop head into a wait for everything ----
         if (i1 >= ntl) break;
         st.template landed<0>();
-#ifndef AMT_LIN_NO_CONVERT
         st.convert();
-#endif
         {
             int i2 = i1, g2 = g1;
             advance(i2, g2);
@@ -617,13 +595,8 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
                 st.setup_units(Lp, Xp, T, (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
                 iu = i2;
             }
-#if defined(AMT_LIN_RAW_SAMEFRAME)                              // (ablation: every request hits the cache -- what the raw loads' LATENCY costs)
-            st.request(frame_desc<pix_t>(A.Y, A.frame_map, A.frame_stride, 0));
-#else
             st.request(frame_desc<pix_t>(A.Y, A.frame_map, A.frame_stride, F0 + (more ? g2 : g1)));
-#endif
         }
-        AMT_LTICK(1);
         i0 = i1; g0 = g1;
         advance(i1, g1);
     }
@@ -631,12 +604,6 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
     if (wave < ntl) st.template landed<0>();
     if (lane == 0) qcount[wave] = qn;
     __syncthreads();
-#ifdef AMT_LIN_TIMING
-    if (lane == 0 && logo == 0 && grp == A.ngroups / 2 && wave < 4) {      // a workgroup of logo 0 (the deint logo)
-        long long* tb = reinterpret_cast<long long*>(A.out + (long long)A.nframes * A.out_frame_stride);      // host reserves room
-        for (int k = 0; k < 8; ++k) tb[wave * 8 + k] = tacc[k];
-    }
-#endif
     // (the thread index is re-derived: kept across the loop it would be one register too many)
     const int tid_end = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     // ---- the listed pairs, all threads at once: exact mean -> exact bin -> where it differs from the tentative one, the correction

@@ -90,18 +90,6 @@ void logo_eval_pair_kernel(const PairLaunch A)
     f2* const planes = reinterpret_cast<f2*>(lds);                       // [kTileWaves][kTileCap] {s, bg}: a wave's own tile
     float* const rows = lds + kTileWaves * kTileCap * 2;                 // [2][2 G][kPairRowPitch] per-pixel terms of a band
 
-#ifdef AMT_PAIR_TIMING
-    long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tprev = clock64();
-#define AMT_PTICK(k) do { const long long t_ = clock64(); tacc[k] += t_ - tprev; tprev = t_; } while (0)
-#define AMT_PDUMP() do { if (lane == 0 && logo == 0 && grp == A.ngroups / 2) { \
-        long long* tb = reinterpret_cast<long long*>(A.out + (long long)A.nframes * A.out_frame_stride);   /* the host reserves room */ \
-        for (int k = 0; k < 8; ++k) tb[wave * 8 + k] = tacc[k]; \
-        tb[16 * 8 + wave] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   /* HW_REG_HW_ID: SIMD id in bits 5:4 */ } } while (0)
-#else
-#define AMT_PTICK(k) do { } while (0)
-#define AMT_PDUMP() do { } while (0)
-#endif
     const int G = A.G;
     const WgMap wm = wg_map_shared_rows((int)blockIdx.x, A.nlogos, A.ngroups);
     if (wm.grp >= A.ngroups) return;                               // (the grid is whole blocks of eight groups; a whole workgroup leaves: no barrier is missed)
@@ -113,7 +101,6 @@ void logo_eval_pair_kernel(const PairLaunch A)
     const EvalLogoDev* const Lp = A.logos + logo;
     const TileLogoDev* const Xp = A.tls + logo;
     const int nbands = Xp->nbands;
-    constexpr int ES = (int)sizeof(pix_t);
 
     if (wave == kTileWaves) {
         // ---------------- the summing wave: after the barrier that ends band b it adds band b's rows ----------------
@@ -126,22 +113,14 @@ void logo_eval_pair_kernel(const PairLaunch A)
         const const_band_ptr bd = (const_band_ptr)Xp->bands;
         for (int b = 0; b < nbands; ++b) {
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            AMT_PTICK(5);
             const int npix = bd[b].npix;
-#ifndef AMT_PAIR_NO_SUM                                         // (ablations of the instrumented builds: wrong results, timing only)
             if (lane < 2 * gcount) acc = ordered_row_sum(rows + ((b & 1) * 2 * G + lane) * kPairRowPitch, npix, acc);
-#endif
-#ifdef AMT_PAIR_TIMING
-            asm volatile("" : "+v"(acc));
-#endif
-            AMT_PTICK(0);
         }
         if (lane < 2 * gcount) {
             float r = acc / Lp->blackScore;
             if (A.take_abs) r = fabsf(r);
             A.out[(long long)(F0 + (lane >> 1)) * A.out_frame_stride + Lp->out_off + (lane & 1)] = r;
         }
-        AMT_PDUMP();
         return;
     }
 
@@ -184,26 +163,13 @@ void logo_eval_pair_kernel(const PairLaunch A)
     for (int it = 0; it < niter; ++it) {
         const bool band_end = g + 1 == gcount;
         // ---- 1. the iteration's tile: raw -> {s, bg} pairs in this wave's plane ----
-        AMT_PTICK(6);
-#ifdef AMT_PAIR_TIMING
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");       // (timing build: the wait for the raw samples on its own)
-        AMT_PTICK(7);
-#endif
-#ifndef AMT_PAIR_NO_CONVERT
         st.convert();
-#endif
-        AMT_PTICK(0);
         // ---- 2. the next iteration's raw samples travel during the evaluation (past the last iteration: a repeat nobody reads) ----
         if (band_end && b + 1 < nbands) {
             fetch_tile(T, tiles + (b + 1) * kTileWaves);
             st.setup_units(T, lane);
         }
-#if defined(AMT_PAIR_RAW_SAMEFRAME)                             // (ablation: every request hits the cache -- separates the loads' latency from their issue cost)
-        st.request(frame_rsrc<pix_t>(A.Y, A.frame_map, A.frame_stride, 0));
-#elif !defined(AMT_PAIR_NO_RAW)
         st.request(frame_rsrc<pix_t>(A.Y, A.frame_map, A.frame_stride, F0 + (band_end ? 0 : g + 1)));
-#endif
-        AMT_PTICK(1);
         // ---- 3. both fades of the frame: one packed window evaluation ----
         // (the taps are loop-invariant: LICM would hoist their {k,k} broadcasts and keep 50 registers of copies; the empty asm
         //  makes them opaque per iteration and the broadcast folds into the multiply's op_sel)
@@ -212,30 +178,14 @@ void logo_eval_pair_kernel(const PairLaunch A)
         f2 W[25];
         unsigned wrow[5];
         px.rows(wrow);
-#ifdef AMT_PAIR_NO_EVAL
-        const f2 M = px.Kp[1] + f2{100.0f, 120.0f}, R = px.Kp[0];
-        (void)W;
-#else
         const f2 M = window_load_means(wrow, W);      // (issuing the reads before the next requests instead: 2.630 ms either way, round 5)
         const f2 R = window_corr_exact(px.Kp, W, M);
-#endif
-#ifdef AMT_PAIR_TIMING
-        { f2 Rt = R; asm volatile("" : "+v"(Rt)); }
-#endif
-        AMT_PTICK(2);
         // ---- 4. the previous iteration's terms -> the band's score rows, at the pixel's raster position; then this iteration's two
         //      scale gathers go straight into the registers the terms were read from (a copy would wait for them here) ----
-#ifndef AMT_PAIR_NO_FLUSH
         flush_terms();
-#endif
-#ifdef AMT_PAIR_NO_GATHER
-        psc0 = f2{1e-3f, 1.0f} + M; psc1 = f2{1e-3f, 1.0f} - M;
-#else
         psc0 = gld<f2>(gSc, __umul24(score_bin_bounded(M.x), nslots8) + px.slot8);
         psc1 = gld<f2>(gSc, __umul24(score_bin_bounded(M.y), nslots8) + px.slot8);
-#endif
         pR = R; pact = px.act;
-        AMT_PTICK(3);
         prow = (b & 1) * 2 * G + g * 2;
         if (band_end) {
             flush_terms();                                           // the band's rows are complete before the waves meet
@@ -248,14 +198,11 @@ void logo_eval_pair_kernel(const PairLaunch A)
                 st.coefs_landed();
                 px.load(gK, gInfo, nslots8, (unsigned)(b * kTileWaves + wave) * 64u + (unsigned)lane, T, plane_base);
             }
-            AMT_PTICK(4);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            AMT_PTICK(5);
         } else {
             ++g;
         }
     }
-    AMT_PDUMP();
 }
 
 hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,

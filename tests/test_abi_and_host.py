@@ -355,11 +355,10 @@ def test_kfm_and_cm_output_file_contracts(tmp_path, lib):
 
 def test_release_library_reads_no_experiment_knobs(lib):
     from amatsukaze_amd import binding
-    """AMTGPU_DBG / AMTGPU_LDSPAD / AMTGPU_FPI / AMTGPU_G exist only in instrumented builds (-DAMT_EXPERIMENT,
-    amatsukaze_amd/build.py build_variant): a stray environment variable must not be able to change the release
-    library's results, so the strings are not even in it."""
+    """AMTGPU_DBG / AMTGPU_LDSPAD / AMTGPU_FPI / AMTGPU_G / AMTGPU_VERBOSE / AMTGPU_NO_PAIR exist in no build any more: a stray
+    environment variable must not be able to change the library's results, so the strings are not even in it."""
     blob = open(binding.LIB_PATH, "rb").read()
-    for knob in (b"AMTGPU_DBG", b"AMTGPU_LDSPAD", b"AMTGPU_FPI", b"AMTGPU_G\0", b"AMTGPU_VERBOSE"):
+    for knob in (b"AMTGPU_DBG", b"AMTGPU_LDSPAD", b"AMTGPU_FPI", b"AMTGPU_G\0", b"AMTGPU_VERBOSE", b"AMTGPU_NO_PAIR"):
         assert knob not in blob, knob
 
 
@@ -544,9 +543,11 @@ def test_decisions_do_not_depend_on_how_the_clip_is_cut_over_threads(lib, thread
 
 
 def test_release_build_defines_no_knob_and_knobs_are_fenced(tmp_path):
-    """The kernels carry ablation macros that compute WRONG results by design, phase timers and shape parameters.  The release library
-    is built with none of them (build.FLAGS / EXTRA_FLAGS carry no -DAMT_), and csrc/build_knobs.h -- included first by every source --
-    turns any of them on the command line into a compile error unless the build says it is an instrumented variant."""
+    """The sources carry shape parameters and host-side call tracing.  The release library is built with none of them (build.FLAGS /
+    EXTRA_FLAGS carry no -DAMT_), and csrc/build_knobs.h -- included first by every source -- turns any of them on the command line
+    into a compile error unless the build says it is an instrumented variant.  The evaluation kernels' ablation macros, phase timers
+    and AMT_EXPERIMENT are retired: no source holds them any more, and the fence refuses them in every build, instrumented or not
+    (the define would silently time the release kernel)."""
     import re
     import subprocess
     from amatsukaze_amd import build as B
@@ -554,26 +555,41 @@ def test_release_build_defines_no_knob_and_knobs_are_fenced(tmp_path):
     assert not [f for f in flags if f.startswith("-DAMT_")], flags
     csrc = os.path.join(ROOT, "amatsukaze_amd", "csrc")
     fence = open(os.path.join(csrc, "build_knobs.h")).read()
-    fenced = set(re.findall(r"defined\((AMT_[A-Z0-9_]+)\)", fence)) - {"AMT_INSTRUMENTED_BUILD"}
+    # the retired block stands in front of the instrumented-build fence: unconditional
+    retired_text, allowed_text = fence.split("#if !defined(AMT_INSTRUMENTED_BUILD)")
+    retired = set(re.findall(r"defined\((AMT_[A-Z0-9_]+)\)", retired_text))
+    fenced = set(re.findall(r"defined\((AMT_[A-Z0-9_]+)\)", allowed_text))
+    assert retired == {"AMT_LIN_NO_EVAL", "AMT_LIN_NO_FIXUP", "AMT_LIN_NO_FLUSH", "AMT_LIN_NO_CONVERT", "AMT_LIN_RAW_SAMEFRAME",
+                       "AMT_PAIR_NO_SUM", "AMT_PAIR_NO_EVAL", "AMT_PAIR_NO_CONVERT", "AMT_PAIR_NO_FLUSH", "AMT_PAIR_NO_GATHER",
+                       "AMT_PAIR_NO_RAW", "AMT_PAIR_RAW_SAMEFRAME", "AMT_LIN_TIMING", "AMT_PAIR_TIMING", "AMT_FUSED_TIMING", "AMT_EXPERIMENT"}
+    assert fenced and not (fenced & retired)
     used = set()
     for f in os.listdir(csrc):
         text = open(os.path.join(csrc, f)).read()
         if f != "build_knobs.h":
             used |= set(re.findall(r"#\s*(?:ifn?def|if|elif)\b[^\n]*?\b(AMT_[A-Z0-9_]+)", text))
             used |= set(re.findall(r"defined\((AMT_[A-Z0-9_]+)\)", text))
+            assert not [n for n in retired if re.search(r"\b%s\b" % n, text)], f"{f} still holds a retired switch"
         if f in B.SOURCES:
             first = re.search(r'^#include\s+[<"]([^>"]+)[>"]', text, re.M)
             assert first and first.group(1) == "build_knobs.h", f"{f}: build_knobs.h must be its first include"
     # internal helper macros (defined by the sources themselves, never on a command line) are not knobs
     internal = {"AMT_GPU_H", "AMT_HD", "AMT_TILE_HD", "AMT_HIP", "AMT_TRACE_SCOPE", "AMT_TRACE_CAT", "AMT_TRACE_CAT2", "AMT_TRACE_BLOCK_BEGIN",
-                "AMT_LTICK", "AMT_PTICK", "AMT_PDUMP", "AMT_TICK", "AMT_STATS_LAUNCH", "AMT_LAUNCH", "AMT_PAIR_OCC_ATTR", "AMT_INSTRUMENTED_BUILD"}
+                "AMT_STATS_LAUNCH", "AMT_LAUNCH", "AMT_PAIR_OCC_ATTR", "AMT_INSTRUMENTED_BUILD"}
     assert used - internal <= fenced, f"knobs the fence does not know: {sorted(used - internal - fenced)}"
-    # ... and the fence bites: an ablation on the command line of a release-style compile fails, the instrumented spelling passes
+    # ... and the list cannot rot: every name the fence allows in an instrumented build is tested by at least one source
+    assert fenced <= used, f"fenced names no source tests: {sorted(fenced - used)}"
+    # ... and the fence bites: a knob on the command line of a release-style compile fails, the instrumented spelling passes
     src = tmp_path / "t.cpp"
     src.write_text('#include "build_knobs.h"\nint main() { return 0; }\n')
     cc = ["g++", "-fsyntax-only", "-I", csrc, str(src)]
     assert subprocess.run(cc, capture_output=True).returncode == 0
-    for knob in ("AMT_LIN_NO_FIXUP", "AMT_PAIR_NO_SUM", "AMT_LIN_G=3", "AMT_FUSED_TIMING", "AMT_STATS_ROWS8=8", "AMT_EXPERIMENT"):
+    for knob in ("AMT_LIN_G=3", "AMT_STATS_ROWS8=8", "AMT_DELOGO_ROWS=4"):
         r = subprocess.run(cc + ["-D" + knob], capture_output=True, text=True)
         assert r.returncode != 0 and "build_variant" in r.stderr, knob
         assert subprocess.run(cc + ["-D" + knob, "-DAMT_INSTRUMENTED_BUILD"], capture_output=True).returncode == 0, knob
+    # ... a retired switch fails in both spellings
+    for knob in ("AMT_LIN_NO_FIXUP", "AMT_PAIR_NO_SUM", "AMT_FUSED_TIMING", "AMT_EXPERIMENT"):
+        for extra in ([], ["-DAMT_INSTRUMENTED_BUILD"]):
+            r = subprocess.run(cc + ["-D" + knob] + extra, capture_output=True, text=True)
+            assert r.returncode != 0 and "build_variant" in r.stderr and "removed" in r.stderr, (knob, extra)

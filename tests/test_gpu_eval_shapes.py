@@ -87,7 +87,7 @@ def test_many_frames_per_workgroup(gpu):
 @pytest.mark.parametrize("group,bits", [(4, 8), (5, 10)])
 def test_scan_in_ragged_batches_bit_exact(gpu, group, bits):
     """LogoFrame::scanFrames fed in batches of 23 frames (40 = 23 + 17) with two logos; frames-per-workgroup sizes above 1 are
-    covered by test_many_frames_per_workgroup (the AMTGPU_G knob set here only exists in instrumented builds)."""
+    covered by test_many_frames_per_workgroup (the AMTGPU_G knob set here is read by no build any more)."""
     import ctypes as C
     import amt_synth as S
     from amatsukaze_amd import Logo, LogoFrame

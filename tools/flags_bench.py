@@ -10,12 +10,7 @@ VARIANTS = {"noslp_all": {f: NOSLP for f in ("eval_linear_kernels.hip", "eval_pa
             "lin_maxilp": {"eval_linear_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]},
             "lin_maxmem": {"eval_linear_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]},
             "pair_maxilp": {"eval_pair_kernels.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}}
-DEFS = {"lin_g6": ["AMT_LIN_G=6"], "lin_g5": ["AMT_LIN_G=5"], "lin_g4": ["AMT_LIN_G=4"], "lin_occ3": ["AMT_LIN_OCC=3", "AMT_LIN_OCC16=3"],
-        # ablations (wrong results by design: what a part of a kernel costs)
-        "abl_lin_raw_sameframe": ["AMT_LIN_RAW_SAMEFRAME"], "abl_lin_no_flush": ["AMT_LIN_NO_FLUSH"], "abl_lin_no_fixup": ["AMT_LIN_NO_FIXUP"],
-        "abl_lin_no_convert": ["AMT_LIN_NO_CONVERT"], "abl_lin_no_eval": ["AMT_LIN_NO_EVAL"],
-        "abl_pair_raw_sameframe": ["AMT_PAIR_RAW_SAMEFRAME"], "abl_pair_no_sum": ["AMT_PAIR_NO_SUM"], "abl_pair_no_gather": ["AMT_PAIR_NO_GATHER"],
-        "abl_pair_no_flush": ["AMT_PAIR_NO_FLUSH"], "abl_pair_no_convert": ["AMT_PAIR_NO_CONVERT"], "abl_pair_no_eval": ["AMT_PAIR_NO_EVAL"]}
+DEFS = {"lin_g6": ["AMT_LIN_G=6"], "lin_g5": ["AMT_LIN_G=5"], "lin_g4": ["AMT_LIN_G=4"], "lin_occ3": ["AMT_LIN_OCC=3", "AMT_LIN_OCC16=3"]}
 for k in DEFS:
     VARIANTS.setdefault(k, {})
 if "--build" in sys.argv:
