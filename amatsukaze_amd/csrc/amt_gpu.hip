@@ -379,7 +379,7 @@ int amtgpu_logoframe_scan_surfaces(AmtGpuLogoFrame* lf, const AmtGpuSurfaces* ba
         auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
         if (first < 0 || nframes < 0 || first + nframes > lf->numFrames) throw std::runtime_error("frame range outside the clip");
         if (nframes == 0) return;
-        const SurfaceBatch b = surface_batch(batch, who, true);
+        const FrameBatch b = surface_batch(batch, who, true);
         if (batch->bits != lf->bits) refuse("surface bits differ from the depth given to amtgpu_logoframe_begin");
         if (!lf->engine) return;
         // the union of the rectangles of the logos that are scanned: all the engine reads
@@ -735,7 +735,7 @@ int amtgpu_analyze_surfaces(AmtGpuAnalyze* an, const AmtGpuSurfaces* batch, int 
         auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
         if (nframes < 0) refuse("negative frame count");
         if (nframes == 0) return;
-        const SurfaceBatch b = surface_batch(batch, who, true);
+        const FrameBatch b = surface_batch(batch, who, true);
         if (!dout) refuse("null output");
         const LogoPlanes& P = an->logo;
         if (b.pitchY < P.imgx + P.w) refuse("surface pitchY smaller than the rectangle's rows");

@@ -144,7 +144,7 @@ static const float2* erase_fades(AmtGpuErase* er, int nframes, const float* fade
 
 // Delogo of a batch that has passed erase_wanted: reads src, writes dst (laid out like src; the same planes for the in-place calls).
 // rect_only: the planes hold the logo's rectangle and nothing else.  `span`: the profile span the call records, whichever kernel runs
-static void erase_run(AmtGpuErase* er, const char* span, int bits, const SurfaceBatch& src, const PlanesOut& dst, bool rect_only, int nframes,
+static void erase_run(AmtGpuErase* er, const char* span, int bits, const FrameBatch& src, const PlanesOut& dst, bool rect_only, int nframes,
                       const float* fades, const float* d_fades)
 {
     const LogoPlanes& P = er->logo;
@@ -165,8 +165,7 @@ static void erase_run(AmtGpuErase* er, const char* span, int bits, const Surface
     const bool skip_fade0 = er->zeroIdentity && (bits == 8 || bits == 16 || src.shift != 0);
     // planar LSB batches are delogo_kernel's, every other layout delogo_surfaces_kernel's
     if (!src.interleaved && !src.shift)
-        AMT_HIP(launch_delogo(er->ctx->stream, bits, PlaneBatch{src.Y, src.U, src.V, src.strideY / src.es, src.strideUV / src.es, src.pitchY, src.pitchUV},
-                              dst, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
+        AMT_HIP(launch_delogo(er->ctx->stream, bits, src, dst, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
     else
         AMT_HIP(launch_delogo_surfaces(er->ctx->stream, bits, src, dst, er->dPlanes.get(), g, nframes, dfades, skip_fade0 ? 1 : 0));
     er->ctx->prof_end(sp);
@@ -177,7 +176,7 @@ static void erase_planes(AmtGpuErase* er, const void* sY, const void* sU, const 
                          int pitchY, int pitchUV, int bits, int nframes, const float* fades, const float* d_fades, bool rect_only)
 {
     if (!erase_wanted(er, bits, nframes)) return;
-    const SurfaceBatch src = planar_surfaces(plane_batch(bits, sY, sU, sV, strideY, strideUV, pitchY, pitchUV), sample_bytes(bits));
+    const FrameBatch src = plane_batch(bits, sY, sU, sV, strideY, strideUV, pitchY, pitchUV);
     erase_run(er, "delogo_kernel", bits, src, PlanesOut{dY, dU, dV}, rect_only, nframes, fades, d_fades);
 }
 
@@ -229,7 +228,7 @@ static void erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* src, const Amt
     auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
     if (nframes < 0) refuse("negative frame count");
     if (nframes == 0) return;
-    const SurfaceBatch b = surface_batch(src, who);
+    const FrameBatch b = surface_batch(src, who);
     const int bits = src->bits;
     if (!erase_wanted(er, bits, nframes)) return;
     if (device_fades ? !d_fades : !fades) refuse(device_fades ? "null device fades" : "null fades");
@@ -238,7 +237,7 @@ static void erase_surfaces(AmtGpuErase* er, const AmtGpuSurfaces* src, const Amt
     if (b.pitchUV < (b.interleaved ? 2 : 1) * ((P.imgx >> P.logUVx) + P.wUV())) refuse("surface pitchUV smaller than the rectangle's rows");
     PlanesOut out{const_cast<void*>(b.Y), const_cast<void*>(b.U), const_cast<void*>(b.V)};
     if (dst != src) {
-        const SurfaceBatch d = surface_batch(dst, who);
+        const FrameBatch d = surface_batch(dst, who);
         if (dst->bits != src->bits || d.interleaved != b.interleaved || d.shift != b.shift || d.pitchY != b.pitchY || d.pitchUV != b.pitchUV ||
             d.strideY != b.strideY || d.strideUV != b.strideUV)
             refuse("destination surfaces differ from the source's in bits, interleaved, msb_aligned, pitches or strides");
@@ -331,7 +330,7 @@ static void logoscan_pull(AmtGpuLogoScan* s)
 }
 
 // border verdicts for a batch (8..12 bits) of the scan's rectangle at r's origin, then accumulate the accepted subset; returns accepted count
-static int logoscan_add(AmtGpuLogoScan* s, const PlaneBatch& b, const ScanRect& r, int bits, int nframes, int max_valid, const uint8_t* use_mask,
+static int logoscan_add(AmtGpuLogoScan* s, const FrameBatch& b, const ScanRect& r, int bits, int nframes, int max_valid, const uint8_t* use_mask,
                         uint8_t* valid_out, const int* frame_ids /* optional: batch slot -> frame index in b */,
                         const int4* known_verdicts /* optional: skip the border kernel */)
 {
@@ -461,7 +460,7 @@ namespace {
 
 // The frames round 0 kept, which every later step reads again: where they lie and what their border said.
 struct KeptFrames {
-    PlaneBatch planes{};              // the resident clip, or a session's store
+    FrameBatch planes{};              // the resident clip, or a session's store
     ScanRect r{};                     // the scan rectangle in those planes
     int bits = 8;
     std::vector<int> index;           // frame index in `planes` of every kept frame
@@ -533,7 +532,7 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
             EvalEngine eng(c, std::move(specs), fades, true, 20, "logo_eval_fused_kernel.remake");
             std::vector<uint8_t> use(numFrames, 0);
             if (numFrames) {
-                eng.run(kept.planes.Y, luma_stride_bytes(kept.planes, sample_bytes(kept.bits)), kept.planes.pitchY, kept.bits, numFrames, dEval.get(), dMap.get());
+                eng.run(kept.planes.Y, kept.planes.strideY, kept.planes.pitchY, kept.bits, numFrames, dEval.get(), dMap.get());
                 download_via_pinned(c, hEval.data(), dEval.get(), hEval.size() * sizeof(float));
             }
             for (int i = 0; i < numFrames; ++i) {
@@ -650,7 +649,7 @@ void stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const 
     if (!dY || !dU || !dV) throw std::runtime_error("[ScanLogo] null plane");
     const ScanRect r = rect_only ? scan_rect(0, 0, s->rect.w, s->rect.h) : s->rect;
     if (pitchY < r.imgx + r.w || pitchUV < r.cx + r.wUV) throw std::runtime_error("[ScanLogo] pitch smaller than the rectangle's rows");
-    const PlaneBatch b = plane_batch(s->bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, PlaneRules::ScanLogo);
+    const FrameBatch b = plane_batch(s->bits, dY, dU, dV, strideY, strideUV, pitchY, pitchUV, PlaneRules::ScanLogo);
     AmtGpuContext* c = s->ctx;
     // verdicts alone (quota 0): which valid frames count is decided here, in stream order
     logoscan_add(s->scan.get(), b, r, s->bits, nframes, 0, nullptr, nullptr, nullptr, nullptr);
@@ -675,7 +674,7 @@ void stream_feed(AmtGpuScanLogoStream* s, const void* dY, const void* dU, const 
         AMT_HIP(hipMemcpyAsync(s->dKeep.get(), s->hKeep, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
         AMT_HIP(hipEventRecord(s->keepUploaded, c->stream));
         const int sp = c->prof_begin("scan_keep_kernel");
-        AMT_HIP(launch_scan_keep(c->stream, s->es, b, r, s->dKeep.get(), m, PlanesOut{s->storeY.get(), s->storeU.get(), s->storeV.get()}, first));
+        AMT_HIP(launch_scan_keep(c->stream, b, r, s->dKeep.get(), m, PlanesOut{s->storeY.get(), s->storeU.get(), s->storeV.get()}, first));
         c->prof_end(sp);
         for (int k = 0; k < m; ++k) s->keptVerdict.push_back(v[s->hKeep[k]]);
     }
@@ -726,7 +725,8 @@ void stream_finish(AmtGpuScanLogoStream* s, const AmtGpuCollectives* coll, int s
     s->ctx->bind();
     const int n = sg.quota_share(s->nkept(), s->numMaxFrames);
     const ScanRect r = scan_rect(0, 0, s->rect.w, s->rect.h);
-    const PlaneBatch store{s->storeY.get(), s->storeU.get(), s->storeV.get(), (long long)r.w * r.h, (long long)r.wUV * r.hUV, r.w, r.wUV};
+    // (the store is tight: a slot's bytes apart)
+    const FrameBatch store = plane_batch(s->bits, s->storeY.get(), s->storeU.get(), s->storeV.get(), (int64_t)s->slotY(), (int64_t)s->slotC(), r.w, r.wUV);
     KeptFrames kept{store, r, s->bits, std::vector<int>(n), std::vector<int4>(s->keptVerdict.begin(), s->keptVerdict.begin() + n)};
     std::iota(kept.index.begin(), kept.index.end(), 0);          // the store holds the kept frames alone, in order
     accumulate_kept(sg, s->scan.get(), kept);
@@ -872,7 +872,7 @@ int amtgpu_scanlogo_sharded_bits(AmtGpuContext* c, const AmtGpuCollectives* coll
 {
     if (!c) return 0;
     return guard(c, [&] {
-        const int es = scan_sample_bytes(bits, thy);         // (refused before anything is exchanged: the same on every rank)
+        (void)scan_sample_bytes(bits, thy);                  // (refused before anything is exchanged: the same on every rank)
         ShardGuard sg(coll, cb);
         if (sg.sharded() && (!coll->allgather || !coll->allreduce_sum_i64 || coll->rank < 0 || coll->rank >= coll->world))
             throw std::runtime_error("AmtGpuCollectives incomplete");
@@ -891,7 +891,7 @@ int amtgpu_scanlogo_sharded_bits(AmtGpuContext* c, const AmtGpuCollectives* coll
             scan.reset(logoscan_new(c, r.w, r.h, 1, 1, thy));
             for (int f0 = 0; f0 < nframes_local && wanted(); f0 += chunk) {
                 const int n = std::min(chunk, nframes_local - f0);
-                logoscan_add(scan.get(), plane_batch_from(kept.planes, f0, es), r, bits, n, sg.sharded() ? 0 : numMaxFrames - kept.count(), nullptr,
+                logoscan_add(scan.get(), plane_batch_from(kept.planes, f0), r, bits, n, sg.sharded() ? 0 : numMaxFrames - kept.count(), nullptr,
                              nullptr, nullptr, nullptr);
                 for (int i = 0; i < n; ++i)
                     if (scan->lastVerdicts[i].x && wanted()) { kept.index.push_back(f0 + i); kept.verdict.push_back(scan->lastVerdicts[i]); }

@@ -132,7 +132,7 @@ int amtgpu_logofind_add_surfaces(AmtGpuLogoFind* lf, const AmtGpuSurfaces* batch
     return guard(lf->ctx, [&] {
         if (nframes < 0) throw std::runtime_error("[LogoFind] negative frame count");
         if (nframes == 0) return;
-        const SurfaceBatch b = surface_batch(batch, "[LogoFind]", true);
+        const FrameBatch b = surface_batch(batch, "[LogoFind]", true);
         if (batch->bits != lf->bits) throw std::runtime_error("[LogoFind] surfaces of another depth than the finder's");
         // a Y plane is a Y plane whatever the chroma layout; the MSB form (shift 0 at 16 bits: the plain one) reads container >> shift
         logofind_add(lf, b.Y, b.strideY, b.pitchY, nframes, b.shift);

@@ -22,9 +22,9 @@ const char* const kWho = "[KFMRender]";
 [[noreturn]] void refuse(const std::string& what) { throw std::runtime_error(std::string(kWho) + " " + what); }
 
 // surfaces of `bits` in any layout, rows of at least width containers (chroma: width / 2 planar, 2 * (width / 2) interleaved)
-SurfaceBatch render_surfaces(const AmtGpuSurfaces* s, const char* which, int width)
+FrameBatch render_surfaces(const AmtGpuSurfaces* s, const char* which, int width)
 {
-    const SurfaceBatch b = surface_batch(s, kWho);
+    const FrameBatch b = surface_batch(s, kWho);
     if (b.strideY < 0 || b.strideUV < 0) refuse(std::string(which) + ": negative frame stride");
     if (b.pitchY < width || b.pitchUV < (b.interleaved ? width : width / 2)) refuse(std::string(which) + ": pitch smaller than the row");
     return b;
@@ -49,7 +49,7 @@ void render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc
     if (nout == 0) return;
     if (!plan) refuse("null plan");
     if (width <= 0 || height < 4 || (width & 1) || (height & 1)) refuse("width and height must be even and height at least 4 (4:2:0 field pairs)");
-    const SurfaceBatch s = render_surfaces(src, "source", width), d = render_surfaces(dst, "destination", width);
+    const FrameBatch s = render_surfaces(src, "source", width), d = render_surfaces(dst, "destination", width);
     if (src->bits != dst->bits) refuse("source and destination differ in bits");
     if (s.interleaved != d.interleaved || s.shift != d.shift)
         refuse("source and destination are not in kind (equal bits, interleaved and MSB shift): the renderer converts no layouts");
@@ -111,9 +111,8 @@ void render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc
         for (int j = 0; j < nplanes; ++j)
             if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place rendering)");
     // (an interleaved batch has null V planes, which count as aligned: surface_batch drops whatever the descriptor holds there)
-    auto al16 = [](const void* p, long long stride, int pitch) { return (uintptr_t)p % 16 == 0 && stride % 16 == 0 && pitch % 16 == 0; };
-    a.vec = al16(a.srcY, a.src_strideY, a.src_pitchY) && al16(a.srcU, a.src_strideUV, a.src_pitchUV) && al16(a.srcV, a.src_strideUV, a.src_pitchUV) &&
-            al16(a.dstY, a.dst_strideY, a.dst_pitchY) && al16(a.dstU, a.dst_strideUV, a.dst_pitchUV) && al16(a.dstV, a.dst_strideUV, a.dst_pitchUV);
+    a.vec = render_vec16(RowsAt{lane_addr(a.srcY), 0, a.src_strideY, a.src_pitchY}, RowsAt{lane_addr(a.srcU), lane_addr(a.srcV), a.src_strideUV, a.src_pitchUV},
+                         RowsAt{lane_addr(a.dstY), 0, a.dst_strideY, a.dst_pitchY}, RowsAt{lane_addr(a.dstU), lane_addr(a.dstV), a.dst_strideUV, a.dst_pitchUV});
     c->bind();
     if (adaptive) {
         DevBuf<RenderAdaptiveEntry> dplan;

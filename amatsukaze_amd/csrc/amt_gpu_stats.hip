@@ -39,28 +39,60 @@ void gather_frame_metrics(const AmtGpuCollectives* coll, const uint64_t* local, 
     allgather_records(coll, local, first, nlocal, num_frames, rec * sizeof(uint64_t), out, true, local_error, "the frame metrics");
 }
 
-// What the surfaces entry points launch with: the Y planes of a batch of decoder surfaces and of the one picture before it (prev may be
-// null), checked against the object and against each other.  Chroma is never looked at.
-struct StatSurfaces { const void* Y; int64_t strideY; int pitchY; const void* prevY; int shift; };
-StatSurfaces stat_surfaces(const AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch, const AmtGpuSurfaces* prev)
+// What a launch reads: the Y planes of a batch (stride in bytes, pitch in containers) and of the one picture before it (prevY may be
+// null); sample = container >> shift.  A plane call is this with shift 0.  Chroma is never looked at.
+struct StatLuma { const void* Y; int64_t strideY; int pitchY; const void* prevY; int shift; };
+// ... of a batch of decoder surfaces, checked against the object and against each other
+StatLuma stat_surfaces(const AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch, const AmtGpuSurfaces* prev)
 {
     const char* who = "[FrameStats]";
-    const SurfaceBatch b = surface_batch(batch, who, true);
+    const FrameBatch b = surface_batch(batch, who, true);
     if (batch->bits != fs->bits) throw std::runtime_error("[FrameStats] surfaces of another depth than the object's");
     if (b.pitchY < fs->width || b.strideY < 0) throw std::runtime_error("[FrameStats] surface pitchY below the width or negative stride");
-    StatSurfaces s{b.Y, b.strideY, b.pitchY, nullptr, b.shift};
+    StatLuma s{b.Y, b.strideY, b.pitchY, nullptr, b.shift};
     if (prev) {
-        const SurfaceBatch p = surface_batch(prev, who, true);
+        const FrameBatch p = surface_batch(prev, who, true);
         if (prev->bits != batch->bits || (prev->msb_aligned != 0) != (batch->msb_aligned != 0) || prev->pitchY != batch->pitchY)
             throw std::runtime_error("[FrameStats] the previous picture must have the batch's bits, msb_aligned and pitchY");
         s.prevY = p.Y;
     }
     return s;
 }
-hipError_t launch_stat_surfaces(const AmtGpuFrameStats* fs, const StatSurfaces& s, int nframes, unsigned long long* dout)
+
+// the records of nframes frames into dout (device): both batch entry points, once their arguments are read
+void stats_launch(AmtGpuFrameStats* fs, const StatLuma& s, int nframes, unsigned long long* dout)
 {
-    return s.shift ? launch_frame_stats_msb(fs->ctx->stream, fs->bits, s.shift, s.Y, s.strideY, s.pitchY, fs->width, fs->height, s.prevY, nframes, dout)
-                   : launch_frame_stats(fs->ctx->stream, fs->bits, s.Y, s.strideY, s.pitchY, fs->width, fs->height, s.prevY, nframes, dout);
+    fs->ctx->bind();
+    const int sp = fs->ctx->prof_begin("frame_stats_kernel");
+    AMT_HIP(s.shift ? launch_frame_stats_msb(fs->ctx->stream, fs->bits, s.shift, s.Y, s.strideY, s.pitchY, fs->width, fs->height, s.prevY, nframes, dout)
+                    : launch_frame_stats(fs->ctx->stream, fs->bits, s.Y, s.strideY, s.pitchY, fs->width, fs->height, s.prevY, nframes, dout));
+    fs->ctx->prof_end(sp);
+}
+
+// launch, download and gather: both sharded entry points.  luma(): the shard's descriptor, called (and free to refuse) once the range is
+// known to hold frames; have_prev / prev_words: whether the caller gave the frame before the shard, and what its absence is called
+template <typename F>
+void stats_sharded(AmtGpuFrameStats* fs, const AmtGpuCollectives* coll, bool have_prev, const char* prev_words, F&& luma, int first, int nlocal,
+                   int num_frames, uint64_t* metrics_out)
+{
+    std::string err;
+    std::vector<uint64_t> local;
+    try {
+        if (first < 0 || nlocal < 0 || (long long)first + nlocal > num_frames) throw std::runtime_error("frame range outside the clip");
+        // the first frame of a shard is compared with the frame before it: only the shard that starts the clip has none
+        if (first > 0 && nlocal > 0 && !have_prev)
+            throw std::runtime_error(std::string("[FrameStats] a shard that does not start the clip needs the ") + prev_words);
+        if (nlocal > 0) {
+            const StatLuma s = luma();
+            fs->ctx->bind();
+            const size_t n = (size_t)nlocal * AMTGPU_FS_WORDS;
+            if (fs->dShard.size() < n) fs->dShard.alloc(n);
+            stats_launch(fs, s, nlocal, fs->dShard.get());
+            local.resize(n);
+            download_via_pinned(fs->ctx, local.data(), fs->dShard.get(), n * sizeof(uint64_t));
+        }
+    } catch (const std::exception& e) { err = e.what(); }
+    gather_frame_metrics(coll, local.data(), first, nlocal, num_frames, metrics_out, err);
 }
 } // namespace
 
@@ -80,13 +112,7 @@ void amtgpu_framestats_destroy(AmtGpuFrameStats* fs) { delete fs; }
 int amtgpu_framestats_batch(AmtGpuFrameStats* fs, const void* dY, int64_t frame_stride, int pitch, const void* dprevY, int nframes,
                             uint64_t* dout)
 {
-    return guard(fs->ctx, [&] {
-        fs->ctx->bind();
-        const int sp = fs->ctx->prof_begin("frame_stats_kernel");
-        AMT_HIP(launch_frame_stats(fs->ctx->stream, fs->bits, dY, frame_stride, pitch, fs->width, fs->height, dprevY, nframes,
-                                   (unsigned long long*)dout));
-        fs->ctx->prof_end(sp);
-    });
+    return guard(fs->ctx, [&] { stats_launch(fs, StatLuma{dY, frame_stride, pitch, dprevY, 0}, nframes, (unsigned long long*)dout); });
 }
 
 int amtgpu_framestats_allgather(AmtGpuFrameStats* fs, const AmtGpuCollectives* coll, const uint64_t* local_metrics, int first, int nlocal,
@@ -99,25 +125,8 @@ int amtgpu_framestats_sharded(AmtGpuFrameStats* fs, const AmtGpuCollectives* col
                               const void* dprevY, int first, int nlocal, int num_frames, uint64_t* metrics_out)
 {
     return guard(fs->ctx, [&] {
-        std::string err;
-        std::vector<uint64_t> local;
-        try {
-            if (first < 0 || nlocal < 0 || (long long)first + nlocal > num_frames) throw std::runtime_error("frame range outside the clip");
-            // the first frame of a shard is compared with the frame before it: only the shard that starts the clip has none
-            if (first > 0 && nlocal > 0 && !dprevY) throw std::runtime_error("[FrameStats] a shard that does not start the clip needs the frame before it (dprevY)");
-            if (nlocal > 0) {
-                fs->ctx->bind();
-                const size_t n = (size_t)nlocal * AMTGPU_FS_WORDS;
-                if (fs->dShard.size() < n) fs->dShard.alloc(n);
-                const int sp = fs->ctx->prof_begin("frame_stats_kernel");
-                AMT_HIP(launch_frame_stats(fs->ctx->stream, fs->bits, dY, frame_stride, pitch, fs->width, fs->height, first > 0 ? dprevY : nullptr,
-                                           nlocal, fs->dShard.get()));
-                fs->ctx->prof_end(sp);
-                local.resize(n);
-                download_via_pinned(fs->ctx, local.data(), fs->dShard.get(), n * sizeof(uint64_t));
-            }
-        } catch (const std::exception& e) { err = e.what(); }
-        gather_frame_metrics(coll, local.data(), first, nlocal, num_frames, metrics_out, err);
+        stats_sharded(fs, coll, dprevY != nullptr, "frame before it (dprevY)",
+                      [&] { return StatLuma{dY, frame_stride, pitch, first > 0 ? dprevY : nullptr, 0}; }, first, nlocal, num_frames, metrics_out);
     });
 }
 
@@ -126,12 +135,9 @@ int amtgpu_framestats_surfaces(AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch
     return guard(fs->ctx, [&] {
         if (nframes < 0) throw std::runtime_error("[FrameStats] negative frame count");
         if (nframes == 0) return;
-        const StatSurfaces s = stat_surfaces(fs, batch, prev);
+        const StatLuma s = stat_surfaces(fs, batch, prev);
         if (!dout) throw std::runtime_error("[FrameStats] null metrics pointer");
-        fs->ctx->bind();
-        const int sp = fs->ctx->prof_begin("frame_stats_kernel");
-        AMT_HIP(launch_stat_surfaces(fs, s, nframes, (unsigned long long*)dout));
-        fs->ctx->prof_end(sp);
+        stats_launch(fs, s, nframes, (unsigned long long*)dout);
     });
 }
 
@@ -139,25 +145,8 @@ int amtgpu_framestats_sharded_surfaces(AmtGpuFrameStats* fs, const AmtGpuCollect
                                        const AmtGpuSurfaces* prev, int first, int nlocal, int num_frames, uint64_t* metrics_out)
 {
     return guard(fs->ctx, [&] {
-        std::string err;
-        std::vector<uint64_t> local;
-        try {
-            if (first < 0 || nlocal < 0 || (long long)first + nlocal > num_frames) throw std::runtime_error("frame range outside the clip");
-            // the first frame of a shard is compared with the frame before it: only the shard that starts the clip has none
-            if (first > 0 && nlocal > 0 && !prev) throw std::runtime_error("[FrameStats] a shard that does not start the clip needs the picture before it (prev)");
-            if (nlocal > 0) {
-                const StatSurfaces s = stat_surfaces(fs, batch, first > 0 ? prev : nullptr);
-                fs->ctx->bind();
-                const size_t n = (size_t)nlocal * AMTGPU_FS_WORDS;
-                if (fs->dShard.size() < n) fs->dShard.alloc(n);
-                const int sp = fs->ctx->prof_begin("frame_stats_kernel");
-                AMT_HIP(launch_stat_surfaces(fs, s, nlocal, fs->dShard.get()));
-                fs->ctx->prof_end(sp);
-                local.resize(n);
-                download_via_pinned(fs->ctx, local.data(), fs->dShard.get(), n * sizeof(uint64_t));
-            }
-        } catch (const std::exception& e) { err = e.what(); }
-        gather_frame_metrics(coll, local.data(), first, nlocal, num_frames, metrics_out, err);
+        stats_sharded(fs, coll, prev != nullptr, "picture before it (prev)", [&] { return stat_surfaces(fs, batch, first > 0 ? prev : nullptr); }, first,
+                      nlocal, num_frames, metrics_out);
     });
 }
 

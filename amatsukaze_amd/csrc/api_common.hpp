@@ -80,11 +80,13 @@ inline int scan_sample_bytes(int bits, int thy = 0)
     return sample_bytes(bits);
 }
 
-// The ABI's description of a batch (byte strides) as the kernels take it (strides in samples): the one place that divides.  ScanLogo's
-// entry points also refuse the depth and a plane base off the sample size, in their own words; a caller that reads the luma plane alone
-// passes null chroma planes and a zero chroma stride.
+// The ABI's description of a batch of planes (byte strides, sample pitches) as the launchers take it: the same units, planar and LSB.
+// Nothing is converted here or anywhere else in the host code; this is the one place that checks that the sample size divides the byte
+// strides, so that a launcher whose kernel counts in samples may divide (kernels.hpp, FrameBatch).  ScanLogo's entry points also refuse
+// the depth and a plane base off the sample size, in their own words; a caller that reads the luma plane alone passes null chroma planes
+// and a zero chroma stride.
 enum class PlaneRules { Plain, ScanLogo };
-inline amt::PlaneBatch plane_batch(int bits, const void* Y, const void* U, const void* V, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV,
+inline amt::FrameBatch plane_batch(int bits, const void* Y, const void* U, const void* V, int64_t strideY, int64_t strideUV, int pitchY, int pitchUV,
                                    PlaneRules rules = PlaneRules::Plain)
 {
     const bool scan = rules == PlaneRules::ScanLogo;
@@ -92,12 +94,12 @@ inline amt::PlaneBatch plane_batch(int bits, const void* Y, const void* U, const
     if (strideY % es || strideUV % es)
         throw std::runtime_error(scan ? "[ScanLogo] odd byte stride for 16-bit samples" : "frame stride not a multiple of the sample size");
     if (scan && ((uintptr_t)Y % es || (uintptr_t)U % es || (uintptr_t)V % es)) throw std::runtime_error("[ScanLogo] plane base not aligned to the sample size");
-    return amt::PlaneBatch{Y, U, V, strideY / es, strideUV / es, pitchY, pitchUV};
+    return amt::FrameBatch{Y, U, V, strideY, strideUV, pitchY, pitchUV, es, 0, 0};
 }
 
 // A batch of decoder surfaces as the kernels take it, or a refusal in the caller's words (`who`: "[ScanLogo]", ...): the one place that
 // reads an AmtGpuSurfaces.  luma_only: the chroma fields are not looked at (the logo finder).
-inline amt::SurfaceBatch surface_batch(const AmtGpuSurfaces* s, const char* who, bool luma_only = false)
+inline amt::FrameBatch surface_batch(const AmtGpuSurfaces* s, const char* who, bool luma_only = false)
 {
     auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
     if (!s) refuse("null surface descriptor");
@@ -109,8 +111,8 @@ inline amt::SurfaceBatch surface_batch(const AmtGpuSurfaces* s, const char* who,
     if (s->strideY % es || (!luma_only && s->strideUV % es)) refuse("odd byte stride for 16-bit containers");
     if ((uintptr_t)s->Y % es || (!luma_only && ((uintptr_t)s->U % es || (!s->interleaved && (uintptr_t)s->V % es))))
         refuse("surface plane base not aligned to the container size");
-    amt::SurfaceBatch b{s->Y, luma_only ? nullptr : s->U, luma_only || s->interleaved ? nullptr : s->V, s->strideY, luma_only ? 0 : s->strideUV,
-                        s->pitchY, luma_only ? 0 : s->pitchUV, es, s->interleaved ? 1 : 0, s->msb_aligned ? 16 - s->bits : 0};
+    amt::FrameBatch b{s->Y, luma_only ? nullptr : s->U, luma_only || s->interleaved ? nullptr : s->V, s->strideY, luma_only ? 0 : s->strideUV,
+                      s->pitchY, luma_only ? 0 : s->pitchUV, es, s->interleaved ? 1 : 0, s->msb_aligned ? 16 - s->bits : 0};
     return b;
 }
 
@@ -122,7 +124,7 @@ inline void surfaces_extract(AmtGpuContext* c, const AmtGpuSurfaces* src, const 
     auto refuse = [who](const char* what) { throw std::runtime_error(std::string(who) + " " + what); };
     if (nframes < 0) refuse("negative frame count");
     if (nframes == 0) return;
-    const amt::SurfaceBatch b = surface_batch(src, who);
+    const amt::FrameBatch b = surface_batch(src, who);
     if (r.imgx < 0 || r.imgy < 0 || r.w <= 0 || r.h <= 0 || (r.w & 1) || (r.h & 1)) refuse("rectangle must be even-sized and inside the surface");
     if (b.pitchY < r.imgx + r.w) refuse("surface pitchY smaller than the rectangle's rows");
     if (b.pitchUV < (b.interleaved ? 2 : 1) * (r.cx + r.wUV)) refuse("surface pitchUV smaller than the rectangle's rows");
@@ -144,7 +146,7 @@ inline void surfaces_extract(AmtGpuContext* c, const AmtGpuSurfaces* src, const 
 // the engines' alignment-dependent choices are those of an aligned planar clip.  The scratch is the caller's (one per object: its
 // surfaces entry points are not re-entrant).
 struct LumaView { const void* Y; int64_t stride_bytes; int pitch; };
-inline LumaView surfaces_luma_view(AmtGpuContext* c, const amt::SurfaceBatch& b, int row0, int row1, int col0, int col1, int nframes,
+inline LumaView surfaces_luma_view(AmtGpuContext* c, const amt::FrameBatch& b, int row0, int row1, int col0, int col1, int nframes,
                                    amt::DevBuf<uint8_t>& scratch)
 {
     if (!b.shift) return LumaView{b.Y, b.strideY, b.pitchY};
@@ -157,7 +159,7 @@ inline LumaView surfaces_luma_view(AmtGpuContext* c, const amt::SurfaceBatch& b,
     c->bind();
     if (scratch.size() < need) scratch.alloc(need);        // (hipFree waits for the kernels that still read the old scratch)
     uint8_t* band = scratch.get();
-    amt::SurfaceBatch luma = b;
+    amt::FrameBatch luma = b;
     luma.U = luma.V = nullptr; luma.strideUV = 0; luma.pitchUV = 0;
     const int sp = c->prof_begin("surfaces_extract_kernel");
     AMT_HIP(amt::launch_surfaces_extract(c->stream, luma, amt::ScanRect{c0, row0, 0, 0, bw, rows, 0, 0}, nframes, amt::PlanesOut{band, nullptr, nullptr},

@@ -191,7 +191,7 @@ private:
     int out_frame_stride_;
     std::string prof_name_;
     int plane_cap_ = 0;
-    int group_frames_ = 0;   // frames per workgroup (0 = pick per batch; AMTGPU_G overrides)
+    int group_frames_ = 0;   // frames per workgroup (0 = pick per batch from the frame and logo counts; nothing sets another value)
     std::vector<EvalBand> bands_;
     // device state
     std::vector<DevBuf<float>> d_a_, d_b_;

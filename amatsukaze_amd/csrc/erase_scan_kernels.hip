@@ -173,29 +173,33 @@ void delogo_kernel(const pix_t* sY, const pix_t* sU, const pix_t* sV, pix_t* Y, 
     }
 }
 
-hipError_t launch_delogo(hipStream_t st, int bits, const PlaneBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g, int nframes,
+// what the kernels of this file take: planar LSB planes of the depth's sample size, whole samples between frames
+static bool planar_lsb(const FrameBatch& b, int es) { return b.es == es && !b.interleaved && !b.shift && b.strideY % es == 0 && b.strideUV % es == 0; }
+
+hipError_t launch_delogo(hipStream_t st, int bits, const FrameBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g, int nframes,
                          const float2* dfades, int zero_identity)
 {
     if (nframes <= 0) return hipSuccess;
+    const int es = bits <= 8 ? 1 : 2;
+    if (!planar_lsb(src, es)) return hipErrorInvalidValue;
     const int rows = g.h + 2 * g.hUV;
     dim3 grid((unsigned)((rows + kDelogoRows - 1) / kDelogoRows), (unsigned)((nframes + kDelogoFrames - 1) / kDelogoFrames)), block(kDelogoThreads);
     const float maxv = (float)((1 << bits) - 1);
-    const int es = bits <= 8 ? 1 : 2;
-    auto even = [](long long v) { return (v & 1) == 0; };
     // a pair access needs 2*es alignment of every row start and an even width (plane bases come from hipMalloc /
-    // AviSynth's 64-byte aligned planes; a caller handing odd byte offsets falls back to single samples)
-    auto aligned = [&](const void* p) { return (uintptr_t)p % (2 * es) == 0; };
-    const int pairY = even(g.w) && even(g.imgx) && even(src.pitchY) && even(src.strideY) && aligned(dst.Y) && aligned(src.Y);
-    const int pairUV = even(g.wUV) && even(g.cx) && even(src.pitchUV) && even(src.strideUV) && aligned(dst.U) && aligned(dst.V) && aligned(src.U) &&
-                       aligned(src.V);
+    // AviSynth's 64-byte aligned planes; a caller handing odd byte offsets falls back to single samples).  dst is laid out like src
+    const long long pitchY = (long long)src.pitchY * es, pitchUV = (long long)src.pitchUV * es;
+    const int pairY = delogo_pair_lanes(es, RowsAt{lane_addr(src.Y), 0, src.strideY, pitchY}, RowsAt{lane_addr(dst.Y), 0, src.strideY, pitchY},
+                                        (long long)g.imgx * es, (long long)g.w * es);
+    const int pairUV = delogo_pair_lanes(es, RowsAt{lane_addr(src.U), lane_addr(src.V), src.strideUV, pitchUV},
+                                         RowsAt{lane_addr(dst.U), lane_addr(dst.V), src.strideUV, pitchUV}, (long long)g.cx * es, (long long)g.wUV * es);
     // four samples per lane where a row is a multiple of 4 wide (coefficient rows are then 16-byte aligned float4s)
     const int quadY = pairY && g.w % 4 == 0;
     const int quadUV = pairUV && g.wUV % 4 == 0;
     with_sample_type(bits, [&](auto px) {
         typedef decltype(px) pix_t;
         hipLaunchKernelGGL(delogo_kernel<pix_t>, grid, block, 0, st, (const pix_t*)src.Y, (const pix_t*)src.U, (const pix_t*)src.V, (pix_t*)dst.Y,
-                           (pix_t*)dst.U, (pix_t*)dst.V, src.strideY, src.strideUV, src.pitchY, src.pitchUV, dplanes, g, maxv, dfades, pairY, pairUV,
-                           nframes, quadY, quadUV, zero_identity);
+                           (pix_t*)dst.U, (pix_t*)dst.V, src.strideY / es, src.strideUV / es, src.pitchY, src.pitchUV, dplanes, g, maxv, dfades, pairY,
+                           pairUV, nframes, quadY, quadUV, zero_identity);
     });
     return hipGetLastError();
 }
@@ -428,16 +432,18 @@ void scan_border_kernel(const pix_t* __restrict__ Y, const pix_t* __restrict__ U
     if (threadIdx.x == 0) out[frame] = make_int4(ok ? 1 : 0, bgY, bgU, bgV);
 }
 
-hipError_t launch_scan_border(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, int thy, int nframes, int4* dout)
+hipError_t launch_scan_border(hipStream_t st, int bits, const FrameBatch& b, const ScanRect& r, int thy, int nframes, int4* dout)
 {
     if (nframes <= 0) return hipSuccess;
+    const int es = bits <= 8 ? 1 : 2;
+    if (!planar_lsb(b, es)) return hipErrorInvalidValue;
     const int nbins = 1 << bits;
     const size_t lds = (size_t)nbins * 4 + 2 * kBorderThreads * 4 + kBorderThreads * 8;
     dim3 grid((unsigned)nframes), block(kBorderThreads);
     with_sample_type(bits, [&](auto px) {
         typedef decltype(px) pix_t;
-        hipLaunchKernelGGL(scan_border_kernel<pix_t>, grid, block, lds, st, (const pix_t*)b.Y, (const pix_t*)b.U, (const pix_t*)b.V, b.strideY,
-                           b.strideUV, b.pitchY, b.pitchUV, r.imgx, r.imgy, r.cx, r.cy, r.w, r.h, r.wUV, r.hUV, nbins, thy, dout);
+        hipLaunchKernelGGL(scan_border_kernel<pix_t>, grid, block, lds, st, (const pix_t*)b.Y, (const pix_t*)b.U, (const pix_t*)b.V, b.strideY / es,
+                           b.strideUV / es, b.pitchY, b.pitchUV, r.imgx, r.imgy, r.cx, r.cy, r.w, r.h, r.wUV, r.hUV, nbins, thy, dout);
     });
     return hipGetLastError();
 }
@@ -498,16 +504,18 @@ void scan_accumulate_kernel(const pix_t* __restrict__ Y, const pix_t* __restrict
     }
 }
 
-hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, const int4* daccepted, int naccepted,
+hipError_t launch_scan_accumulate(hipStream_t st, int bits, const FrameBatch& b, const ScanRect& r, const int4* daccepted, int naccepted,
                                   unsigned long long* dacc)
 {
     if (naccepted <= 0) return hipSuccess;
+    const int es = bits <= 8 ? 1 : 2;
+    if (!planar_lsb(b, es)) return hipErrorInvalidValue;
     const int per = std::max(kAccMinFramesPerBlock, (naccepted + kAccFrameChunks - 1) / kAccFrameChunks);
     dim3 grid((unsigned)(r.h + 2 * r.hUV), (unsigned)((naccepted + per - 1) / per)), block(256);
     with_sample_type(bits, [&](auto px) {
         typedef decltype(px) pix_t;
-        hipLaunchKernelGGL(scan_accumulate_kernel<pix_t>, grid, block, 0, st, (const pix_t*)b.Y, (const pix_t*)b.U, (const pix_t*)b.V, b.strideY,
-                           b.strideUV, b.pitchY, b.pitchUV, r.imgx, r.imgy, r.cx, r.cy, r.w, r.h, r.wUV, r.hUV, daccepted, naccepted, per, dacc);
+        hipLaunchKernelGGL(scan_accumulate_kernel<pix_t>, grid, block, 0, st, (const pix_t*)b.Y, (const pix_t*)b.U, (const pix_t*)b.V, b.strideY / es,
+                           b.strideUV / es, b.pitchY, b.pitchUV, r.imgx, r.imgy, r.cx, r.cy, r.w, r.h, r.wUV, r.hUV, daccepted, naccepted, per, dacc);
     });
     return hipGetLastError();
 }
@@ -561,14 +569,15 @@ void scan_keep_kernel(ScanKeepArgs a, const int* __restrict__ keep, long long to
     }
 }
 
-hipError_t launch_scan_keep(hipStream_t st, int es, const PlaneBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
+hipError_t launch_scan_keep(hipStream_t st, const FrameBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
                             long long first_slot)
 {
     if (nkeep <= 0 || r.w <= 0 || r.h <= 0) return hipSuccess;
-    if (es != 1 && es != 2) return hipErrorInvalidValue;
+    const int es = b.es;
+    if ((es != 1 && es != 2) || !planar_lsb(b, es)) return hipErrorInvalidValue;
     ScanKeepArgs a;
-    // (the batch's strides and pitches are in samples; everything below is in bytes)
-    a.strideY = b.strideY * es; a.strideUV = b.strideUV * es;
+    // (the batch's pitches are in samples; everything below is in bytes)
+    a.strideY = b.strideY; a.strideUV = b.strideUV;
     const long long pitchY = (long long)b.pitchY * es, pitchUV = (long long)b.pitchUV * es;
     if (pitchY > INT_MAX || pitchUV > INT_MAX) return hipErrorInvalidValue;
     a.pitchY = (int)pitchY; a.pitchUV = (int)pitchUV;
@@ -580,10 +589,8 @@ hipError_t launch_scan_keep(hipStream_t st, int es, const PlaneBatch& b, const S
     a.dstU = (uint8_t*)store.U + first_slot * a.rowC * r.hUV;
     a.dstV = (uint8_t*)store.V + first_slot * a.rowC * r.hUV;
     // a slot's rows start at multiples of the row length from the store's base, so the row length covers the destination's alignment too
-    auto width = [es](uintptr_t v) { return v % 16 == 0 ? 16 : v % 4 == 0 ? 4 : es; };
-    a.vbY = width((uintptr_t)a.srcY | (uintptr_t)store.Y | (uintptr_t)a.strideY | (uintptr_t)a.pitchY | (uintptr_t)a.rowY);
-    a.vbC = width((uintptr_t)a.srcU | (uintptr_t)a.srcV | (uintptr_t)store.U | (uintptr_t)store.V | (uintptr_t)a.strideUV | (uintptr_t)a.pitchUV |
-                  (uintptr_t)a.rowC);
+    a.vbY = scan_keep_lane_bytes(es, RowsAt{lane_addr(a.srcY), 0, a.strideY, a.pitchY}, lane_addr(store.Y), 0, a.rowY);
+    a.vbC = scan_keep_lane_bytes(es, RowsAt{lane_addr(a.srcU), lane_addr(a.srcV), a.strideUV, a.pitchUV}, lane_addr(store.U), lane_addr(store.V), a.rowC);
     a.vrowY = a.rowY / a.vbY; a.vrowC = a.rowC / a.vbC;
     a.vecsY = a.vrowY * r.h; a.vecsC = a.vrowC * r.hUV;
     const long long total = (long long)(a.vecsY + 2 * a.vecsC) * nkeep;

@@ -163,7 +163,7 @@ void delogo_surfaces_kernel(DelogoSurfaceArgs s, const float* __restrict__ plane
     else delogo_surface_row<C, 1>(srow, row, stride, rowlen, A, boff, voff, il, fd, live, maxv, s.shift, lane);
 }
 
-hipError_t launch_delogo_surfaces(hipStream_t st, int bits, const SurfaceBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g,
+hipError_t launch_delogo_surfaces(hipStream_t st, int bits, const FrameBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g,
                                   int nframes, const float2* dfades, int zero_identity)
 {
     if (nframes <= 0) return hipSuccess;
@@ -187,10 +187,11 @@ hipError_t launch_delogo_surfaces(hipStream_t st, int bits, const SurfaceBatch& 
     a.interleaved = il; a.shift = src.shift;
     // a lane's access of n containers is naturally aligned: the first container's address, stride, pitch and row length are multiples
     // of n * es bytes
-    auto width = [es](uintptr_t v) { return v % (4 * (uintptr_t)es) == 0 ? 4 : v % (2 * (uintptr_t)es) == 0 ? 2 : 1; };
-    auto b = [es](long long containers) { return (uintptr_t)(containers * es); };
-    a.nY = width((uintptr_t)a.sY | (uintptr_t)a.Y | (uintptr_t)src.strideY | b(src.pitchY) | b(g.w));
-    a.nC = width((uintptr_t)a.sU | (uintptr_t)a.sV | (uintptr_t)a.U | (uintptr_t)a.V | (uintptr_t)src.strideUV | b(src.pitchUV) | b((il ? 2LL : 1LL) * g.wUV));
+    const long long pitchY = (long long)src.pitchY * es, pitchUV = (long long)src.pitchUV * es;
+    a.nY = delogo_surface_lane_containers(es, RowsAt{lane_addr(a.sY), 0, src.strideY, pitchY}, RowsAt{lane_addr(a.Y), 0, src.strideY, pitchY},
+                                          (long long)g.w * es);
+    a.nC = delogo_surface_lane_containers(es, RowsAt{lane_addr(a.sU), lane_addr(a.sV), src.strideUV, pitchUV},
+                                          RowsAt{lane_addr(a.U), lane_addr(a.V), src.strideUV, pitchUV}, (il ? 2LL : 1LL) * g.wUV * es);
     const int rows = g.h + (il ? 1 : 2) * g.hUV;
     dim3 grid((unsigned)((rows + kSurfRows - 1) / kSurfRows), (unsigned)((nframes + kSurfFrames - 1) / kSurfFrames)), block(kSurfThreads);
     const float maxv = (float)((1 << bits) - 1);

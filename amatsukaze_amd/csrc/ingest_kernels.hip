@@ -110,8 +110,7 @@ hipError_t launch_ingest_rows(hipStream_t st, const void* src, long long src_str
                               long long nchunks)
 {
     if (!chunk || nchunks <= 0) return hipSuccess;
-    const uintptr_t a = (uintptr_t)src | (uintptr_t)dst | (uintptr_t)src_stride | (uintptr_t)dst_stride | (uintptr_t)chunk;
-    const int vb = (a % 16 == 0) ? 16 : (a % 4 == 0) ? 4 : 1;
+    const int vb = ingest_lane_bytes(lane_addr(src), lane_addr(dst), src_stride, dst_stride, chunk);
     const long long total = (long long)(chunk / vb) * nchunks;
     // enough lanes in flight to cover the PCIe round trip (a few microseconds) at the link's rate, never more than the work
     const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 2048);

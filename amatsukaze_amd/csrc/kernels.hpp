@@ -1,6 +1,8 @@
 // kernels.hpp -- the interface between the kernel files (*_kernels.hip) and the host code that launches them: every launcher is declared
 // here and nowhere else (default arguments too), and so is every struct both sides see.  Each kernel file includes it, so a definition
 // that has drifted from its declaration, or a second definition of a struct passed by value into a kernel, does not compile.
+// A batch of frames crosses it as one struct in one unit convention (FrameBatch: frame strides in bytes), and the lane widths the
+// copy-shaped launchers choose come from one rule (lane_rule.h; the weave's vec flag is still formed in amt_gpu_ingest.hip).
 // Kept light on purpose (no <vector>, <string>, <mutex>): it goes into translation units that are all device code.
 #pragma once
 
@@ -8,24 +10,26 @@
 #include <cstdint>
 
 #include "eval_plan.h"
+#include "lane_rule.h"
 
 namespace amt {
 
 struct TileDesc; struct TileBandDesc;     // eval_tiles.hpp
 
 // ---- descriptors ----
-// A batch of planar 4:2:0 frames in HBM.  Strides (between frames) and pitches (between rows) are in SAMPLES: the host divides the
-// ABI's byte strides by the sample size once, where it builds the descriptor.
-struct PlaneBatch { const void *Y, *U, *V; long long strideY, strideUV; int pitchY, pitchUV; };
-// the same batch from frame `frames` on (es: bytes per sample)
-inline PlaneBatch plane_batch_from(const PlaneBatch& b, long long frames, int es)
+// A batch of 4:2:0 frames in HBM, the one description every launcher takes.  Strides (between frames) are in BYTES, as the ABI counts them;
+// pitches (between rows) in containers of es bytes.  interleaved: U is the U0 V0 U1 V1 ... plane and V unused; sample = container >> shift.
+// Planar LSB planes are interleaved = 0, shift = 0.  A kernel whose argument list counts strides in samples gets stride / es on the line
+// that forms that argument, and nowhere else.  Built by plane_batch / surface_batch (api_common.hpp), which refuse what es does not divide.
+struct FrameBatch { const void *Y, *U, *V; long long strideY, strideUV; int pitchY, pitchUV; int es, interleaved, shift; };
+// the same batch from frame `frames` on
+inline FrameBatch plane_batch_from(FrameBatch b, long long frames)
 {
-    auto at = [&](const void* p, long long stride) { return (const void*)((const uint8_t*)p + frames * stride * es); };
-    return PlaneBatch{at(b.Y, b.strideY), at(b.U, b.strideUV), at(b.V, b.strideUV), b.strideY, b.strideUV, b.pitchY, b.pitchUV};
+    auto at = [&](const void* p, long long stride) { return (const void*)((const uint8_t*)p + frames * stride); };
+    b.Y = at(b.Y, b.strideY); b.U = at(b.U, b.strideUV); b.V = at(b.V, b.strideUV);
+    return b;
 }
-// and back to what the ABI and the evaluation engine count in: bytes between luma frames
-inline long long luma_stride_bytes(const PlaneBatch& b, int es) { return b.strideY * es; }
-// the planes Delogo writes: laid out like the PlaneBatch it reads (the same planes for the in-place call)
+// the planes Delogo writes: laid out like the FrameBatch it reads (the same planes for the in-place call)
 struct PlanesOut { void *Y, *U, *V; };
 // a 4:2:0 rectangle of a frame: origin and size in the luma plane, and in the chroma planes
 struct ScanRect { int imgx, imgy, cx, cy, w, h, wUV, hUV; };
@@ -40,38 +44,30 @@ struct EraseGeom {
     int imgx, imgy, cx, cy;       // rectangle origin in luma / chroma planes
     int uvparity;
 };
-hipError_t launch_delogo(hipStream_t st, int bits, const PlaneBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g, int nframes,
+hipError_t launch_delogo(hipStream_t st, int bits, const FrameBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g, int nframes,
                          const float2* dfades, int zero_identity);
-// erase_surface_kernels.hip: the same Delogo on decoder surfaces where they lie (interleaved and / or MSB-aligned; planar LSB surfaces are
-// ordinary planes and go to launch_delogo).  SurfaceBatch is declared below; dst is laid out like src (the same planes for the in-place call)
-struct SurfaceBatch;
-hipError_t launch_delogo_surfaces(hipStream_t st, int bits, const SurfaceBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g,
+// erase_surface_kernels.hip: the same Delogo on decoder surfaces where they lie (interleaved and / or MSB-aligned; planar LSB batches go to
+// launch_delogo, which refuses every other); dst is laid out like src (the same planes for the in-place call)
+hipError_t launch_delogo_surfaces(hipStream_t st, int bits, const FrameBatch& src, const PlanesOut& dst, const float* dplanes, EraseGeom g,
                                   int nframes, const float2* dfades, int zero_identity);
 hipError_t launch_calc_fades(hipStream_t st, const float* danalysis, int analysis_first, int analysis_count, int num_frames, int first,
                              int nframes, const uint8_t* dstate, int half, float2* dout);
+// (these three and launch_delogo take planar LSB batches; any other is hipErrorInvalidValue)
 // dout[frame] = {valid, bgY, bgU, bgV}
-hipError_t launch_scan_border(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, int thy, int nframes, int4* dout);
+hipError_t launch_scan_border(hipStream_t st, int bits, const FrameBatch& b, const ScanRect& r, int thy, int nframes, int4* dout);
 // daccepted[i] = {frame, bgY, bgU, bgV}; dacc: 3 int64 per sample of the rectangle, added to
-hipError_t launch_scan_accumulate(hipStream_t st, int bits, const PlaneBatch& b, const ScanRect& r, const int4* daccepted, int naccepted,
+hipError_t launch_scan_accumulate(hipStream_t st, int bits, const FrameBatch& b, const ScanRect& r, const int4* daccepted, int naccepted,
                                   unsigned long long* dacc);
-// the rectangle r of frames dkeep[0 .. nkeep) of a batch of es-byte samples (batch-local indices) into slots first_slot .. of a tight
+// the rectangle r of frames dkeep[0 .. nkeep) of a planar LSB batch (batch-local indices) into slots first_slot .. of a tight
 // store: Y [slot][h][w], U / V [slot][hUV][wUV] samples.  Plane bases (batch and store) are multiples of es.  One launch; none when
 // nkeep <= 0
-hipError_t launch_scan_keep(hipStream_t st, int es, const PlaneBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
+hipError_t launch_scan_keep(hipStream_t st, const FrameBatch& b, const ScanRect& r, const int* dkeep, int nkeep, const PlanesOut& store,
                             long long first_slot);
 
 // ---- surface_kernels.hip ----
-// A batch of decoder surfaces (AmtGpuSurfaces, amt_gpu.h) that has passed surface_batch (api_common.hpp): strides in bytes, pitches in
-// containers of es bytes; interleaved: U is the U0 V0 U1 V1 ... plane and V unused; sample = container >> shift (0 for LSB input)
-struct SurfaceBatch { const void *Y, *U, *V; long long strideY, strideUV; int pitchY, pitchUV; int es, interleaved, shift; };
-// a planar LSB PlaneBatch of es-byte samples as the surfaces it is
-inline SurfaceBatch planar_surfaces(const PlaneBatch& b, int es)
-{
-    return SurfaceBatch{b.Y, b.U, b.V, b.strideY * es, b.strideUV * es, b.pitchY, b.pitchUV, es, 0, 0};
-}
 // the rectangle r of all nframes surfaces as planar LSB samples: w x h luma at dst.Y, wUV x hUV chroma at dst.U / dst.V per frame (strides
 // in bytes, pitches in samples).  Plane bases are multiples of es.  One launch
-hipError_t launch_surfaces_extract(hipStream_t st, const SurfaceBatch& s, const ScanRect& r, int nframes, const PlanesOut& dst, long long dstrideY,
+hipError_t launch_surfaces_extract(hipStream_t st, const FrameBatch& s, const ScanRect& r, int nframes, const PlanesOut& dst, long long dstrideY,
                                    long long dstrideUV, int dpitchY, int dpitchUV);
 
 // ---- ingest_kernels.hip ----

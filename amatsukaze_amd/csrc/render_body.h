@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "pack16.h"
+
 namespace amt {
 
 constexpr int kRenderRows = 8;      // rows per workgroup (one wave per row, two rounds)
@@ -47,23 +49,8 @@ template <int ES, bool TEMPORAL> __device__ __forceinline__ uint32_t render_mix(
     return (render_avg<ES>(ta, tb) & m) | (spatial & ~m);
 }
 
-// both 16-bit halves of w shifted right / left by s (v_pk_lshrrev_b16 / v_pk_lshlrev_b16)
-__device__ __forceinline__ uint32_t render_pk_shr16(uint32_t w, int s)
-{
-    render_us2 v = __builtin_bit_cast(render_us2, w);
-    v >>= (unsigned short)s;
-    return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ uint32_t render_pk_shl16(uint32_t w, int s)
-{
-    render_us2 v = __builtin_bit_cast(render_us2, w);
-    v <<= (unsigned short)s;
-    return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ uint4 render_pk_shr16(uint4 v, int s)
-{
-    return uint4{render_pk_shr16(v.x, s), render_pk_shr16(v.y, s), render_pk_shr16(v.z, s), render_pk_shr16(v.w, s)};
-}
+// every 16-bit container of 16 bytes shifted right by s (pack16.h)
+__device__ __forceinline__ uint4 render_pk_shr16(uint4 v, int s) { return uint4{pk_shr16(v.x, s), pk_shr16(v.y, s), pk_shr16(v.z, s), pk_shr16(v.w, s)}; }
 
 // one missing row: nb bytes at d from the rows up / dn (and ta / tb).  The vector form issues the 2 (4) loads of a lane's 16 bytes before
 // their first use; the row's last nb % 16 bytes go container by container.  MSB (16-bit containers): the rule runs on the samples
@@ -80,8 +67,8 @@ __device__ __forceinline__ void render_fill_row(uint8_t* d, const uint8_t* up, c
             const uint32_t u = *reinterpret_cast<const T*>(up + k), w = *reinterpret_cast<const T*>(dn + k);
             uint32_t p = u, q = u;
             if constexpr (TEMPORAL) { p = *reinterpret_cast<const T*>(ta + k); q = *reinterpret_cast<const T*>(tb + k); }
-            const uint32_t v = render_mix<ES, TEMPORAL>(render_pk_shr16(u, s), render_pk_shr16(w, s), render_pk_shr16(p, s), render_pk_shr16(q, s), (uint32_t)t);
-            *reinterpret_cast<T*>(d + k) = (T)render_pk_shl16(v, s);
+            const uint32_t v = render_mix<ES, TEMPORAL>(pk_shr16(u, s), pk_shr16(w, s), pk_shr16(p, s), pk_shr16(q, s), (uint32_t)t);
+            *reinterpret_cast<T*>(d + k) = (T)pk_shl16(v, s);
             return;
         }
         const int u = *reinterpret_cast<const T*>(up + k), w = *reinterpret_cast<const T*>(dn + k);
@@ -104,7 +91,7 @@ __device__ __forceinline__ void render_fill_row(uint8_t* d, const uint8_t* up, c
             uint4 o;
             o.x = render_mix<ES, TEMPORAL>(u.x, w.x, p.x, q.x, (uint32_t)t); o.y = render_mix<ES, TEMPORAL>(u.y, w.y, p.y, q.y, (uint32_t)t);
             o.z = render_mix<ES, TEMPORAL>(u.z, w.z, p.z, q.z, (uint32_t)t); o.w = render_mix<ES, TEMPORAL>(u.w, w.w, p.w, q.w, (uint32_t)t);
-            if constexpr (MSB) { o.x = render_pk_shl16(o.x, s); o.y = render_pk_shl16(o.y, s); o.z = render_pk_shl16(o.z, s); o.w = render_pk_shl16(o.w, s); }
+            if constexpr (MSB) { o.x = pk_shl16(o.x, s); o.y = pk_shl16(o.y, s); o.z = pk_shl16(o.z, s); o.w = pk_shl16(o.w, s); }
             *reinterpret_cast<uint4*>(d + x) = o;
         }
         for (int k = (nb & ~15) + lane * ES; k < nb; k += 64 * ES) one(k);             // the row's last nb % 16 bytes

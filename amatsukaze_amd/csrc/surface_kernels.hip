@@ -120,7 +120,7 @@ void surfaces_extract_kernel(SurfaceExtractArgs a, long long total_vecs)
     }
 }
 
-hipError_t launch_surfaces_extract(hipStream_t st, const SurfaceBatch& s, const ScanRect& r, int nframes, const PlanesOut& dst, long long dstrideY,
+hipError_t launch_surfaces_extract(hipStream_t st, const FrameBatch& s, const ScanRect& r, int nframes, const PlanesOut& dst, long long dstrideY,
                                    long long dstrideUV, int dpitchY, int dpitchUV)
 {
     if (nframes <= 0 || r.w <= 0 || r.h <= 0) return hipSuccess;
@@ -143,19 +143,11 @@ hipError_t launch_surfaces_extract(hipStream_t st, const SurfaceBatch& s, const 
     a.h = r.h; a.hUV = r.hUV;
     a.es = es; a.interleaved = il; a.shift = s.shift;
     const int rowY = r.w * es, rowC = r.wUV * es * (il ? 2 : 1);          // SOURCE bytes of a rectangle row
-    auto bits_of = [](uintptr_t v, uintptr_t m) { return v % m == 0; };
-    const uintptr_t srcYbits = (uintptr_t)a.srcY | (uintptr_t)a.sstrideY | (uintptr_t)a.spitchY | (uintptr_t)rowY;
-    const uintptr_t dstYbits = (uintptr_t)a.dstY | (uintptr_t)a.dstrideY | (uintptr_t)a.dpitchY;
-    a.vbY = bits_of(srcYbits | dstYbits, 16) ? 16 : bits_of(srcYbits | dstYbits, 4) ? 4 : es;
-    const uintptr_t srcCbits = (uintptr_t)a.srcU | (uintptr_t)a.srcV | (uintptr_t)a.sstrideUV | (uintptr_t)a.spitchUV | (uintptr_t)rowC;
-    const uintptr_t dstCbits = (uintptr_t)a.dstU | (uintptr_t)a.dstV | (uintptr_t)a.dstrideUV | (uintptr_t)a.dpitchUV;
-    if (il) {
-        // a lane stores half of what it loads to each plane: 8-byte stores behind a 16-byte load, 2-byte stores behind a 4-byte one
-        a.vbC = bits_of(srcCbits, 16) && bits_of(dstCbits, 8) ? 16 : bits_of(srcCbits, 4) && bits_of(dstCbits, 2) ? 4 : 2 * es;
-    } else {
-        a.vbC = bits_of(srcCbits | dstCbits, 16) ? 16 : bits_of(srcCbits | dstCbits, 4) ? 4 : es;
-    }
-    a.pairC = il && !(bits_of(srcCbits, 4) && bits_of(dstCbits, 2));
+    a.vbY = extract_lane_bytes(es, RowsAt{lane_addr(a.srcY), 0, a.sstrideY, a.spitchY}, RowsAt{lane_addr(a.dstY), 0, a.dstrideY, a.dpitchY}, rowY);
+    const RowsAt srcC{lane_addr(a.srcU), lane_addr(a.srcV), a.sstrideUV, a.spitchUV}, dstC{lane_addr(a.dstU), lane_addr(a.dstV), a.dstrideUV, a.dpitchUV};
+    const SplitLanes split = extract_split_lanes(es, srcC, dstC, rowC);
+    a.vbC = il ? split.bytes : extract_lane_bytes(es, srcC, dstC, rowC);
+    a.pairC = il ? split.pairwise : 0;
     a.vrowY = rowY / a.vbY; a.vrowC = rowC / a.vbC;
     a.vecsY = a.vrowY * r.h; a.vecsC = a.vrowC * r.hUV;
     const long long total = (long long)(a.vecsY + (il ? 1 : 2) * a.vecsC) * nframes;

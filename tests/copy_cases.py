@@ -200,7 +200,7 @@ WEAVE_CASES = [
 GRID_PASS = 2048 * 256                 # lanes of one pass of ingest_rows_kernel's grid
 
 
-# RESTATES launch_ingest_rows (ingest_kernels.hip); byte offsets are relative to 16-byte-aligned allocations.  Used only to assert
+# RESTATES launch_ingest_rows (ingest_kernels.hip; ingest_lane_bytes, lane_rule.h); byte offsets are relative to 16-byte-aligned allocations.  Used only to assert
 # that the tables reach every lane width.
 def row_lanes(src_off, src_stride, dst_off, dst_stride, chunk):
     a = src_off | src_stride | dst_off | dst_stride | chunk
