@@ -10,7 +10,8 @@
 //   tail  the elements behind the last boundary (at most 7),
 // head and tail read with one 2-byte load per lane (lanes 0..6 and 8..14).  The aligned addresses are found by rounding the span's START
 // UP and its END DOWN, so no load touches a byte outside the span, let alone outside the caller's buffer.  A lane of the last group that
-// has no chunk re-reads the group's last one and drops the value (branch-free: the loads of a group leave back to back).
+// has no chunk re-reads the span's last one and drops the value (branch-free: the loads of a group leave back to back).  The split
+// and the offset of every load are audio_span.h's functions, which tests/cpp/audio_span_replay.cpp replays on the host.
 //
 // Exact for every input: |s| is taken in packed 16-bit lanes as max(s, 0 - s), which leaves 0x8000 for -32768 -- 32768 once the lane is
 // read as UNSIGNED, as every later step does; the sum of |s| is kept in 32 bits for one group (64 elements a lane: at most 2^21) and in
@@ -18,6 +19,7 @@
 // to a 64-bit total.  The wave's 64 partials are folded by DPP (row_shr / row_bcast, stats_body.h's pattern; the 64-bit sums as two
 // halves moved by the same DPP control and one 64-bit add per step) into lane 63, which writes the record with plain stores.
 #include "build_knobs.h"
+#include "audio_span.h"
 #include "kernels.hpp"
 
 #include <hip/hip_runtime.h>
@@ -28,7 +30,6 @@ namespace {
 
 constexpr int kAudioThreads = 256;
 constexpr int kAudioWaves = kAudioThreads / 64;       // video frames per workgroup
-constexpr int kAudioGroup = 8;                        // 16-byte loads a lane has in flight
 
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef short s2 __attribute__((ext_vector_type(2)));
@@ -106,38 +107,30 @@ void audio_levels_kernel(const int16_t* __restrict__ pcm, long long pcm_first, A
     if (s1 > s0) {
         const long long e0 = (s0 - pcm_first) * t.channels, e1 = (s1 - pcm_first) * t.channels;      // elements of pcm
         count = e1 - e0;
-        // byte offsets from pcm (every address below is pcm + offset: the loads stay global ones)
-        const unsigned mis = (unsigned)(uintptr_t)pcm & 15u;
-        const long long a0 = 2 * e0, a1 = 2 * e1;
-        const long long b0 = min(((a0 + mis + 15) & ~15LL) - mis, a1);      // the span's start rounded UP to a 16-byte address, at most its end
-        const long long b1 = max(((a1 + mis) & ~15LL) - mis, b0);          // its end rounded DOWN, never below b0
-        const unsigned nhead = (unsigned)(b0 - a0) / 2, ntail = (unsigned)(a1 - b1) / 2;
-        const long long nchunks = (b1 - b0) / 16;
+        // byte offsets from pcm (every address below is pcm + offset: the loads stay global ones); the split and every offset: audio_span.h
+        const AudioSpan sp = audio_span_split((unsigned)(uintptr_t)pcm & 15u, e0, e1);
         const char* const bytes = reinterpret_cast<const char*>(pcm);
 
         // head and tail: lanes without an element read the span's first one (it exists) and drop it
-        const bool head = lane < nhead, tail = lane >= 8 && lane - 8 < ntail;
-        const long long edge_off = head ? a0 + 2 * lane : tail ? b1 + 2 * (lane - 8) : a0;
-        const unsigned edge_word = *reinterpret_cast<const unsigned short*>(bytes + edge_off);
+        const AudioEdgeLoad edge_load = audio_span_edge_load(sp, lane);
+        const unsigned edge_word = *reinterpret_cast<const unsigned short*>(bytes + edge_load.off);
 
-        const u4* body = reinterpret_cast<const u4*>(bytes + b0);
-        for (long long c0 = 0; c0 < nchunks; c0 += 64 * kAudioGroup) {
+        const u4* body = reinterpret_cast<const u4*>(bytes + sp.b0);
+        for (long long c0 = 0; c0 < sp.nchunks; c0 += 64 * kAudioGroup) {
             u4 v[kAudioGroup];
 #pragma unroll
-            for (int k = 0; k < kAudioGroup; ++k) {
-                const long long c = c0 + k * 64 + lane;
-                v[k] = __builtin_nontemporal_load(body + min(c, nchunks - 1));
-            }
+            for (int k = 0; k < kAudioGroup; ++k)
+                v[k] = __builtin_nontemporal_load(body + audio_span_body_load(sp, c0, k, lane).chunk);
             __builtin_amdgcn_sched_barrier(0);            // the group's loads all leave before the first value is used
 #pragma unroll
             for (int k = 0; k < kAudioGroup; ++k) {
-                const bool mine = c0 + k * 64 + lane < nchunks;
+                const bool mine = audio_span_body_load(sp, c0, k, lane).mine;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc.add(mine ? v[k][j] : 0u);
             }
             acc.fold();
         }
-        acc.add(head || tail ? edge_word : 0u);
+        acc.add(audio_span_edge_counts(edge_load) ? edge_word : 0u);
         acc.fold();
     }
 

@@ -1,5 +1,6 @@
-"""Inputs and numpy references of the audio tests (tests/test_audio_host.py, tests/test_gpu_audio_levels.py): an amts file with its
-wave file, AMTSource::GetAudio restated in numpy, the per-video-frame level records and the mute sections restated in numpy."""
+"""Inputs and numpy references of the audio tests (tests/test_audio_host.py, tests/test_gpu_audio_levels.py, tests/test_gpu_audio_spans.py):
+an amts file with its wave file, AMTSource::GetAudio restated in numpy, the per-video-frame level records and the mute sections restated
+in numpy, and the kernel's split of a span restated in Python (for the checks that a case list reaches what it says)."""
 import os
 
 import numpy as np
@@ -100,6 +101,41 @@ def levels_ref(pcm, sample_rate, channels, fps_num, fps_den, num_samples, first_
         if x.size:
             out[i] = (int(x.max()), int(x.sum()), int((x * x).sum()), x.size)
     return out
+
+
+def levels_ref_window(pcm, pcm_first, sample_rate, channels, fps_num, fps_den, num_samples, first_frame, nframes):
+    """levels_ref for a window of the timeline: pcm's row 0 is sample-frame pcm_first, (>= the frames' cover, channels) int16.  Positions
+    are Python integers throughout, so a batch may lie anywhere in the timeline; a span outside the window is an error, not a guess"""
+    pcm = np.asarray(pcm).reshape(-1, channels)
+    out = np.zeros((nframes, 4), np.uint64)
+    for i in range(nframes):
+        s0 = min(frame_start(int(first_frame) + i, sample_rate, fps_num, fps_den), int(num_samples))
+        s1 = min(frame_start(int(first_frame) + i + 1, sample_rate, fps_num, fps_den), int(num_samples))
+        if s1 <= s0:
+            continue
+        assert int(pcm_first) <= s0 and s1 - int(pcm_first) <= pcm.shape[0], "the window does not cover the frame's span"
+        x = [abs(int(v)) for v in pcm[s0 - int(pcm_first):s1 - int(pcm_first)].reshape(-1)]
+        out[i] = (max(x), sum(x), sum(v * v for v in x), len(x))
+    return out
+
+
+class SpanSplit:
+    """audio_levels_kernel's split of the elements [e0, e1) of a buffer whose address has the low four bits `mis` (audio_span.h,
+    restated): byte offsets a0 <= b0 <= b1 <= a1, head and tail in elements, body in 16-byte chunks and in groups of 512 chunks"""
+
+    def __init__(self, mis, e0, e1):
+        assert mis % 2 == 0 and 0 <= mis < 16 and e1 > e0
+        self.a0, self.a1 = 2 * e0, 2 * e1
+        self.b0 = min(((self.a0 + mis + 15) & ~15) - mis, self.a1)
+        self.b1 = max(((self.a1 + mis) & ~15) - mis, self.b0)
+        self.nhead, self.ntail = (self.b0 - self.a0) // 2, (self.a1 - self.b1) // 2
+        self.nchunks = (self.b1 - self.b0) // 16
+        self.groups = -(-self.nchunks // 512)
+        self.whole_head = self.nchunks == 0 and self.ntail == 0           # the span holds no 16-byte boundary behind its start
+
+
+def span_split(mis, e0, e1):
+    return SpanSplit(mis, e0, e1)
 
 
 def mute_sections_ref(levels, mute_level, min_frames):
