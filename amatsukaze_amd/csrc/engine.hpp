@@ -208,6 +208,7 @@ private:
     // tile plans (eval_tiles.hpp), built when the pair kernel is chosen
     void ensure_tiles();
     bool tiles_ready_ = false;
+    bool tile_slots_ok_ = true;                    // every logo's plan has fewer than kTileSlotLimit slots (decided in ensure_tiles)
     std::vector<DevBuf<float2>> d_tkp_, d_tsc_, d_tpq_;
     std::vector<DevBuf<uint32_t>> d_tinfo_, d_tpos_;
     std::vector<DevBuf<char>> d_tlin_;

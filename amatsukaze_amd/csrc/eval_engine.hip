@@ -246,16 +246,20 @@ bool EvalEngine::pair_eligible()
             if (!(std::fabs(a[p]) + std::fabs(b[p]) < 8192.0f)) return false;       // |bg| <= (|a| + |b|) * 65535 < 2^30; NaN fails the comparison
     }
     ensure_tiles();
+    if (!tile_slots_ok_) return false;
     pair_state_ = 1;
     return true;
 }
 
-// the pair kernel addresses a frame's samples with 32-bit byte offsets
+// the tile kernels address a frame's samples with 32-bit byte offsets, and form them -- a row number times the pitch in bytes, a logo row
+// times the logo's width -- with 24-bit multiplies (eval_tiles.hpp mul24): the OPERANDS stay below 2^24, the offsets below 2^31
 bool EvalEngine::pair_addressable(int pitch_bytes) const
 {
     for (const EvalLogoSpec& S : specs_) {
-        const long long last = (long long)(S.imgy + S.row0 + (long long)S.planes.h * S.row_step + 1) * pitch_bytes + (long long)(S.imgx + S.planes.w) * 2;
+        const long long last_row = (long long)S.imgy + S.row0 + (long long)S.planes.h * S.row_step + 1;
+        const long long last = last_row * pitch_bytes + (long long)(S.imgx + S.planes.w) * 2;
         if (last >= (1LL << 31) || pitch_bytes <= 0) return false;
+        if ((long long)S.imgy + S.row0 < 0 || !tile_mul24_operands_ok(pitch_bytes, S.row_step, last_row, S.planes.w, S.planes.h)) return false;
     }
     return true;
 }
@@ -275,6 +279,9 @@ void EvalEngine::ensure_tiles()
         // (the scan -- fades {0, 1}: the pair kernel, raster-order sums -- takes the cut with the lower modelled critical path; every
         //  other engine keeps the coarse cut: the linear kernel's summation order follows the tiles)
         const TilePlan P = build_tile_plan(T.pos, T.count, S.planes.w, S.planes.h, fades_.size() == 2 ? kTileCutBest : kTileCutCoarse);
+        // (a sparse mask spends a whole tile of 64 slots on a few pixels: the slot count is bounded by nothing but this check.  Beyond the
+        //  limit no table is built and both tile kernels are off for this engine: pair_eligible, run_linear)
+        if (!tile_slots_ok(P.nslots())) { tile_slots_ok_ = false; continue; }
         const size_t ns = (size_t)P.nslots();
         std::vector<float2> kp(13 * ns, float2{0.0f, 0.0f}), sc((size_t)kNumBins * ns, float2{0.0f, 0.0f}), pq(ns, float2{0.0f, 0.0f});
         std::vector<uint32_t> spos(ns, 0u);
@@ -406,7 +413,8 @@ bool EvalEngine::tiles_usable(int pitch_bytes) const
 {
     for (const EvalLogoSpec& S : specs_) {
         const int w = S.planes.w, h = S.planes.h;
-        // (24-bit slot byte offsets; the linear kernel's list entries carry the slot number -- at most 1.1 x count -- in 20 bits)
+        // (24-bit slot byte offsets; the linear kernel's list entries carry the slot number in 20 bits: about 1.1 x count for a dense mask,
+        //  checked for every plan in ensure_tiles -- tile_slots_ok)
         if (w < 6 || (w & 1) || h < 5 || S.tables.count <= 0 || S.tables.count >= 900000) return false;
     }
     return pair_addressable(pitch_bytes);
@@ -431,6 +439,7 @@ void EvalEngine::run_linear(const void* dY, int64_t frame_stride_bytes, int pitc
     ensure_linear();
     if (!lin_formula_ok_) { run(dY, frame_stride_bytes, pitch, bits, nframes, dout, dframe_map); return; }      // (a degenerate logo: the exact kernel)
     ensure_tiles();
+    if (!tile_slots_ok_) { run(dY, frame_stride_bytes, pitch, bits, nframes, dout, dframe_map); return; }      // (a tile plan beyond the slot limit: the exact kernel)
     ctx_->bind();
     if (frame_stride_bytes % es) throw std::runtime_error("frame stride not a multiple of the sample size");
     const int nl = (int)specs_.size();

@@ -190,6 +190,18 @@ __device__ __forceinline__ f2 pk_fma_hi_lo_v(f2 a, f2 v)
     return r;
 }
 
+// max(|r|, L) of a term's scale as ONE instruction, L (the logo's floorResp, wave-uniform) read from its scalar register.  As
+// __builtin_fmaxf(__builtin_fabsf(r), L) it took two per fade and one more per trip: r comes out of inline assembly and L out of
+// memory, the compiler cannot know either to be canonical (quiet, not denormal where those are flushed) and puts v_max_f32 x, |r|, |r|
+// and v_max_f32 l, L, L in front of the maximum it was asked for.  r is finite (non-finite response lines keep the exact kernel:
+// EvalEngine::ensure_linear) and fp32 denormals are on, so those change no bit and neither does leaving them out.
+__device__ __forceinline__ float max_abs_floor(float r, float L)
+{
+    float m;
+    asm("v_max_f32 %0, |%1|, %2" : "=v"(m) : "v"(r), "s"(L));
+    return m;
+}
+
 // One wave's staging state, as eval_tile_stage.h's TileStager but with the loads above and fewer registers: only the unit's own row
 // offset is kept -- the rows above / below are re-derived at every request -- and "this row is blended" rides in the sign bit of the
 // unit's LDS offset.  BLEND = false: a field logo, whose rows are the source rows themselves (CopyY): one row load per unit instead of
@@ -236,9 +248,11 @@ template <typename pix_t, bool BLEND> struct LinStager {
             const TileUnit U = tile_unit(T, lane + 64 * k, w);
             const bool blend = BLEND && deint && U.y > 0 && U.y < h - 1;       // DeintY copies the first and the last row (LogoScan.hpp:763-780)
             ulds[k] = U.lds | (blend ? (int)0x80000000 : 0);
-            ug[k] = (srow0 + U.y * srow_step) * pitchB + (scol0 + U.xs) * ES;
-            ua[k] = gld<f4a8>(base, (unsigned)(U.y * w + U.xs) * 4u + oa);
-            ub[k] = gld<f4a8>(base, (unsigned)(U.y * w + U.xs) * 4u + ob);
+            // (24-bit multiplies, as TileStager::setup_units: every operand is below 2^24 -- tile_mul24_operands_ok on the host)
+            ug[k] = (int)mul24((unsigned)srow0 + mul24_opaque((unsigned)U.y, (unsigned)srow_step), (unsigned)pitchB) + (scol0 + U.xs) * ES;
+            const unsigned ocoef = (mul24((unsigned)U.y, (unsigned)w) + (unsigned)U.xs) * 4u;
+            ua[k] = gld<f4a8>(base, ocoef + oa);
+            ub[k] = gld<f4a8>(base, ocoef + ob);
         }
         coef_fresh = true;
     }
@@ -398,6 +412,10 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
         for (int f = 0; f < NF; ++f) fd[f] = fp[f];
 #pragma unroll
         for (int j = 0; j < NP; ++j) fdp[j] = f2{fd[2 * j], fd[2 * j + 1]};
+        // (consumed HERE: the compiler's wait for these scalar loads must not drift to their first use inside the loop -- no path into
+        //  the loop's partial lgkmcnt waits may carry a scalar load in flight, not even the one only a wave without tiles takes, which
+        //  skips the loop; tests/test_isa_guards.py walks every path)
+        asm volatile("" : : "s"(fd[0]), "s"(fd[NF - 1]));
     }
     float* const myacc = wacc + wave * G * (kLinAccFrameBytes / 4);
     for (int i = lane; i < G * (kLinAccFrameBytes / 4); i += 64) myacc[i] = 0.0f;
@@ -524,55 +542,57 @@ __device__ __forceinline__ void logo_eval_linear_body(const LinLaunch& A)
         //      r is |P + Q bin| up to the rounding of the table's fp32 evaluation (the composite of a flat level is affine in the level):
         //      one multiply-add instead of an 8-byte gather per fade; what the difference can do to a term is computed per (pixel, bin)
         //      on the host and is part of the error bound (eval_engine.hip ensure_linear).  Then the sum over each quad of lanes by two
-        //      DPP steps; lane 0 of the quad adds the sums to the quad's running sums of the frame in LDS (48 bytes per quad: 16 partial
+        //      DPP steps; lanes 0..2 of the quad add the sums to the quad's running sums of the frame in LDS (48 bytes per quad: 16 partial
         //      sums per fade, added up at the very end).  A lane's cells are its own and LDS operations of a wave complete in order: no
         //      barrier, no atomics. ----
         {
             typedef __attribute__((address_space(3))) f4* lds_quad;
             const float R0 = R.x, dR = R.y - R.x;
-            // Every lane of a quad ends up with all eleven quad sums; lane j < 3 of the quad keeps the four of fades 4j .. 4j + 3 and adds
-            // them to its 16 bytes of the quad's cell: ONE 16-byte read-modify-write per iteration for the whole wave (a 16-byte LDS store
-            // costs 13 cycles of the CU's store path whatever its exec mask: three of them by lane 0 alone were a fifth of the loop's LDS time)
+            // Lane j < 3 of a quad ends up with the quad's sums of fades 4j .. 4j + 3 and adds them to its 16 bytes of the quad's cell: ONE
+            // 16-byte read-modify-write per iteration for the whole wave (a 16-byte LDS store costs 13 cycles of the CU's store path whatever
+            // its exec mask: three of them by lane 0 alone were a fifth of the loop's LDS time)
             f4 mine;
             const f2 RR = f2{R0, dR};
-            float term[NF + 1];
+            float term[NF];
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
                 const f2 resp = pk_fma_hi_lo_v(binp[j], PQ);        // {Q * bin + P} of the two fades
                 const f2 x = pk_fma_hi_lo_s(fdp[j], RR);            // {fade * dR + R0}
                 const f2 md = f2{__builtin_amdgcn_fmed3f(x.x, -__builtin_fabsf(resp.x), __builtin_fabsf(resp.x)),
                                  __builtin_amdgcn_fmed3f(x.y, -__builtin_fabsf(resp.y), __builtin_fabsf(resp.y))};
-                const f2 rc = f2{__builtin_amdgcn_rcpf(__builtin_fmaxf(__builtin_fabsf(resp.x), floorResp)),
-                                 __builtin_amdgcn_rcpf(__builtin_fmaxf(__builtin_fabsf(resp.y), floorResp))};
+                const f2 rc = f2{__builtin_amdgcn_rcpf(max_abs_floor(resp.x, floorResp)), __builtin_amdgcn_rcpf(max_abs_floor(resp.y, floorResp))};
                 const f2 tt = md * rc;
                 term[2 * j] = tt.x; term[2 * j + 1] = tt.y;
             }
             {
-                const float resp = __builtin_fabsf(__builtin_fmaf(PQ.y, binl, PQ.x));
+                const float rl = __builtin_fmaf(PQ.y, binl, PQ.x), resp = __builtin_fabsf(rl);
                 const float x = __builtin_fmaf(fd[NF - 1], dR, R0);
-                term[NF - 1] = __builtin_amdgcn_fmed3f(x, -resp, resp) * __builtin_amdgcn_rcpf(__builtin_fmaxf(resp, floorResp));
-                term[NF] = 0.0f;
+                term[NF - 1] = __builtin_amdgcn_fmed3f(x, -resp, resp) * __builtin_amdgcn_rcpf(max_abs_floor(rl, floorResp));
             }
+            // The sums over each quad of lanes as a reduce-scatter: a lane hands its partner the terms it will not keep and adds what it is
+            // handed.  Step 1 (partner l ^ 1): the even lane keeps fades 0..3 and 8..10, the odd lane 4..7; step 2 (partner l ^ 2): lane 0
+            // keeps 0..3, lane 1 4..7, lane 2 8..10.  The association is (l0 + l1) + (l2 + l3) -- what two DPP adds of every term in every
+            // lane, followed by eight selects, gave (30 instructions; these are 14 selects + 11 DPP adds), so the sums are the same bits.
+            // The twelfth value of a cell is padding: what lane 2 adds to it, and everything lane 3 holds, is never read.
+            static_assert(NF == 11, "the exchange is written out for eleven fades: three lanes of four, the last one short");
+            {
+                const bool odd = (lane & 1) != 0, hi2 = (lane & 2) != 0;
+                auto xadd = [](float keep, float give, int perm1) -> float {
+                    float r = keep + __builtin_bit_cast(float, perm1 ? __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, give), 0xB1, 0xF, 0xF, true)     // quad_perm:[1,0,3,2]
+                                                                     : __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, give), 0x4E, 0xF, 0xF, true));   // quad_perm:[2,3,0,1]
+                    asm volatile("" : "+v"(r));
+                    return r;
+                };
+                float u[7];
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                float tq[4];
+                for (int i = 0; i < 4; ++i) u[i] = xadd(odd ? term[4 + i] : term[i], odd ? term[i] : term[4 + i], 1);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int f = 4 * q + r;
-                    if (f < NF) {
-                        float t = term[f];
-                        t += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, t), 0xB1, 0xF, 0xF, true));   // quad_perm:[1,0,3,2]
-                        t += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, t), 0x4E, 0xF, 0xF, true));   // quad_perm:[2,3,0,1]
-                        asm volatile("" : "+v"(t));       // (left alone the add sinks behind the selects below and its DPP operand stays a v_mov_b32_dpp: one more instruction per fade)
-                        tq[r] = t;
-                    } else tq[r] = 0.0f;
-                }
-                if (q == 0) mine = f4{tq[0], tq[1], tq[2], tq[3]};
-                else {
-                    const bool me = (lane & 3) == q;
-                    mine = f4{me ? tq[0] : mine[0], me ? tq[1] : mine[1], me ? tq[2] : mine[2], me ? tq[3] : mine[3]};
-                }
-                __builtin_amdgcn_sched_barrier(0);          // (four fades at a time: left alone the scheduler forms all eleven sums first -- eleven registers too many)
+                for (int i = 0; i < 3; ++i) u[4 + i] = xadd(term[8 + i], term[8 + i], 1);
+                float m[4];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) m[i] = xadd(hi2 ? u[4 + i] : u[i], hi2 ? u[i] : u[4 + i], 0);
+                m[3] = xadd(u[3], u[3], 0);
+                mine = f4{m[0], m[1], m[2], m[3]};
             }
             if ((lane & 3) != 3) {
                 const lds_quad cell = (lds_quad)(unsigned long long)(myacc_base + (unsigned)g0 * (unsigned)kLinAccFrameBytes + (unsigned)(lane >> 2) * 48u + (unsigned)(lane & 3) * 16u);

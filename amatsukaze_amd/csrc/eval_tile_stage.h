@@ -230,6 +230,15 @@ template <> struct Quad<uint16_t> {
     }
 };
 
+// mul24() whose result the optimiser cannot look into.  An outer mul24 reads only 24 bits of an inner one, which the compiler takes as
+// leave to widen the inner multiply to a full v_mul_lo_u32 again (it cannot see that the operands are small; the host checked).
+__device__ __forceinline__ unsigned mul24_opaque(unsigned a, unsigned b)
+{
+    unsigned r = mul24(a, b);
+    asm("" : "+v"(r));
+    return r;
+}
+
 typedef const __attribute__((address_space(4))) TileDesc* const_tile_ptr;          // constant address space: scalar loads
 typedef const __attribute__((address_space(4))) int* const_int_ptr;
 __device__ __forceinline__ void fetch_tile(TileDesc& D, const_tile_ptr t)
@@ -275,12 +284,15 @@ template <typename pix_t> struct TileStager {
             const bool blend = deint && U.y > 0 && U.y < h - 1;       // DeintY copies the first and the last row (LogoScan.hpp:763-780)
             ulds[k] = U.lds;
             ubias[k] = blend ? Quad<pix_t>::kBias : 0u;
-            ug[k][1] = (srow0 + U.y * srow_step) * pitchB + (scol0 + U.xs) * ES;
+            // (24-bit multiplies, eval_tiles.hpp mul24: logo rows and widths, the source row number and the pitch in bytes are below
+            //  2^24 -- tile_mul24_operands_ok on the host; the byte offset itself may be anything below 2^31)
+            ug[k][1] = (int)mul24((unsigned)srow0 + mul24_opaque((unsigned)U.y, (unsigned)srow_step), (unsigned)pitchB) + (scol0 + U.xs) * ES;
             ug[k][0] = blend ? ug[k][1] - pitchB : ug[k][1];
             ug[k][2] = blend ? ug[k][1] + pitchB : ug[k][1];
             typedef f4 __attribute__((aligned(8))) f4a8;
-            ua[k] = gld<f4a8>(gA, (unsigned)(U.y * w + U.xs) * 4u);
-            ubmv[k] = gld<f4a8>(gB, (unsigned)(U.y * w + U.xs) * 4u);
+            const unsigned ocoef = (mul24((unsigned)U.y, (unsigned)w) + (unsigned)U.xs) * 4u;
+            ua[k] = gld<f4a8>(gA, ocoef);
+            ubmv[k] = gld<f4a8>(gB, ocoef);
         }
     }
     // b -> b * maxv, rounded once, exactly as in a*s + b*maxv: called once between setup_units() and the next convert(), at a point where

@@ -48,18 +48,45 @@ struct TileBandDesc {
 #else
 #define AMT_TILE_HD inline
 #endif
+// a * b for operands below 2^24 -- tile coordinates, logo dimensions, row numbers, a pitch in bytes.  On the device one
+// v_mul_u32_u24 / v_mad_u32_u24 (the issue cost of an add) instead of the full-width v_mul_lo_u32, which issues at a quarter of that
+// rate; the low 32 bits of the 48-bit product, so the PRODUCT may exceed 2^24 (a row offset in an 18 MB frame does).  The host -- the
+// CPU replay of the kernels' addressing -- multiplies plainly.  The operand limits are enforced where the kernels are chosen:
+// tile_mul24_operands_ok() below, EvalEngine::pair_addressable.
+AMT_TILE_HD unsigned mul24(unsigned a, unsigned b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul24(a, b);
+#else
+    return a * b;
+#endif
+}
+constexpr long long kMul24Limit = 1LL << 24;          // operands of mul24() lie below it
+constexpr long long kTileSlotLimit = 1LL << 20;       // slots of a logo's tile plan: the linear kernel's list entries carry the slot number in 20 bits,
+                                                      // and 8 * nslots is a 24-bit multiplier of the scan kernel's scale gather
+// What the tile kernels multiply with mul24() beyond tile coordinates: a logo row (below h) times row_step, the source row number that
+// gives (at most last_row: the row below the rectangle's last) times the pitch in bytes, and a logo row times the logo's width (w, h:
+// what the 16-bit halves of MaskTables::pos can hold).  Not met: the caller keeps the generic kernel.
+inline bool tile_mul24_operands_ok(long long pitch_bytes, long long row_step, long long last_row, long long w, long long h)
+{
+    return pitch_bytes > 0 && pitch_bytes < kMul24Limit && row_step >= 1 && row_step < kMul24Limit &&
+           last_row >= 0 && last_row < kMul24Limit && w > 0 && w <= 65536 && h > 0 && h <= 65536;
+}
+inline bool tile_slots_ok(long long nslots) { return nslots >= 0 && nslots < kTileSlotLimit; }
+
 // staging unit u of a tile (one tile row x four columns; units beyond the tile's last repeat it): the logo row and first column
 // it covers and its pair offset in the tile plane.  Shared by the kernel and the CPU replay of its addressing.
+// (24-bit multiplies: u < 128 and rcp <= 65536, so u * rcp < 2^23; row < 128, ncol4 <= 128, tp < 512.)
 struct TileUnit { int y, xs, lds; };
 AMT_TILE_HD TileUnit tile_unit(const TileDesc& T, int u, int w)
 {
     const int last = T.nrows * T.ncol4 - 1;
     u = u < last ? u : (last < 0 ? 0 : last);
-    const int row = (u * T.rcp) >> 16;
-    const int c4 = u - row * T.ncol4;
+    const int row = (int)(mul24((unsigned)u, (unsigned)T.rcp) >> 16);
+    const int c4 = u - (int)mul24((unsigned)row, (unsigned)T.ncol4);
     const int x = T.x0 + 4 * c4;
     const int xs = x < w - 4 ? x : w - 4;             // a ragged right edge: the last unit moves left
-    return TileUnit{T.y0 + row, xs, row * T.tp + (xs - T.x0)};
+    return TileUnit{T.y0 + row, xs, (int)mul24((unsigned)row, (unsigned)T.tp) + (xs - T.x0)};
 }
 
 // Workgroup -> (logo, frame group) of the scan's tile kernel.  Workgroups are dealt to the 8 XCDs round-robin by their linear id, each XCD
