@@ -209,6 +209,9 @@ private:
     void ensure_tiles();
     bool tiles_ready_ = false;
     bool tile_slots_ok_ = true;                    // every logo's plan has fewer than kTileSlotLimit slots (decided in ensure_tiles)
+    // DeintY's 0.25 folded into the taps of the scan's pair kernel: every logo is checked (stage4_eligible), the engine decides (ensure_tiles)
+    static bool stage4_eligible(const EvalLogoSpec& S);
+    bool tiles_stage4_ = false;                    // the taps carry the 0.25; otherwise the pair kernel's ldexp form runs on plain taps
     std::vector<DevBuf<float2>> d_tkp_, d_tsc_, d_tpq_;
     std::vector<DevBuf<uint32_t>> d_tinfo_, d_tpos_;
     std::vector<DevBuf<char>> d_tlin_;

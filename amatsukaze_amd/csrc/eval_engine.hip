@@ -1,6 +1,7 @@
 // eval_engine.hip -- host side of the evaluation kernel: run slots, band partition, table upload, launches.
 #include "build_knobs.h"
 #include "engine.hpp"
+#include "exact_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -201,10 +202,12 @@ void EvalEngine::run(const void* dY, int64_t frame_stride_bytes, int pitch, int 
     if (pair_eligible() && pair_addressable(pitch * es)) {
         // fades {0, 1}: the window of s and the window of bg are the two blends themselves
         const size_t dot = prof_name_.find('.');
-        const int sp = ctx_->prof_begin(("logo_eval_pair_kernel" + (dot == std::string::npos ? std::string() : prof_name_.substr(dot))).c_str());
+        const std::string suffix = dot == std::string::npos ? std::string() : prof_name_.substr(dot);
         const int Gp = group_frames_ > 0 ? group_frames_ : (int)std::max(1LL, std::min((long long)kTileMaxFrames, (long long)nframes * nl / 2048));
+        // (tables that carry DeintY's 0.25 -- every engine, in practice -- or the kernel's ldexp form on unscaled ones: ensure_tiles)
+        const int sp = ctx_->prof_begin(((tiles_stage4_ ? "logo_eval_pair_kernel" : "logo_eval_pair_ldexp_kernel") + suffix).c_str());
         AMT_HIP(launch_logo_eval_pair(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, dY, dframe_map,
-                                      frame_stride_bytes / es, pitch, nframes, Gp, dout, out_frame_stride_, take_abs_ ? 1 : 0));
+                                      frame_stride_bytes / es, pitch, nframes, Gp, dout, out_frame_stride_, take_abs_ ? 1 : 0, tiles_stage4_ ? 0 : 1));
         ctx_->prof_end(sp);
         return;
     }
@@ -264,6 +267,41 @@ bool EvalEngine::pair_addressable(int pitch_bytes) const
     return true;
 }
 
+// May the scan's pair kernel stage this logo's [1 2 1] sums unscaled -- {4 s, 4 bg} in the tile planes, the taps scaled by 0.25 here on
+// the host (eval_tile_stage.h Quad)?  The records stay the same bits as long as scaling by four commutes with every rounding on the way,
+// i.e. as long as no intermediate value of the UNSCALED evaluation is rounded in the denormal range and the scaled one does not overflow:
+//   * only a deinterlaced logo has the 0.25 (a field logo's rows are the samples themselves);
+//   * |a| + |b| < 8192 (pair_eligible's limit, NaN fails): |4 bg| <= 4 * 8192 * 65535 < 2^32, far from overflow, and the bin select
+//     clamps the mean in front of its conversion to an integer;
+//   * a nonzero a or b is at least 2^-64 in magnitude: s is 0 or >= 1/4, so a * s and b * maxv are 0 or >= 2^-66 -- normal -- and
+//     multiples of 2^-89; so are bg (sums and differences of floats are exact wherever their result is denormal, and scale exactly
+//     everywhere else), the window sums and the mean's dividend x: x is 0 or >= 2^-89, and div25's x * 0.04, its exact remainder and
+//     its correction all stay normal;
+//   * a nonzero tap, and the taps' nonzero sum, is at least 2^-124 in magnitude: a quarter of it is a normal number, k / 4 is exact.
+//     The products (k / 4) * (4 (w - M)) are then the same real numbers as k * (w - M) and round alike whatever their size.
+// tests/cpp/stage4_identities_test.cpp replays these identities over the operands this rule admits.
+// (the limits themselves: exact_math.h stage4_coef_ok / stage4_tap_ok)
+bool EvalEngine::stage4_eligible(const EvalLogoSpec& S)
+{
+    if (!S.deint) return false;
+    const float* a = S.planes.A(0);
+    const float* b = S.planes.B(0);
+    const size_t npx = (size_t)S.planes.w * S.planes.h;
+    for (size_t p = 0; p < npx; ++p)
+        if (!stage4_coef_ok(a[p], b[p])) return false;
+    const MaskTables& T = S.tables;
+    for (int m = 0; m < T.count; ++m) {
+        const float* k = &T.kernels[(size_t)m * 25];
+        float ksum = 0.0f;                                    // (the sum as ensure_tiles forms it)
+        for (int t = 0; t < 25; ++t) {
+            ksum += k[t];
+            if (!stage4_tap_ok(k[t])) return false;           // (a NaN tap: not eligible either)
+        }
+        if (!stage4_tap_ok(ksum)) return false;
+    }
+    return true;
+}
+
 // tile plans of the pair kernel (eval_tiles.hpp): per logo the bands, the eight wave tiles of every band, and per slot
 // (= lane of a tile) the mask pixel's window offset, taps and scales
 void EvalEngine::ensure_tiles()
@@ -272,6 +310,13 @@ void EvalEngine::ensure_tiles()
     ctx_->bind();
     const int nl = (int)specs_.size();
     std::vector<TileLogoDev> hl(nl);
+    // The scan's pair kernel (fades {0, 1}) comes in two forms: the [1 2 1] sums staged unscaled on taps that carry the 0.25, or scaled
+    // sample by sample (ldexp) on plain taps.  Every logo is checked, and the engine takes the first form when all of them pass: one
+    // kernel per launch -- a logo that fails has denormal coefficients or taps, and a second launch beside a per-workgroup check is more
+    // than it is worth.  (The linear analysis kernel keeps plain taps: the same change did not measure faster there,
+    // profiles/stage_unscaled_notes.md.)
+    tiles_stage4_ = fades_.size() == 2;
+    for (const EvalLogoSpec& S : specs_) tiles_stage4_ = tiles_stage4_ && stage4_eligible(S);
     d_tkp_.resize(nl); d_tsc_.resize(nl); d_tpq_.resize(nl); d_tinfo_.resize(nl); d_tpos_.resize(nl); d_tlin_.resize(nl); d_tiles_.resize(nl); d_tbands_.resize(nl); d_tlist_.resize(nl);
     for (int i = 0; i < nl; ++i) {
         const EvalLogoSpec& S = specs_[i];
@@ -283,6 +328,7 @@ void EvalEngine::ensure_tiles()
         //  limit no table is built and both tile kernels are off for this engine: pair_eligible, run_linear)
         if (!tile_slots_ok(P.nslots())) { tile_slots_ok_ = false; continue; }
         const size_t ns = (size_t)P.nslots();
+        const float kscale = tiles_stage4_ ? 0.25f : 1.0f;      // DeintY's 0.25 lives in the taps (k / 4 is exact: stage4_eligible)
         std::vector<float2> kp(13 * ns, float2{0.0f, 0.0f}), sc((size_t)kNumBins * ns, float2{0.0f, 0.0f}), pq(ns, float2{0.0f, 0.0f});
         std::vector<uint32_t> spos(ns, 0u);
         for (size_t s = 0; s < ns; ++s) {
@@ -293,7 +339,7 @@ void EvalEngine::ensure_tiles()
             const float* k = &T.kernels[(size_t)m * 25];
             float ksum = 0.0f;
             for (int t = 0; t < 25; ++t) ksum += k[t];
-            for (int j = 0; j < 13; ++j) kp[(size_t)j * ns + s] = float2{k[2 * j], 2 * j + 1 < 25 ? k[2 * j + 1] : ksum};    // [12].y = sum of the taps (linear kernel)
+            for (int j = 0; j < 13; ++j) kp[(size_t)j * ns + s] = float2{kscale * k[2 * j], kscale * (2 * j + 1 < 25 ? k[2 * j + 1] : ksum)};    // [12].y = sum of the taps (linear kernel: kscale is 1)
             for (int c = 0; c < kNumBins; ++c)
                 sc[(size_t)c * ns + s] = float2{T.scales[((size_t)m * 32 + c) * 2], T.scales[((size_t)m * 32 + c) * 2 + 1]};
         }

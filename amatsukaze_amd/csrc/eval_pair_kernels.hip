@@ -61,8 +61,14 @@ __device__ __forceinline__ f2 window_corr_exact(const f2 (&Kp)[13], const f2 (&W
     return ((p[0] + p[4]) + p[2]) + (p[1] + p[3]);
 }
 
-// bin of CorrelationScore (LogoScan.hpp:304) for a mean below 2^31 (guaranteed by pair_eligible: |bg| < 2^30)
-__device__ __forceinline__ unsigned score_bin_bounded(float mean) { return (unsigned)((int)__builtin_amdgcn_fmed3f(mean, 0.0f, 255.0f) >> 3); }
+// bin of CorrelationScore (LogoScan.hpp:304), (int)clamp(mean, 0, 255) >> 3; the clamp in front of the conversion bounds what is
+// converted (pair_eligible keeps |bg| below 2^30 so that it is finite at all).  STAGE4: `mean` is four times the window mean
+// (eval_tile_stage.h Quad) -- floor(4 m) >> 5 == floor(m) >> 3 for m in [0, 255] (both are floor(m / 8)), and anything above
+// clamps to bin 31 either way (1020 >> 5 == 255 >> 3 == 31)
+template <bool STAGE4> __device__ __forceinline__ unsigned score_bin_bounded(float mean)
+{
+    return STAGE4 ? (unsigned)((int)__builtin_amdgcn_fmed3f(mean, 0.0f, 1020.0f) >> 5) : (unsigned)((int)__builtin_amdgcn_fmed3f(mean, 0.0f, 255.0f) >> 3);
+}
 
 struct PairLaunch {
     const EvalLogoDev* logos;
@@ -82,9 +88,11 @@ struct PairLaunch {
 #else
 #define AMT_PAIR_OCC_ATTR
 #endif
-template <typename pix_t>
-__global__ __launch_bounds__(kPairThreads) AMT_PAIR_OCC_ATTR
-void logo_eval_pair_kernel(const PairLaunch A)
+// STAGE4: the logos' tables carry the 0.25 of DeintY (taps scaled on the host: EvalEngine::ensure_tiles) and the tile planes hold
+// {4 s, 4 bg} -- no v_ldexp_f32 per staged sample; records are the same bits (eval_tile_stage.h Quad).  An engine with a logo whose
+// tables cannot be scaled runs the other instance (logo_eval_pair_ldexp_kernel) on unscaled tables.
+template <typename pix_t, bool STAGE4>
+__device__ __forceinline__ void logo_eval_pair_body(const PairLaunch& A)
 {
     extern __shared__ float lds[];
     f2* const planes = reinterpret_cast<f2*>(lds);                       // [kTileWaves][kTileCap] {s, bg}: a wave's own tile
@@ -131,7 +139,7 @@ void logo_eval_pair_kernel(const PairLaunch A)
     const const_tile_ptr tiles = (const_tile_ptr)(Xp->tiles + wave);
     f2* const myplane = planes + wave * kTileCap;
     const unsigned plane_base = lds_address(myplane);
-    TileStager<pix_t> st;
+    TileStager<pix_t, STAGE4> st;
     st.init(Lp, A.pitch, A.maxv, myplane);
     TilePixel px;
 
@@ -183,8 +191,8 @@ void logo_eval_pair_kernel(const PairLaunch A)
         // ---- 4. the previous iteration's terms -> the band's score rows, at the pixel's raster position; then this iteration's two
         //      scale gathers go straight into the registers the terms were read from (a copy would wait for them here) ----
         flush_terms();
-        psc0 = gld<f2>(gSc, __umul24(score_bin_bounded(M.x), nslots8) + px.slot8);
-        psc1 = gld<f2>(gSc, __umul24(score_bin_bounded(M.y), nslots8) + px.slot8);
+        psc0 = gld<f2>(gSc, __umul24(score_bin_bounded<STAGE4>(M.x), nslots8) + px.slot8);
+        psc1 = gld<f2>(gSc, __umul24(score_bin_bounded<STAGE4>(M.y), nslots8) + px.slot8);
         pR = R; pact = px.act;
         prow = (b & 1) * 2 * G + g * 2;
         if (band_end) {
@@ -205,9 +213,17 @@ void logo_eval_pair_kernel(const PairLaunch A)
     }
 }
 
+template <typename pix_t>
+__global__ __launch_bounds__(kPairThreads) AMT_PAIR_OCC_ATTR
+void logo_eval_pair_kernel(const PairLaunch A) { logo_eval_pair_body<pix_t, true>(A); }
+template <typename pix_t>
+__global__ __launch_bounds__(kPairThreads) AMT_PAIR_OCC_ATTR
+void logo_eval_pair_ldexp_kernel(const PairLaunch A) { logo_eval_pair_body<pix_t, false>(A); }
+
+// ldexp_form: the engine's tables are NOT scaled (EvalEngine::ensure_tiles)
 hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
                                  const void* dY, const int* dframe_map, long long frame_stride_elems, int pitch,
-                                 int nframes, int G, float* dout, int out_frame_stride, int take_abs)
+                                 int nframes, int G, float* dout, int out_frame_stride, int take_abs, int ldexp_form)
 {
     if (nframes <= 0 || nlogos <= 0) return hipSuccess;
     PairLaunch A;
@@ -218,8 +234,13 @@ hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dl
     const size_t lds = ((size_t)kTileWaves * kTileCap * 2 + (size_t)2 * 2 * G * kPairRowPitch) * sizeof(float);
     if (G < 1 || 2 * G > 64 || lds > 160 * 1024) return hipErrorInvalidValue;
     dim3 grid((unsigned)wg_grid_shared_rows(A.ngroups, nlogos));
-    if (bits <= 8) hipLaunchKernelGGL(logo_eval_pair_kernel<uint8_t>, grid, dim3(kPairThreads), lds, st, A);
-    else hipLaunchKernelGGL(logo_eval_pair_kernel<uint16_t>, grid, dim3(kPairThreads), lds, st, A);
+    if (ldexp_form) {
+        if (bits <= 8) hipLaunchKernelGGL(logo_eval_pair_ldexp_kernel<uint8_t>, grid, dim3(kPairThreads), lds, st, A);
+        else hipLaunchKernelGGL(logo_eval_pair_ldexp_kernel<uint16_t>, grid, dim3(kPairThreads), lds, st, A);
+    } else {
+        if (bits <= 8) hipLaunchKernelGGL(logo_eval_pair_kernel<uint8_t>, grid, dim3(kPairThreads), lds, st, A);
+        else hipLaunchKernelGGL(logo_eval_pair_kernel<uint16_t>, grid, dim3(kPairThreads), lds, st, A);
+    }
     return hipGetLastError();
 }
 

@@ -179,12 +179,30 @@ __device__ __forceinline__ void window_eval_streamed(const unsigned (&wrow)[5], 
 // (r0 + 2 r1 + r2 + 2) / 4.0f (LogoScan.hpp:763-780) -- an integer sum below 2^24 times 0.25, the reference's value bit for bit.
 // bias = the blend's + 2; a row that is NOT blended (the logo's first / last row under DeintY, every row of a field logo under
 // CopyY, :782-790) loads r0 = r2 = r1 and has bias 0: 4 r1 / 4 = r1 -- one code path, no branch.
+//
+// QUARTER = false (the scan's pair kernel on tables that carry the factor) stages the integer sum n = r0 + 2 r1 + r2 + bias ITSELF, s' = 4 s
+// (exact: n <= 4 * 65535 + 2 < 2^24), and saves the v_ldexp_f32 per sample.  Everything downstream then runs on four times the
+// reference's values, and scaling by a power of two commutes with every rounding on the way as long as nothing leaves the normal range
+// (the host checks every logo: EvalEngine::stage4_eligible):
+//   bg' = a * s' + b * (4 maxv) = 4 bg          fl(a * 4s) = 4 fl(a * s), fl(b * 4maxv) = 4 fl(b * maxv), fl(4p + 4q) = 4 fl(p + q)
+//   M'  = 4 M                                   the column sums, hsum5 and div25's three operations scale alike
+//   (k / 4) * (w' - M') = k * (w - M)           the taps come scaled by 0.25 from the host (k / 4 exact, 4 (w - M) exact): the product is
+//                                               the same real number, so every product, every sum and the correlation are the bits they were
+// so only the bin select sees the factor: it reads M' with the edges scaled by four (score_bin_bounded).
+// 4 x for a wave-uniform, normal, positive v well below 2^126 (the sample maximum): two added to its exponent -- a scalar integer add.
+// (The hardware has no scalar float multiply: written 4.0f * v the product is a vector instruction and lives in a vector register --
+// four registers more in the pair kernel.)
+__device__ __forceinline__ float times4_uniform(float v) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) + 0x01000000u); }
+template <bool QUARTER> __device__ __forceinline__ float blend_value(unsigned n)
+{
+    return QUARTER ? __builtin_amdgcn_ldexpf((float)n, -2) : (float)n;
+}
 template <typename pix_t> struct Quad;
 template <> struct Quad<uint8_t> {
     unsigned v;
     __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t r, int voff) { v = __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0); }
     // two samples per instruction: bytes 0, 2 and bytes 1, 3 spread over 16-bit lanes (sums <= 1022)
-    static __device__ __forceinline__ void blend(const Quad& r0, const Quad& r1, const Quad& r2, unsigned bias, float (&s)[4])
+    template <bool QUARTER = true> static __device__ __forceinline__ void blend(const Quad& r0, const Quad& r1, const Quad& r2, unsigned bias, float (&s)[4])
     {
         const unsigned e0 = __builtin_amdgcn_perm(r0.v, r0.v, 0x0C020C00u), o0 = __builtin_amdgcn_perm(r0.v, r0.v, 0x0C030C01u);
         const unsigned e1 = __builtin_amdgcn_perm(r1.v, r1.v, 0x0C020C00u), o1 = __builtin_amdgcn_perm(r1.v, r1.v, 0x0C030C01u);
@@ -198,10 +216,10 @@ template <> struct Quad<uint8_t> {
         const unsigned so = to + o2 + bias;
         // (ldexp, not a multiply by 0.25: the vectoriser would pair the multiplies and the pairs {s0,s1}, {s2,s3} then need four
         //  moves into the {s, bg} order of the LDS store)
-        s[0] = __builtin_amdgcn_ldexpf((float)(se & 0xFFFFu), -2);
-        s[1] = __builtin_amdgcn_ldexpf((float)(so & 0xFFFFu), -2);
-        s[2] = __builtin_amdgcn_ldexpf((float)(se >> 16), -2);
-        s[3] = __builtin_amdgcn_ldexpf((float)(so >> 16), -2);
+        s[0] = blend_value<QUARTER>(se & 0xFFFFu);
+        s[1] = blend_value<QUARTER>(so & 0xFFFFu);
+        s[2] = blend_value<QUARTER>(se >> 16);
+        s[3] = blend_value<QUARTER>(so >> 16);
     }
     static constexpr unsigned kBias = 0x00020002u;
     // a row that is never blended (CopyY, LogoScan.hpp:782-790): the four samples as they are
@@ -213,13 +231,13 @@ template <> struct Quad<uint8_t> {
 template <> struct Quad<uint16_t> {
     u2 v;
     __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t r, int voff) { v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, 0, 0); }
-    static __device__ __forceinline__ void blend(const Quad& r0, const Quad& r1, const Quad& r2, unsigned bias, float (&s)[4])
+    template <bool QUARTER = true> static __device__ __forceinline__ void blend(const Quad& r0, const Quad& r1, const Quad& r2, unsigned bias, float (&s)[4])
     {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const unsigned a = (r0.v[k >> 1] >> (16 * (k & 1))) & 0xFFFFu, b = (r1.v[k >> 1] >> (16 * (k & 1))) & 0xFFFFu,
                            c = (r2.v[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
-            s[k] = __builtin_amdgcn_ldexpf((float)(((b << 1) + a) + (c + bias)), -2);
+            s[k] = blend_value<QUARTER>(((b << 1) + a) + (c + bias));
         }
     }
     static constexpr unsigned kBias = 2u;
@@ -252,7 +270,8 @@ __device__ __forceinline__ void fetch_tile(TileDesc& D, const_tile_ptr t)
 // would be gone.  Only the conversion of the units beyond the first 64 is skipped for small tiles.
 // Everything a unit needs is kept in registers: its three row offsets, its bias and its logo coefficients (a, b * maxv).  Every unit
 // loads three rows and goes through the [1 2 1] sum; a row that is not blended loads the same row three times with bias 0 (Quad).
-template <typename pix_t> struct TileStager {
+// STAGE4: the plane holds {4 s, 4 bg} (Quad, QUARTER = false): the sums unscaled, and b * (4 maxv) where b * maxv stood.
+template <typename pix_t, bool STAGE4> struct TileStager {
     static constexpr int ES = (int)sizeof(pix_t);
     // (wave-uniform)
     int w, h, deint, srow0, srow_step, scol0, pitchB;
@@ -272,7 +291,7 @@ template <typename pix_t> struct TileStager {
         w = Lp->w; h = Lp->h; deint = Lp->deint;
         srow0 = Lp->imgy + Lp->row0; srow_step = Lp->row_step; scol0 = Lp->imgx;
         gA = (gptr_t)Lp->a; gB = (gptr_t)Lp->b;
-        pitchB = pitch * ES; maxv = maxv_; plane = plane_;
+        pitchB = pitch * ES; maxv = STAGE4 ? times4_uniform(maxv_) : maxv_; plane = plane_;
         second_pass = false;
     }
     __device__ __forceinline__ void setup_units(const TileDesc& T, int lane)
@@ -316,7 +335,7 @@ template <typename pix_t> struct TileStager {
     __device__ __forceinline__ void convert_unit(int k)
     {
         float sv[4];
-        Quad<pix_t>::blend(raw[k][0], raw[k][1], raw[k][2], ubias[k], sv);
+        Quad<pix_t>::template blend<!STAGE4>(raw[k][0], raw[k][1], raw[k][2], ubias[k], sv);
         f2* dst = plane + ulds[k];
         reinterpret_cast<f4*>(dst)[0] = f4{sv[0], ua[k][0] * sv[0] + ubmv[k][0], sv[1], ua[k][1] * sv[1] + ubmv[k][1]};
         reinterpret_cast<f4*>(dst)[1] = f4{sv[2], ua[k][2] * sv[2] + ubmv[k][2], sv[3], ua[k][3] * sv[3] + ubmv[k][3]};

@@ -86,6 +86,19 @@ AMT_HD float score_term(float corr, float scale, float scale2)
     return nm * scale2;
 }
 
+// What the scan kernel's unscaled staging (eval_tile_stage.h Quad: {4 s, 4 bg} in the tile planes, taps scaled by 0.25 on the host)
+// asks of a deinterlaced logo -- EvalEngine::stage4_eligible has the argument, tests/cpp/stage4_identities_test.cpp replays it:
+// a pixel's coefficients: |a| + |b| < 8192 (NaN fails) and a nonzero one at least 2^-64 in magnitude; a tap, and the taps' sum: zero or
+// at least 2^-124 in magnitude (its quarter is a normal number).
+constexpr float kStage4MinCoef = 5.421010862427522e-20f;        // 2^-64
+constexpr float kStage4MinTap = 4.70197740328915e-38f;          // 2^-124
+AMT_HD bool stage4_coef_ok(float a, float b)
+{
+    const float fa = a < 0 ? -a : a, fb = b < 0 ? -b : b;
+    return fa + fb < 8192.0f && (fa == 0.0f || fa >= kStage4MinCoef) && (fb == 0.0f || fb >= kStage4MinCoef);
+}
+AMT_HD bool stage4_tap_ok(float k) { return k == 0.0f || k >= kStage4MinTap || -k >= kStage4MinTap; }
+
 // unblend one pixel (LogoScan.hpp:244-249 / :1253-1257)
 AMT_HD float unblend_bg(float a, float b, float maxv, float s) { return a * s + b * maxv; }
 AMT_HD float fade_mix(float fade, float bg, float s) { return fade * bg + (1 - fade) * s; }

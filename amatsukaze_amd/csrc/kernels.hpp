@@ -146,7 +146,8 @@ hipError_t launch_audio_levels(hipStream_t st, const int16_t* dpcm, long long pc
 // ---- eval_fused_kernels.hip, eval_pair_kernels.hip, eval_linear_kernels.hip ----
 // tile plan of one evaluation logo resident in HBM (eval_tiles.hpp; eval_pair_kernels.hip).  slot = (band * kTileWaves + wave) * 64 + lane
 struct TileLogoDev {
-    const float2* kp;            // [13][nslots]  taps of the slot's mask pixel as pairs {k[2j], k[2j+1]} (k[25] = 0), pair-major
+    const float2* kp;            // [13][nslots]  taps of the slot's mask pixel as pairs {k[2j], k[2j+1]} (k[25] = 0), pair-major; times 0.25
+                                 //               when the scan's pair kernel stages unscaled (EvalEngine::ensure_tiles)
     const float2* sc;            // [32][nslots]  bin-major {scale, scale2} of the slot's mask pixel (the exact scan kernel)
     const float2* pq;            // [nslots]      {P, Q}: the pixel's response on flat level c is |P + Q c| (the linear analysis kernel: no gathers)
     const uint32_t* sinfo;       // [nslots]      tile_slot_info
@@ -177,7 +178,7 @@ hipError_t launch_logo_eval_linear(hipStream_t st, int bits, const EvalLogoDev* 
 // eval_pair_kernels.hip: fades {0, 1} of every logo, bit-exact
 hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
                                  const void* dY, const int* dframe_map, long long frame_stride_elems, int pitch,
-                                 int nframes, int G, float* dout, int out_frame_stride, int take_abs);
+                                 int nframes, int G, float* dout, int out_frame_stride, int take_abs, int ldexp_form);
 // Sentinel monitor of AMTGPU_ANALYZE_LINEAR_MONITORED: persistent per-analyzer device state.  max_abs_bits: the largest |linear - exact| over
 // every compared score as float bits (non-negative floats order like unsigned ints; NaN counts as +inf); tripped: a comparison failed (sticky
 // until re-armed); frames_checked: sentinel frames compared; batches_tripped: batches in which a comparison failed
