@@ -1061,7 +1061,10 @@ def kfm_render(ctx: Context, src: "DeviceSurfaces | DeviceClip", plan, dst: "Dev
     when msb: interpolated rows are then computed on samples and stored with zero low bits, copied rows keep theirs.
     deint="adaptive" fills the missing rows of the 60i frames with the edge-directed, motion-adaptive rule instead (amtgpu_kfm_render_deint;
     DESIGN.md section 6d): still areas weave, moving areas interpolate along the edge.  It has no threshold (thresh must stay -1), reads
-    frames n - 1 and n + 1 of every bob entry wherever the clip has them, and takes planar LSB clips only.  Synchronises"""
+    frames n - 1 and n + 1 of every bob entry wherever the clip has them, and takes every pair in kind: planar LSB clips go through
+    amtgpu_kfm_render_deint as before, interleaved or MSB-aligned surfaces (NV12, P010 / P012, planar MSB) through
+    amtgpu_kfm_render_deint_surfaces, where U and V are planes of their own, the rule runs on samples (container >> (16 - bits) when msb),
+    interpolated containers are stored with zero low bits and copied rows keep theirs.  Synchronises"""
     if deint not in ("line", "adaptive"):
         raise AmtError(f"kfm_render: deint is 'line' or 'adaptive', not {deint!r}")
     pl = np.ascontiguousarray(plan, RENDER_FRAME).reshape(-1)
@@ -1072,8 +1075,9 @@ def kfm_render(ctx: Context, src: "DeviceSurfaces | DeviceClip", plan, dst: "Dev
         raise AmtError(f"kfm_render: the plan has {len(pl)} output frames, dst holds {dst.num_frames}")
     s, d = _surfaces_ref(src), _surfaces_ref(dst)
     if deint == "adaptive":
-        ctx.check(ctx.lib.amtgpu_kfm_render_deint(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), _p(pl), len(pl),
-                                                  DEINT_ADAPTIVE, int(thresh), C.byref(d)), "kfm_render")
+        call = ctx.lib.amtgpu_kfm_render_deint_surfaces if s.interleaved or s.msb_aligned else ctx.lib.amtgpu_kfm_render_deint
+        ctx.check(call(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), _p(pl), len(pl), DEINT_ADAPTIVE, int(thresh),
+                       C.byref(d)), "kfm_render")
         return
     ctx.check(ctx.lib.amtgpu_kfm_render(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), _p(pl), len(pl),
                                         int(thresh), C.byref(d)), "kfm_render")

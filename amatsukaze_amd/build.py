@@ -37,6 +37,7 @@ SOURCES = [
     "render_kernels.hip",
     "render_surface_kernels.hip",
     "render_adaptive_kernels.hip",
+    "render_adaptive_surface_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

@@ -38,9 +38,10 @@ Span plane_span(const void* p, long long stride, int pitch_bytes, int row_bytes,
     return Span{lo, lo + (uintptr_t)(n - 1) * (uintptr_t)stride + (uintptr_t)(rows - 1) * (uintptr_t)pitch_bytes + (uintptr_t)row_bytes};
 }
 
-// both entry points: deint LINE is amtgpu_kfm_render, ADAPTIVE the edge-directed, motion-adaptive rule on planes
+// all entry points: deint LINE is amtgpu_kfm_render, ADAPTIVE the edge-directed, motion-adaptive rule -- on planes, and with
+// adaptive_surfaces (amtgpu_kfm_render_deint_surfaces) on every pair in kind
 void render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height, const AmtGpuRenderFrame* plan, int nout,
-            int deint, int thresh, const AmtGpuSurfaces* dst)
+            int deint, int thresh, const AmtGpuSurfaces* dst, bool adaptive_surfaces = false)
 {
     if (deint != AMTGPU_DEINT_LINE && deint != AMTGPU_DEINT_ADAPTIVE) refuse("deint " + std::to_string(deint) + " is neither AMTGPU_DEINT_LINE nor AMTGPU_DEINT_ADAPTIVE");
     const bool adaptive = deint == AMTGPU_DEINT_ADAPTIVE;
@@ -53,7 +54,7 @@ void render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc
     if (src->bits != dst->bits) refuse("source and destination differ in bits");
     if (s.interleaved != d.interleaved || s.shift != d.shift)
         refuse("source and destination are not in kind (equal bits, interleaved and MSB shift): the renderer converts no layouts");
-    if (adaptive && (s.interleaved || s.shift)) refuse("the adaptive rule takes planes only (planar, LSB-aligned): interleaved and MSB-aligned surfaces are refused");
+    if (adaptive && !adaptive_surfaces && (s.interleaved || s.shift)) refuse("the adaptive rule takes planes only (planar, LSB-aligned): interleaved and MSB-aligned surfaces are refused");
     if (src_first < 0 || nsrc <= 0 || (long long)src_first + nsrc > clip_frames) refuse("the source batch does not lie inside the clip");
     const int es = s.es, wUV = width >> 1, hUV = height >> 1;
     const int maxv = s.shift ? (1 << src->bits) - 1 : es == 1 ? 255 : 65535;        // of a sample: MSB-aligned ones are compared shifted
@@ -117,8 +118,10 @@ void render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc
     if (adaptive) {
         DevBuf<RenderAdaptiveEntry> dplan;
         dplan.upload(aentries, c->stream);
-        const int sp_ = c->prof_begin("kfm_render_adaptive_kernel");
-        AMT_HIP(launch_kfm_render_adaptive(c->stream, a, dplan.get(), nout));
+        const bool planes = !s.interleaved && !s.shift;                              // planar LSB: the planar kernel, as before
+        const int sp_ = c->prof_begin(planes ? "kfm_render_adaptive_kernel" : "kfm_render_adaptive_surfaces_kernel");
+        AMT_HIP(planes ? launch_kfm_render_adaptive(c->stream, a, dplan.get(), nout)
+                       : launch_kfm_render_adaptive_surfaces(c->stream, a, s.interleaved, s.shift, dplan.get(), nout));
         c->prof_end(sp_);
         AMT_HIP(hipStreamSynchronize(c->stream));      // the plan's device copy dies with this call
         return;
@@ -160,6 +163,13 @@ int amtgpu_kfm_render_deint(AmtGpuContext* c, const AmtGpuSurfaces* src, int src
 {
     if (!c) return 0;
     return guard(c, [&] { render(c, src, src_first, nsrc, clip_frames, width, height, plan, nout, deint, thresh, dst); });
+}
+
+int amtgpu_kfm_render_deint_surfaces(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
+                                     const AmtGpuRenderFrame* plan, int nout, int deint, int thresh, const AmtGpuSurfaces* dst)
+{
+    if (!c) return 0;
+    return guard(c, [&] { render(c, src, src_first, nsrc, clip_frames, width, height, plan, nout, deint, thresh, dst, true); });
 }
 
 } // extern "C"

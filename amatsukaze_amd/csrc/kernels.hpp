@@ -115,6 +115,11 @@ hipError_t launch_kfm_render_surfaces(hipStream_t st, const RenderArgs& a, int i
 // clip has none (and in WEAVE entries), so that nothing else is ever addressed.  a.thresh is not read
 struct RenderAdaptiveEntry { int kind, top, bottom, prev, next; };
 hipError_t launch_kfm_render_adaptive(hipStream_t st, const RenderArgs& a, const RenderAdaptiveEntry* dplan, int nout);
+// render_adaptive_surface_kernels.hip: the adaptive rule on decoder surfaces, source and destination in kind; interleaved and shift as for
+// launch_kfm_render_surfaces.  U and V of an interleaved plane are planes of their own (neighbours two containers away, the column clamp
+// per component); interpolated samples are container >> shift, stored << shift.  Planar LSB planes (neither) are refused: they are
+// launch_kfm_render_adaptive's
+hipError_t launch_kfm_render_adaptive_surfaces(hipStream_t st, const RenderArgs& a, int interleaved, int shift, const RenderAdaptiveEntry* dplan, int nout);
 
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,

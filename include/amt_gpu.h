@@ -696,13 +696,29 @@ int  amtgpu_kfm_render(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_fi
  * judged: the rule is argued from its construction and a diagonal known answer, not from measured picture quality.
  * ADAPTIVE takes every refusal of amtgpu_kfm_render, and refuses as well: thresh != -1; a deint that is neither constant; a BOB entry
  * whose frame n - 1 (n >= 1) or n + 1 (n + 1 < clip_frames) is outside the batch -- both bobs read both neighbours; and any pair that is
- * not planar and LSB-aligned: NV12 / P010 / P012 and planar MSB surfaces under the adaptive rule are not built yet.
+ * not planar and LSB-aligned: this entry point takes planes only under the adaptive rule, and keeps that contract; NV12 / P010 / P012
+ * and planar MSB surfaces under the adaptive rule are amtgpu_kfm_render_deint_surfaces below.
  * The bytes depend on the clip and the plan alone: batches with one frame of halo on either side give the bytes of one call.
  * Synchronises, and the plan's device copy lives for the one launch, as amtgpu_kfm_render */
 #define AMTGPU_DEINT_LINE     0   /* the rule of amtgpu_kfm_render: line average, temporal mean within thresh */
 #define AMTGPU_DEINT_ADAPTIVE 1   /* edge-directed, motion-adaptive; thresh must be -1 */
 int  amtgpu_kfm_render_deint(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
                              const AmtGpuRenderFrame* plan, int nout, int deint, int thresh, const AmtGpuSurfaces* dst);
+/* amtgpu_kfm_render_deint argument for argument, and the same function behind it, with AMTGPU_DEINT_ADAPTIVE on every pair of surfaces IN
+ * KIND (equal bits, interleaved and shift s = msb_aligned ? 16 - bits : 0): NV12, P010 / P012 / P016, interleaved LSB, planar MSB.  A
+ * planar LSB pair runs the kernel of amtgpu_kfm_render_deint and gives its bytes; AMTGPU_DEINT_LINE is amtgpu_kfm_render.
+ * The result is defined by the planar rule above on samples: de-interleave UV into U and V, each a plane of its own of width / 2 columns
+ * with its own column clamp X(k); take samples container >> s; apply the adaptive rule per plane, unchanged (frames n - 1 / n / n + 1,
+ * the same row clamps); store an interpolated container as output << s, its low bits zero; re-interleave.  Every COPIED row (all rows of
+ * a WEAVE, the kept rows of a BOB) is moved as stored, low bits included, exactly as amtgpu_kfm_render moves it.  An interleaved LSB
+ * 16-bit pair and a P016 pair (msb_aligned with bits 16: s = 0) use the containers as stored.  So dst >> s, de-interleaved, is the planar
+ * adaptive render of src >> s.  (The rule looks at columns x - 3 .. x + 3, so an interleaved row is NOT walked as one plane of `width`
+ * containers as under the line rule: a U container's neighbours are two containers away.)
+ * Every refusal of amtgpu_kfm_render_deint is kept, with the same messages, but "planes only": thresh must be -1, a BOB entry needs
+ * n - 1 and n + 1 in the batch wherever the clip has them, mixed pairs are refused.  The bytes depend on the clip and the plan alone,
+ * with one frame of halo on either side of a batch.  Synchronises */
+int  amtgpu_kfm_render_deint_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
+                                      const AmtGpuRenderFrame* plan, int nout, int deint, int thresh, const AmtGpuSurfaces* dst);
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
