@@ -41,7 +41,7 @@ def test_many_frames_per_workgroup(gpu):
     """Batches large enough that a workgroup owns several frames (G = min(8, frames * logos / 2048) = 4 here, the last group is
     short): the taps of a band are loaded once and re-used across the group's frames, the linear kernel keeps the band's logo
     coefficients in LDS across them and the scan stages two frames per iteration.  Exact analysis and scan: bytes; linear analysis
-    (unguarded): within 1e-4."""
+    (unguarded): within 8 times the reference's own rounding."""
     import ctypes as C
     import torch
     import amt_synth as S
@@ -66,7 +66,16 @@ def test_many_frames_per_workgroup(gpu):
     assert out.cpu().numpy().tobytes() == want.tobytes()
     AMTAnalyzeLogo(ctx, logo, 0.35, mode="linear_unguarded").analyze_device(Yd, 8, out)
     torch.cuda.synchronize()
-    assert np.abs(out.cpu().numpy() - want).max() <= 1e-4
+    # within K times the reference's own rounding on this clip (tests/linear_terms_ref.py; about 1e-5), taken from 64 of its frames
+    import linear_terms_ref as R
+    sample = np.linspace(0, N - 1, 64).astype(int)
+    ref = R.FramesRef("64 frames of the clip", data, (LW, LH, X, Y0, H), 0.35, 8, np.ascontiguousarray(Y[sample]), W=W, mutants=False)
+    assert ref.want.tobytes() == want[sample].tobytes() and 0 < ref.tol < 5e-5, ref.tol
+    lin = out.cpu().numpy()
+    import json
+    print("linear_per_pixel " + json.dumps({"case": "test_many_frames_per_workgroup (%d frames, own and tol from 64 of them)" % N, "own": ref.own, "tol": ref.tol,
+                                            "max_error": float(np.abs(lin.astype(np.float64) - want).max())}))
+    assert np.abs(lin.astype(np.float64) - want).max() <= ref.tol
     guarded = AMTAnalyzeLogo(ctx, logo, 0.35, mode="linear")
     guarded.analyze_device(Yd, 8, out)
     assert guarded.last_refined() <= N // 20
