@@ -360,13 +360,20 @@ int amtgpu_logoframe_begin(AmtGpuLogoFrame* lf, int width, int height, int bits,
     });
 }
 
+// The luma batch of the plane entry points of LogoFrame and AMTAnalyzeLogo: plane_batch and its stride refusal, but a batch without frames is
+// never read and succeeds whatever its stride
+static FrameBatch eval_planes(int bits, const void* dY, int64_t frame_stride, int pitch, int nframes)
+{
+    return plane_batch(bits, dY, nullptr, nullptr, nframes > 0 ? frame_stride : 0, 0, pitch, 0);
+}
+
 int amtgpu_logoframe_scan_batch(AmtGpuLogoFrame* lf, const void* dY, int64_t frame_stride, int pitch, int first, int nframes)
 {
     return guard(lf->ctx, [&] {
         if (first < 0 || nframes < 0 || first + nframes > lf->numFrames) throw std::runtime_error("frame range outside the clip");
         if (!lf->engine || nframes == 0) return;
         const int nl = (int)lf->logos.size();
-        lf->engine->run(dY, frame_stride, pitch, lf->bits, nframes, lf->dResults.get() + (size_t)first * nl * 2);
+        lf->engine->run(eval_planes(lf->bits, dY, frame_stride, pitch, nframes), lf->bits, nframes, lf->dResults.get() + (size_t)first * nl * 2);
         lf->hostValid = false;
         lf->selected = false;
     });
@@ -390,9 +397,9 @@ int amtgpu_logoframe_scan_surfaces(AmtGpuLogoFrame* lf, const AmtGpuSurfaces* ba
             col0 = std::min(col0, P.imgx); col1 = std::max(col1, P.imgx + P.w);
         }
         if (b.pitchY < col1) refuse("surface pitchY smaller than the rectangle's rows");
-        const LumaView v = surfaces_luma_view(lf->ctx, b, row0, row1, col0, col1, nframes, lf->dBand);
+        const FrameBatch luma = surfaces_luma_view(lf->ctx, b, row0, row1, col0, col1, nframes, lf->dBand);
         const int nl = (int)lf->logos.size();
-        lf->engine->run(v.Y, v.stride_bytes, v.pitch, lf->bits, nframes, lf->dResults.get() + (size_t)first * nl * 2);
+        lf->engine->run(luma, lf->bits, nframes, lf->dResults.get() + (size_t)first * nl * 2);
         lf->hostValid = false;
         lf->selected = false;
     });
@@ -610,17 +617,17 @@ static MonitorState monitor_read(AmtGpuAnalyze* an)
 // compared with the exact ones on the device, and a failed comparison -- in this batch or any earlier one -- re-evaluates the whole batch
 // exactly in a gated launch that reads its frame count from the device.  The host never waits: a downgrade it has seen (the device-written
 // flag) only saves the linear work of later batches.
-static void analyze_run(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride, int pitch, int bits, int nframes, float* dout)
+static void analyze_run(AmtGpuAnalyze* an, const FrameBatch& luma, int bits, int nframes, float* dout)
 {
     if (an->mode == AMTGPU_ANALYZE_EXACT) {
-        an->engine->run(dY, frame_stride, pitch, bits, nframes, dout);
+        an->engine->run(luma, bits, nframes, dout);
         return;
     }
     const bool monitored = an->mode == AMTGPU_ANALYZE_LINEAR_MONITORED;
     if (monitored) {
         if (!an->mon_host_downgraded && *(volatile int*)an->hMonFlag == an->mon_epoch) an->mon_host_downgraded = true;
         if (an->mon_host_downgraded) {
-            an->engine->run(dY, frame_stride, pitch, bits, nframes, dout);
+            an->engine->run(luma, bits, nframes, dout);
             an->last_all_exact = std::max(nframes, 0);
             return;
         }
@@ -639,13 +646,13 @@ static void analyze_run(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride,
         force = an->dForce.get();
         if (bits > 8 && bits < 16) {
             const int spf = an->ctx->prof_begin("rect_range_flag_kernel");
-            AMT_HIP(launch_rect_range_flag(an->ctx->stream, dY, frame_stride / 2, pitch, an->logo.imgx, an->logo.imgy, an->logo.w, an->logo.h, bits, nframes, force));
+            AMT_HIP(launch_rect_range_flag(an->ctx->stream, luma, an->logo.imgx, an->logo.imgy, an->logo.w, an->logo.h, bits, nframes, force));
             an->ctx->prof_end(spf);
         } else {
             AMT_HIP(hipMemsetAsync(force, 0, (size_t)nframes, an->ctx->stream));
         }
     }
-    an->engine->run_linear(dY, frame_stride, pitch, bits, nframes, dout, nullptr, force);
+    an->engine->run_linear(luma, bits, nframes, dout, nullptr, force);
     if (!guarded) return;
     float eps[3];
     for (int k = 0; k < 3; ++k) eps[k] = 2.0f * an->engine->linear_error_bound(k, bits);
@@ -665,14 +672,14 @@ static void analyze_run(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride,
     AMT_HIP(launch_analysis_mark(an->ctx->stream, dout, AMTGPU_ANALYZE_FLOATS, nframes, 3, AMTGPU_NUM_FADE, eps, an->dList.get(), an->dCount.get(), force,
                                  sent));
     an->ctx->prof_end(sp);
-    an->engine->run_listed(dY, frame_stride, pitch, bits, nframes, an->dList.get(), an->dCount.get(), dout);
+    an->engine->run_listed(luma, bits, nframes, an->dList.get(), an->dCount.get(), dout);
     if (!monitored) return;
     const int spc = an->ctx->prof_begin("analysis_sentinel_check_kernel");
     AMT_HIP(launch_analysis_sentinel_check(an->ctx->stream, dout, AMTGPU_ANALYZE_FLOATS, nframes, sent, an->mon_tol, an->dMon.get(), an->dMonFlag,
                                            an->mon_epoch));
     an->ctx->prof_end(spc);
     // every frame again, exactly, when the check failed (gate[0] = nframes); otherwise a launch whose workgroups find nothing to do
-    an->engine->run_listed(dY, frame_stride, pitch, bits, nframes, an->dIota.get(), an->dGate.get(), dout, an->engine->exact_group_frames(nframes), 0);
+    an->engine->run_listed(luma, bits, nframes, an->dIota.get(), an->dGate.get(), dout, an->engine->exact_group_frames(nframes), 0);
 }
 
 static AmtGpuAnalyze* analyze_new(AmtGpuContext* c, LogoPlanes logo, float maskratio)
@@ -724,7 +731,7 @@ int amtgpu_analyze_batch(AmtGpuAnalyze* an, const void* dY, int64_t frame_stride
 {
     return guard(an->ctx, [&] {
         if (bits < 8 || bits > 16) throw std::runtime_error("[AMTAnalyzeLogo] Unsupported pixel format");
-        analyze_run(an, dY, frame_stride, pitch, bits, nframes, dout);
+        analyze_run(an, eval_planes(bits, dY, frame_stride, pitch, nframes), bits, nframes, dout);
     });
 }
 
@@ -739,8 +746,7 @@ int amtgpu_analyze_surfaces(AmtGpuAnalyze* an, const AmtGpuSurfaces* batch, int 
         if (!dout) refuse("null output");
         const LogoPlanes& P = an->logo;
         if (b.pitchY < P.imgx + P.w) refuse("surface pitchY smaller than the rectangle's rows");
-        const LumaView v = surfaces_luma_view(an->ctx, b, P.imgy, P.imgy + P.h, P.imgx, P.imgx + P.w, nframes, an->dBand);
-        analyze_run(an, v.Y, v.stride_bytes, v.pitch, batch->bits, nframes, dout);
+        analyze_run(an, surfaces_luma_view(an->ctx, b, P.imgy, P.imgy + P.h, P.imgx, P.imgx + P.w, nframes, an->dBand), batch->bits, nframes, dout);
     });
 }
 
@@ -835,7 +841,7 @@ int amtgpu_analyze_batch_host(AmtGpuAnalyze* an, const void* dY, int64_t frame_s
         static const bool no_kernel = std::getenv("AMT_TRACE_NO_ANALYSIS_KERNEL") != nullptr;
         if (!no_kernel)
 #endif
-        { AMT_TRACE_SCOPE("analyze_batch_host.launches"); analyze_run(an, dY, frame_stride, pitch, bits, nframes, an->dTmp.get()); }
+        { AMT_TRACE_SCOPE("analyze_batch_host.launches"); analyze_run(an, eval_planes(bits, dY, frame_stride, pitch, nframes), bits, nframes, an->dTmp.get()); }
         an->ctx->bind();
 #ifdef AMT_TRACE_CALLS
         AmtGpuContext* c = an->ctx;

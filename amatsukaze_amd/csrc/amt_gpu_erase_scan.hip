@@ -532,7 +532,7 @@ std::unique_ptr<AmtGpuLogo> remake_rounds(AmtGpuContext* c, ShardGuard& sg, AmtG
             EvalEngine eng(c, std::move(specs), fades, true, 20, "logo_eval_fused_kernel.remake");
             std::vector<uint8_t> use(numFrames, 0);
             if (numFrames) {
-                eng.run(kept.planes.Y, kept.planes.strideY, kept.planes.pitchY, kept.bits, numFrames, dEval.get(), dMap.get());
+                eng.run(kept.planes, kept.bits, numFrames, dEval.get(), dMap.get());      // (reads the Y planes alone)
                 download_via_pinned(c, hEval.data(), dEval.get(), hEval.size() * sizeof(float));
             }
             for (int i = 0; i < numFrames; ++i) {

@@ -37,25 +37,20 @@ AmtGpuLogoFind* logofind_new(AmtGpuContext* c, int width, int height, int bits)
     return lf.release();
 }
 
-// shift > 0: the planes are MSB-aligned 16-bit containers, summed as container >> shift (= 16 - bits)
-void logofind_add(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes, int shift = 0)
+// b: the luma batch (b.shift > 0: MSB-aligned 16-bit containers, summed as container >> shift = 16 - bits)
+void logofind_add(AmtGpuLogoFind* lf, const FrameBatch& b, int nframes)
 {
     if (nframes < 0) throw std::runtime_error("[LogoFind] negative frame count");
     if (nframes == 0) return;
-    if (!dY) throw std::runtime_error("[LogoFind] null frame pointer");
-    if (pitch < lf->width || frame_stride < 0) throw std::runtime_error("[LogoFind] pitch below the width or negative frame stride");
+    if (!b.Y) throw std::runtime_error("[LogoFind] null frame pointer");
+    if (b.pitchY < lf->width || b.strideY < 0) throw std::runtime_error("[LogoFind] pitch below the width or negative frame stride");
     lf->ctx->bind();
     const long long cap = logofind_launch_cap(lf->bits);
     const int sp = lf->ctx->prof_begin("logofind_kernel");
     for (long long f0 = 0; f0 < nframes; f0 += cap) {
         const int n = (int)std::min<long long>(cap, nframes - f0);
-        const uint8_t* y0 = (const uint8_t*)dY + f0 * frame_stride;
-        if (shift)
-            AMT_HIP(launch_logofind_msb(lf->ctx->stream, lf->bits, shift, y0, frame_stride, pitch, lf->width, lf->height, n, lf->num_cus,
-                                        lf->dSums.get(), lf->dSums.get() + npx(lf)));
-        else
-            AMT_HIP(launch_logofind(lf->ctx->stream, lf->bits, y0, frame_stride, pitch, lf->width, lf->height, n, lf->num_cus, lf->dSums.get(),
-                                    lf->dSums.get() + npx(lf)));
+        AMT_HIP(launch_logofind(lf->ctx->stream, lf->bits, plane_batch_from(b, f0), lf->width, lf->height, n, lf->num_cus, lf->dSums.get(),
+                                lf->dSums.get() + npx(lf)));
     }
     lf->ctx->prof_end(sp);
     lf->nframes += nframes;
@@ -123,7 +118,7 @@ void amtgpu_logofind_destroy(AmtGpuLogoFind* lf) { delete lf; }
 int amtgpu_logofind_add_batch(AmtGpuLogoFind* lf, const void* dY, int64_t frame_stride, int pitch, int nframes)
 {
     if (!lf) return 0;
-    return guard(lf->ctx, [&] { logofind_add(lf, dY, frame_stride, pitch, nframes); });
+    return guard(lf->ctx, [&] { logofind_add(lf, luma_batch_unchecked(lf->bits, dY, frame_stride, pitch), nframes); });
 }
 
 int amtgpu_logofind_add_surfaces(AmtGpuLogoFind* lf, const AmtGpuSurfaces* batch, int nframes)
@@ -135,7 +130,7 @@ int amtgpu_logofind_add_surfaces(AmtGpuLogoFind* lf, const AmtGpuSurfaces* batch
         const FrameBatch b = surface_batch(batch, "[LogoFind]", true);
         if (batch->bits != lf->bits) throw std::runtime_error("[LogoFind] surfaces of another depth than the finder's");
         // a Y plane is a Y plane whatever the chroma layout; the MSB form (shift 0 at 16 bits: the plain one) reads container >> shift
-        logofind_add(lf, b.Y, b.strideY, b.pitchY, nframes, b.shift);
+        logofind_add(lf, b, nframes);
     });
 }
 
@@ -191,9 +186,9 @@ int amtgpu_scanlogo_auto_bits(AmtGpuContext* c, const void* dY, const void* dU, 
     AmtGpuLogoRect r{};
     const int ok = guard(c, [&] {
         // what amtgpu_scanlogo_bits refuses about the planes, as far as the detection reads them: the luma plane alone
-        (void)plane_batch(bits, dY, nullptr, nullptr, strideY, 0, pitchY, 0, PlaneRules::ScanLogo);
+        const FrameBatch luma = plane_batch(bits, dY, nullptr, nullptr, strideY, 0, pitchY, 0, PlaneRules::ScanLogo);
         std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, bits));
-        logofind_add(lf.get(), dY, strideY, pitchY, nframes);
+        logofind_add(lf.get(), luma, nframes);
         r = best_rect(lf.get(), params);
     });
     if (!ok) return 0;
@@ -223,8 +218,7 @@ int amtgpu_scanlogo_auto_sharded_bits(AmtGpuContext* c, const AmtGpuCollectives*
         std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, imgw, imgh, bits));
         ShardGuard sg(coll, nullptr, "logo detection");
         sg.attempt([&] {
-            (void)plane_batch(bits, dY, nullptr, nullptr, strideY, 0, pitchY, 0, PlaneRules::ScanLogo);
-            logofind_add(lf.get(), dY, strideY, pitchY, nframes_local);
+            logofind_add(lf.get(), plane_batch(bits, dY, nullptr, nullptr, strideY, 0, pitchY, 0, PlaneRules::ScanLogo), nframes_local);
         });
         logofind_reduce(lf.get(), sg);
         r = best_rect(lf.get(), params);       // identical sums on every rank: the same answer (or the same "no logo found") everywhere
@@ -256,7 +250,7 @@ int amtgpu_scanlogo_file_auto(AmtGpuContext* c, const char* srcpath, int service
         RawClipReader in(c, srcpath, true);
         std::unique_ptr<AmtGpuLogoFind> lf(logofind_new(c, in.hd.width, in.hd.height, in.hd.bits));
         while (in.next()) {
-            logofind_add(lf.get(), in.dY, (int64_t)in.ysz, in.hd.width, in.n);
+            logofind_add(lf.get(), luma_batch_unchecked(in.hd.bits, in.dY, (int64_t)in.ysz, in.hd.width), in.n);
             one.progress(0.f, in.nread, in.hd.frames, 0);
         }
         r = best_rect(lf.get(), params);

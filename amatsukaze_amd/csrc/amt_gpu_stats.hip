@@ -39,38 +39,35 @@ void gather_frame_metrics(const AmtGpuCollectives* coll, const uint64_t* local, 
     allgather_records(coll, local, first, nlocal, num_frames, rec * sizeof(uint64_t), out, true, local_error, "the frame metrics");
 }
 
-// What a launch reads: the Y planes of a batch (stride in bytes, pitch in containers) and of the one picture before it (prevY may be
-// null); sample = container >> shift.  A plane call is this with shift 0.  Chroma is never looked at.
-struct StatLuma { const void* Y; int64_t strideY; int pitchY; const void* prevY; int shift; };
+// What a launch reads: a luma batch (a plane call's is luma_batch_unchecked's) and, next to it, the Y plane of the one picture before it (prevY; null: none)
 // ... of a batch of decoder surfaces, checked against the object and against each other
-StatLuma stat_surfaces(const AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch, const AmtGpuSurfaces* prev)
+FrameBatch stat_surfaces(const AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch, const AmtGpuSurfaces* prev, const void*& prevY)
 {
     const char* who = "[FrameStats]";
     const FrameBatch b = surface_batch(batch, who, true);
     if (batch->bits != fs->bits) throw std::runtime_error("[FrameStats] surfaces of another depth than the object's");
     if (b.pitchY < fs->width || b.strideY < 0) throw std::runtime_error("[FrameStats] surface pitchY below the width or negative stride");
-    StatLuma s{b.Y, b.strideY, b.pitchY, nullptr, b.shift};
+    prevY = nullptr;
     if (prev) {
         const FrameBatch p = surface_batch(prev, who, true);
         if (prev->bits != batch->bits || (prev->msb_aligned != 0) != (batch->msb_aligned != 0) || prev->pitchY != batch->pitchY)
             throw std::runtime_error("[FrameStats] the previous picture must have the batch's bits, msb_aligned and pitchY");
-        s.prevY = p.Y;
+        prevY = p.Y;
     }
-    return s;
+    return b;
 }
 
 // the records of nframes frames into dout (device): both batch entry points, once their arguments are read
-void stats_launch(AmtGpuFrameStats* fs, const StatLuma& s, int nframes, unsigned long long* dout)
+void stats_launch(AmtGpuFrameStats* fs, const FrameBatch& luma, const void* prevY, int nframes, unsigned long long* dout)
 {
     fs->ctx->bind();
     const int sp = fs->ctx->prof_begin("frame_stats_kernel");
-    AMT_HIP(s.shift ? launch_frame_stats_msb(fs->ctx->stream, fs->bits, s.shift, s.Y, s.strideY, s.pitchY, fs->width, fs->height, s.prevY, nframes, dout)
-                    : launch_frame_stats(fs->ctx->stream, fs->bits, s.Y, s.strideY, s.pitchY, fs->width, fs->height, s.prevY, nframes, dout));
+    AMT_HIP(launch_frame_stats(fs->ctx->stream, fs->bits, luma, fs->width, fs->height, prevY, nframes, dout));
     fs->ctx->prof_end(sp);
 }
 
-// launch, download and gather: both sharded entry points.  luma(): the shard's descriptor, called (and free to refuse) once the range is
-// known to hold frames; have_prev / prev_words: whether the caller gave the frame before the shard, and what its absence is called
+// launch, download and gather: both sharded entry points.  luma(prevY): the shard's batch and the Y plane before it, called (and free to
+// refuse) once the range is known to hold frames; have_prev / prev_words: whether the caller gave the frame before the shard, and what its absence is called
 template <typename F>
 void stats_sharded(AmtGpuFrameStats* fs, const AmtGpuCollectives* coll, bool have_prev, const char* prev_words, F&& luma, int first, int nlocal,
                    int num_frames, uint64_t* metrics_out)
@@ -83,11 +80,12 @@ void stats_sharded(AmtGpuFrameStats* fs, const AmtGpuCollectives* coll, bool hav
         if (first > 0 && nlocal > 0 && !have_prev)
             throw std::runtime_error(std::string("[FrameStats] a shard that does not start the clip needs the ") + prev_words);
         if (nlocal > 0) {
-            const StatLuma s = luma();
+            const void* prevY = nullptr;
+            const FrameBatch b = luma(prevY);
             fs->ctx->bind();
             const size_t n = (size_t)nlocal * AMTGPU_FS_WORDS;
             if (fs->dShard.size() < n) fs->dShard.alloc(n);
-            stats_launch(fs, s, nlocal, fs->dShard.get());
+            stats_launch(fs, b, prevY, nlocal, fs->dShard.get());
             local.resize(n);
             download_via_pinned(fs->ctx, local.data(), fs->dShard.get(), n * sizeof(uint64_t));
         }
@@ -112,7 +110,7 @@ void amtgpu_framestats_destroy(AmtGpuFrameStats* fs) { delete fs; }
 int amtgpu_framestats_batch(AmtGpuFrameStats* fs, const void* dY, int64_t frame_stride, int pitch, const void* dprevY, int nframes,
                             uint64_t* dout)
 {
-    return guard(fs->ctx, [&] { stats_launch(fs, StatLuma{dY, frame_stride, pitch, dprevY, 0}, nframes, (unsigned long long*)dout); });
+    return guard(fs->ctx, [&] { stats_launch(fs, luma_batch_unchecked(fs->bits, dY, frame_stride, pitch), dprevY, nframes, (unsigned long long*)dout); });
 }
 
 int amtgpu_framestats_allgather(AmtGpuFrameStats* fs, const AmtGpuCollectives* coll, const uint64_t* local_metrics, int first, int nlocal,
@@ -126,7 +124,8 @@ int amtgpu_framestats_sharded(AmtGpuFrameStats* fs, const AmtGpuCollectives* col
 {
     return guard(fs->ctx, [&] {
         stats_sharded(fs, coll, dprevY != nullptr, "frame before it (dprevY)",
-                      [&] { return StatLuma{dY, frame_stride, pitch, first > 0 ? dprevY : nullptr, 0}; }, first, nlocal, num_frames, metrics_out);
+                      [&](const void*& prevY) { prevY = first > 0 ? dprevY : nullptr; return luma_batch_unchecked(fs->bits, dY, frame_stride, pitch); },
+                      first, nlocal, num_frames, metrics_out);
     });
 }
 
@@ -135,9 +134,10 @@ int amtgpu_framestats_surfaces(AmtGpuFrameStats* fs, const AmtGpuSurfaces* batch
     return guard(fs->ctx, [&] {
         if (nframes < 0) throw std::runtime_error("[FrameStats] negative frame count");
         if (nframes == 0) return;
-        const StatLuma s = stat_surfaces(fs, batch, prev);
+        const void* prevY = nullptr;
+        const FrameBatch b = stat_surfaces(fs, batch, prev, prevY);
         if (!dout) throw std::runtime_error("[FrameStats] null metrics pointer");
-        stats_launch(fs, s, nframes, (unsigned long long*)dout);
+        stats_launch(fs, b, prevY, nframes, (unsigned long long*)dout);
     });
 }
 
@@ -145,8 +145,8 @@ int amtgpu_framestats_sharded_surfaces(AmtGpuFrameStats* fs, const AmtGpuCollect
                                        const AmtGpuSurfaces* prev, int first, int nlocal, int num_frames, uint64_t* metrics_out)
 {
     return guard(fs->ctx, [&] {
-        stats_sharded(fs, coll, prev != nullptr, "picture before it (prev)", [&] { return stat_surfaces(fs, batch, first > 0 ? prev : nullptr); }, first,
-                      nlocal, num_frames, metrics_out);
+        stats_sharded(fs, coll, prev != nullptr, "picture before it (prev)", [&](const void*& prevY) { return stat_surfaces(fs, batch, first > 0 ? prev : nullptr, prevY); },
+                      first, nlocal, num_frames, metrics_out);
     });
 }
 

@@ -96,6 +96,13 @@ inline amt::FrameBatch plane_batch(int bits, const void* Y, const void* U, const
     if (scan && ((uintptr_t)Y % es || (uintptr_t)U % es || (uintptr_t)V % es)) throw std::runtime_error("[ScanLogo] plane base not aligned to the sample size");
     return amt::FrameBatch{Y, U, V, strideY, strideUV, pitchY, pitchUV, es, 0, 0};
 }
+// The luma batch of the plane entry points of the frame metrics and the logo finder (amtgpu_framestats_batch, _sharded, _logofind_add_batch,
+// the raw-clip reader's chunks), and of nobody else.  It checks nothing: their kernels count the stride in bytes, so these calls have never
+// refused a stride that the sample size does not divide, and must not start to.  A launcher that divides the stride needs plane_batch.
+inline amt::FrameBatch luma_batch_unchecked(int bits, const void* Y, int64_t strideY, int pitchY)
+{
+    return amt::FrameBatch{Y, nullptr, nullptr, strideY, 0, pitchY, 0, sample_bytes(bits), 0, 0};
+}
 
 // A batch of decoder surfaces as the kernels take it, or a refusal in the caller's words (`who`: "[ScanLogo]", ...): the one place that
 // reads an AmtGpuSurfaces.  luma_only: the chroma fields are not looked at (the logo finder).
@@ -138,18 +145,17 @@ inline void surfaces_extract(AmtGpuContext* c, const AmtGpuSurfaces* src, const 
     c->prof_end(sp);
 }
 
-// The Y planes of a batch of surfaces as the evaluation engines take a luma batch (EvalEngine::run, analyze_run): base of picture 0,
-// bytes between pictures, row pitch in samples.  The engines read rows [row0, row1) and columns [col0, col1) of every picture and
+// The Y planes of a batch of surfaces (b: surface_batch's, luma_only) as the evaluation engines take a luma batch (EvalEngine::run,
+// analyze_run): LSB samples, planar, no chroma.  The engines read rows [row0, row1) and columns [col0, col1) of every picture and
 // nothing else.  LSB surfaces are passed as they lie.  MSB-aligned ones: that band of every picture -- from col0 rounded down to 64
 // containers -- is copied as LSB samples (surfaces_extract_kernel with an empty chroma part) into `scratch`, which grows to the largest
-// batch seen, rows a multiple of 64 samples apart, and the view's base is where sample (0, 0) of picture 0 would lie in that layout:
+// batch seen, rows a multiple of 64 samples apart, and the batch's base is where sample (0, 0) of picture 0 would lie in that layout:
 // the engines' alignment-dependent choices are those of an aligned planar clip.  The scratch is the caller's (one per object: its
 // surfaces entry points are not re-entrant).
-struct LumaView { const void* Y; int64_t stride_bytes; int pitch; };
-inline LumaView surfaces_luma_view(AmtGpuContext* c, const amt::FrameBatch& b, int row0, int row1, int col0, int col1, int nframes,
-                                   amt::DevBuf<uint8_t>& scratch)
+inline amt::FrameBatch surfaces_luma_view(AmtGpuContext* c, const amt::FrameBatch& b, int row0, int row1, int col0, int col1, int nframes,
+                                          amt::DevBuf<uint8_t>& scratch)
 {
-    if (!b.shift) return LumaView{b.Y, b.strideY, b.pitchY};
+    if (!b.shift) return b;
     const int c0 = col0 & ~63, bw = col1 - c0, rows = row1 - row0;
     const int pitch = (bw + 63) & ~63;
     const size_t frame_bytes = (size_t)rows * pitch * b.es;
@@ -159,13 +165,11 @@ inline LumaView surfaces_luma_view(AmtGpuContext* c, const amt::FrameBatch& b, i
     c->bind();
     if (scratch.size() < need) scratch.alloc(need);        // (hipFree waits for the kernels that still read the old scratch)
     uint8_t* band = scratch.get();
-    amt::FrameBatch luma = b;
-    luma.U = luma.V = nullptr; luma.strideUV = 0; luma.pitchUV = 0;
     const int sp = c->prof_begin("surfaces_extract_kernel");
-    AMT_HIP(amt::launch_surfaces_extract(c->stream, luma, amt::ScanRect{c0, row0, 0, 0, bw, rows, 0, 0}, nframes, amt::PlanesOut{band, nullptr, nullptr},
+    AMT_HIP(amt::launch_surfaces_extract(c->stream, b, amt::ScanRect{c0, row0, 0, 0, bw, rows, 0, 0}, nframes, amt::PlanesOut{band, nullptr, nullptr},
                                          (long long)frame_bytes, 0, pitch, 0));
     c->prof_end(sp);
-    return LumaView{band - ((size_t)row0 * pitch + c0) * b.es, (int64_t)frame_bytes, pitch};
+    return amt::FrameBatch{band - ((size_t)row0 * pitch + c0) * b.es, nullptr, nullptr, (long long)frame_bytes, 0, pitch, 0, b.es, 0, 0};
 }
 
 // amtgpu_amts_read_audio (amts_file.cpp) for callers inside the library: throws instead of leaving a message on the file's context

@@ -155,16 +155,15 @@ public:
     // prof_name: label of this engine's launches in amtgpu_profile_report (no spaces)
     EvalEngine(AmtGpuContext* ctx, std::vector<EvalLogoSpec> specs, std::vector<float> fades, bool take_abs, int out_frame_stride,
                const char* prof_name = "logo_eval_fused_kernel");
-    // async on ctx->stream; dout device, nframes*out_frame_stride floats
-    // dframe_map (device, optional): batch frame i reads source frame dframe_map[i] of dY
-    void run(const void* dY, int64_t frame_stride_bytes, int pitch, int bits, int nframes, float* dout,
-             const int* dframe_map = nullptr);
+    // async on ctx->stream; dout device, nframes*out_frame_stride floats.  luma: the batch's Y planes as LSB samples `bits` deep (a
+    // FrameBatch with null chroma, built by plane_batch or surfaces_luma_view, which have checked it)
+    // dframe_map (device, optional): batch frame i reads source frame dframe_map[i] of luma
+    void run(const FrameBatch& luma, int bits, int nframes, float* dout, const int* dframe_map = nullptr);
     // Linear (decision-guarded) evaluation of all fades from one window evaluation of s and one of bg
     // (eval_linear_kernels.hip).  Results are within linear_error_bound(i, bits) of run()'s for logo i; same arguments as run().
     // dforce (device, optional, nframes bytes): the kernel sets the byte of every frame it could not finish in this mode (its list of
     // means next to a bin edge overflowed): the caller re-evaluates those frames exactly
-    void run_linear(const void* dY, int64_t frame_stride_bytes, int pitch, int bits, int nframes, float* dout,
-                    const int* dframe_map = nullptr, uint8_t* dforce = nullptr);
+    void run_linear(const FrameBatch& luma, int bits, int nframes, float* dout, const int* dframe_map = nullptr, uint8_t* dforce = nullptr);
     // (pixel, frame, fade) pairs a wave of the linear kernel can list for the exact bin check (default 256; amtgpu_analyze_set_fixup_queue)
     void set_linear_queue(int entries) { lin_queue_ = entries; }
     // rigorous bound on |run_linear - run| for every score of logo i (rounding analysis in eval_engine.hip)
@@ -173,8 +172,8 @@ public:
     // go to record dlist[j] of dout (scatter).  max_frames bounds *dcount.  async
     // G = frames per workgroup, fade_chunk = fades per workgroup (0: all): the defaults suit a handful of frames; a whole batch (the
     // monitored mode's gated re-evaluation) takes run()'s G and fade_chunk 0
-    void run_listed(const void* dY, int64_t frame_stride_bytes, int pitch, int bits, int max_frames, const int* dlist, const int* dcount,
-                    float* dout, int G = 1, int fade_chunk = -1);
+    void run_listed(const FrameBatch& luma, int bits, int max_frames, const int* dlist, const int* dcount, float* dout, int G = 1,
+                    int fade_chunk = -1);
     // frames per workgroup run() takes for a batch of nframes
     int exact_group_frames(int nframes) const;
     int num_fades() const { return (int)fades_.size(); }

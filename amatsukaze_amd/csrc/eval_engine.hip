@@ -188,26 +188,23 @@ double EvalEngine::mask_pixel_evals_per_frame() const
     return s;
 }
 
-void EvalEngine::run(const void* dY, int64_t frame_stride_bytes, int pitch, int bits, int nframes, float* dout,
-                     const int* dframe_map)
+void EvalEngine::run(const FrameBatch& luma, int bits, int nframes, float* dout, const int* dframe_map)
 {
     if (nframes <= 0 || specs_.empty()) return;
     ctx_->bind();
-    const int es = bits <= 8 ? 1 : 2;
-    if (frame_stride_bytes % es) throw std::runtime_error("frame stride not a multiple of the sample size");
     // frames per workgroup: amortises the per-band tap loads; keep >= ~2k workgroups per launch
     const int nl = (int)specs_.size();
     int G = exact_group_frames(nframes);
     const int nf_all = (int)fades_.size();
-    if (pair_eligible() && pair_addressable(pitch * es)) {
+    if (pair_eligible() && pair_addressable(luma.pitchY * luma.es)) {
         // fades {0, 1}: the window of s and the window of bg are the two blends themselves
         const size_t dot = prof_name_.find('.');
         const std::string suffix = dot == std::string::npos ? std::string() : prof_name_.substr(dot);
         const int Gp = group_frames_ > 0 ? group_frames_ : (int)std::max(1LL, std::min((long long)kTileMaxFrames, (long long)nframes * nl / 2048));
         // (tables that carry DeintY's 0.25 -- every engine, in practice -- or the kernel's ldexp form on unscaled ones: ensure_tiles)
         const int sp = ctx_->prof_begin(((tiles_stage4_ ? "logo_eval_pair_kernel" : "logo_eval_pair_ldexp_kernel") + suffix).c_str());
-        AMT_HIP(launch_logo_eval_pair(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, dY, dframe_map,
-                                      frame_stride_bytes / es, pitch, nframes, Gp, dout, out_frame_stride_, take_abs_ ? 1 : 0, tiles_stage4_ ? 0 : 1));
+        AMT_HIP(launch_logo_eval_pair(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, luma, dframe_map, nframes, Gp, dout, out_frame_stride_,
+                                      take_abs_ ? 1 : 0, tiles_stage4_ ? 0 : 1));
         ctx_->prof_end(sp);
         return;
     }
@@ -215,9 +212,8 @@ void EvalEngine::run(const void* dY, int64_t frame_stride_bytes, int pitch, int 
         const int nf = std::min(kEvalMaxFades, nf_all - f0);
         G = std::max(1, std::min(G, kEvalThreads / nf));
         const int sp = ctx_->prof_begin(prof_name_.c_str());
-        AMT_HIP(launch_logo_eval_fused(ctx_->stream, bits, d_logos_.get(), nl, d_bands_.get(), d_fades_.get(), nf, f0, dY, dframe_map,
-                                       frame_stride_bytes / es, pitch, nframes, G, dout, out_frame_stride_, take_abs_ ? 1 : 0,
-                                       plane_cap_));
+        AMT_HIP(launch_logo_eval_fused(ctx_->stream, bits, d_logos_.get(), nl, d_bands_.get(), d_fades_.get(), nf, f0, luma, dframe_map, nframes, G,
+                                       dout, out_frame_stride_, take_abs_ ? 1 : 0, plane_cap_));
         ctx_->prof_end(sp);
     }
 }
@@ -473,58 +469,54 @@ float EvalEngine::linear_error_bound(int logo, int bits) const
     return (float)(1.25 * (u * (lin_err_corr_[logo] * vmax_unit_ * maxv + lin_err_sum_[logo]) + lin_err_formula_[logo]));
 }
 
-void EvalEngine::run_linear(const void* dY, int64_t frame_stride_bytes, int pitch, int bits, int nframes, float* dout, const int* dframe_map,
-                            uint8_t* dforce)
+void EvalEngine::run_linear(const FrameBatch& luma, int bits, int nframes, float* dout, const int* dframe_map, uint8_t* dforce)
 {
     if (nframes <= 0 || specs_.empty()) return;
-    const int es = bits <= 8 ? 1 : 2;
-    // The linear kernel evaluates AMTAnalyzeLogo's 11 fades on tile plans.  A logo without mask pixels (maskratio 0: results are
-    // 0 / blackScore = 0 / 0, as the reference's), odd or tiny shapes and any other fade list keep the exact kernel.
-    // the linear kernel is written for AMTAnalyzeLogo's fades: eleven, from exactly 0 to exactly 1
-    if ((int)fades_.size() != 11 || fades_.front() != 0.0f || fades_.back() != 1.0f || !tiles_usable(pitch * es)) { run(dY, frame_stride_bytes, pitch, bits, nframes, dout, dframe_map); return; }
-    ensure_linear();
-    if (!lin_formula_ok_) { run(dY, frame_stride_bytes, pitch, bits, nframes, dout, dframe_map); return; }      // (a degenerate logo: the exact kernel)
-    ensure_tiles();
-    if (!tile_slots_ok_) { run(dY, frame_stride_bytes, pitch, bits, nframes, dout, dframe_map); return; }      // (a tile plan beyond the slot limit: the exact kernel)
-    ctx_->bind();
-    if (frame_stride_bytes % es) throw std::runtime_error("frame stride not a multiple of the sample size");
-    const int nl = (int)specs_.size();
-    // The interpolated mean is within 19 u v of the exactly evaluated one (7 + 7 roundings of the two means, 3 to combine them, 9 on
-    // the exact side... see ensure_linear), v = a bound on the window values: fades in [0, 1] blend convexly, so v = max(1, |a| + |b|) * maxv
-    // (vmax_unit_, ensure_linear).  The kernel compares in fixed point -- mean * 2^qlog2 with v * 2^qlog2 < 2^30 -- through three more
-    // fp32 roundings of values below v * 2^qlog2: 22 u v in all.
-    const double vwin = (double)vmax_unit_ * (double)((1 << bits) - 1);
-    const float bin_eps = (float)(22.0 / 16777216.0 * vwin * 1.0001);
-    int qlog2 = 24;
-    while (qlog2 > 4 && std::ldexp(vwin, qlog2) >= 1073741824.0) --qlog2;
-    if (!(std::ldexp(vwin, qlog2) < 1073741824.0)) { run(dY, frame_stride_bytes, pitch, bits, nframes, dout, dframe_map); return; }   // (absurd coefficients: the exact kernel)
     // frames per workgroup: four workgroups of four waves share a CU's 160 KB of LDS -- 16 KB of tile planes, 4 x 8 B x the list's entries,
     // 3 KB of running sums per frame
     const int qcap = std::max(16, std::min(640, lin_queue_));
     const int g_fit = (int)((160 * 1024 / 4 - 16 * 1024 - 4 * 8 * qcap - 16) / (4 * 768));
-    if (g_fit < 1) { run(dY, frame_stride_bytes, pitch, bits, nframes, dout, dframe_map); return; }
+    float bin_eps = 0.0f;
+    int qlog2 = 24;
+    // may the linear kernel take this batch?  (In this order: ensure_linear and ensure_tiles build on first use and throw for some logos.)
+    const auto linear_takes = [&] {
+        // The linear kernel evaluates AMTAnalyzeLogo's 11 fades, from exactly 0 to exactly 1, on tile plans.  A logo without mask pixels
+        // (maskratio 0: results are 0 / blackScore = 0 / 0, as the reference's), odd or tiny shapes and any other fade list keep the exact kernel.
+        if ((int)fades_.size() != 11 || fades_.front() != 0.0f || fades_.back() != 1.0f || !tiles_usable(luma.pitchY * luma.es)) return false;
+        ensure_linear();
+        if (!lin_formula_ok_) return false;             // (a degenerate logo)
+        ensure_tiles();
+        if (!tile_slots_ok_) return false;              // (a tile plan beyond the slot limit)
+        // The interpolated mean is within 19 u v of the exactly evaluated one (7 + 7 roundings of the two means, 3 to combine them, 9 on
+        // the exact side... see ensure_linear), v = a bound on the window values: fades in [0, 1] blend convexly, so v = max(1, |a| + |b|) * maxv
+        // (vmax_unit_, ensure_linear).  The kernel compares in fixed point -- mean * 2^qlog2 with v * 2^qlog2 < 2^30 -- through three more
+        // fp32 roundings of values below v * 2^qlog2: 22 u v in all.
+        const double vwin = (double)vmax_unit_ * (double)((1 << bits) - 1);
+        bin_eps = (float)(22.0 / 16777216.0 * vwin * 1.0001);
+        while (qlog2 > 4 && std::ldexp(vwin, qlog2) >= 1073741824.0) --qlog2;
+        return std::ldexp(vwin, qlog2) < 1073741824.0 && g_fit >= 1;       // (absurd coefficients, or a list that leaves no room for a frame)
+    };
+    if (!linear_takes()) { run(luma, bits, nframes, dout, dframe_map); return; }      // the exact kernel
+    ctx_->bind();
+    const int nl = (int)specs_.size();
     const int gmax = std::min(g_fit, bits > 8 ? kLinMaxFrames16 : kLinMaxFrames);
     const long long wgs_min = bits > 8 ? AMT_LIN_WGS_MIN16 : 2048;
     const int G = std::min(gmax, group_frames_ > 0 ? group_frames_ : (int)std::max(1LL, std::min(16LL, (long long)nframes * nl / wgs_min)));
     const size_t dot = prof_name_.find('.');
     const int sp = ctx_->prof_begin(("logo_eval_linear_kernel" + (dot == std::string::npos ? std::string() : prof_name_.substr(dot))).c_str());
-    AMT_HIP(launch_logo_eval_linear(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, d_fades_.get(), 11, 0, dY, dframe_map,
-                                    frame_stride_bytes / es, pitch, nframes, G, dout, out_frame_stride_, take_abs_ ? 1 : 0, bin_eps, qlog2,
-                                    qcap, dforce));
+    AMT_HIP(launch_logo_eval_linear(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, d_fades_.get(), 11, 0, luma, dframe_map, nframes, G, dout,
+                                    out_frame_stride_, take_abs_ ? 1 : 0, bin_eps, qlog2, qcap, dforce));
     ctx_->prof_end(sp);
 }
 
 #ifndef AMT_LISTED_FADE_CHUNK
 #define AMT_LISTED_FADE_CHUNK 1      /* fades per workgroup of the listed re-evaluation (0: all of them, round 3's form) */
 #endif
-void EvalEngine::run_listed(const void* dY, int64_t frame_stride_bytes, int pitch, int bits, int max_frames, const int* dlist,
-                            const int* dcount, float* dout, int G, int fade_chunk)
+void EvalEngine::run_listed(const FrameBatch& luma, int bits, int max_frames, const int* dlist, const int* dcount, float* dout, int G, int fade_chunk)
 {
     if (max_frames <= 0 || specs_.empty()) return;
     if (fade_chunk < 0) fade_chunk = AMT_LISTED_FADE_CHUNK;
     ctx_->bind();
-    const int es = bits <= 8 ? 1 : 2;
-    if (frame_stride_bytes % es) throw std::runtime_error("frame stride not a multiple of the sample size");
     const int nl = (int)specs_.size();
     const int nf_all = (int)fades_.size();
     for (int f0 = 0; f0 < nf_all; f0 += kEvalMaxFades) {
@@ -532,9 +524,8 @@ void EvalEngine::run_listed(const void* dY, int64_t frame_stride_bytes, int pitc
         // (by default a handful of frames is expected: one per workgroup, so that the pass lasts one frame's walk over the bands)
         const int g = std::max(1, std::min(G, kEvalThreads / nf));
         const int sp = ctx_->prof_begin((prof_name_ + (G > 1 || fade_chunk != AMT_LISTED_FADE_CHUNK ? "_gated" : "_refine")).c_str());
-        AMT_HIP(launch_logo_eval_fused(ctx_->stream, bits, d_logos_.get(), nl, d_bands_.get(), d_fades_.get(), nf, f0, dY, dlist,
-                                       frame_stride_bytes / es, pitch, max_frames, g, dout, out_frame_stride_, take_abs_ ? 1 : 0,
-                                       plane_cap_, dcount, 1, fade_chunk));
+        AMT_HIP(launch_logo_eval_fused(ctx_->stream, bits, d_logos_.get(), nl, d_bands_.get(), d_fades_.get(), nf, f0, luma, dlist, max_frames, g, dout,
+                                       out_frame_stride_, take_abs_ ? 1 : 0, plane_cap_, dcount, 1, fade_chunk));
         ctx_->prof_end(sp);
     }
 }

@@ -361,11 +361,12 @@ static size_t fused_lds_bytes(int plane_cap, int nfades, int sc_pitch, int G, in
 }
 
 hipError_t launch_logo_eval_fused(hipStream_t st, int bits, const EvalLogoDev* dlogos, int nlogos, const EvalBand* dbands,
-                                  const float* dfades, int nfades, int fade0, const void* dY, const int* dframe_map,
-                                  long long frame_stride_elems, int pitch, int nframes, int G, float* dout, int out_frame_stride,
+                                  const float* dfades, int nfades, int fade0, const FrameBatch& luma, const int* dframe_map,
+                                  int nframes, int G, float* dout, int out_frame_stride,
                                   int take_abs, int plane_cap, const int* dnframes, int scatter, int fade_chunk)
 {
     if (nframes <= 0 || nlogos <= 0 || nfades <= 0) return hipSuccess;
+    if (luma.shift || luma.es != (bits <= 8 ? 1 : 2)) return hipErrorInvalidValue;
     if (scatter && !dframe_map) return hipErrorInvalidValue;
     if (nfades > kEvalMaxFades || G * nfades > kEvalThreads || plane_cap > kEvalThreads * kEvalStage) return hipErrorInvalidValue;
     const int ngroups = (nframes + G - 1) / G;
@@ -381,7 +382,7 @@ hipError_t launch_logo_eval_fused(hipStream_t st, int bits, const EvalLogoDev* d
     const size_t lds = fused_lds_bytes(plane_cap, nfades, sc_pitch, G, fpi);
 #define AMT_LAUNCH(T, F)                                                                                                          \
     hipLaunchKernelGGL((logo_eval_fused_kernel<T, F>), grid, dim3(kEvalThreads), lds, st, dlogos, dbands, dfades, nfades, fade0,         \
-                       (const T*)dY, dframe_map, frame_stride_elems, pitch, maxv, nframes, G, ngroups, dout, out_frame_stride, take_abs, \
+                       (const T*)luma.Y, dframe_map, luma.strideY / luma.es, luma.pitchY, maxv, nframes, G, ngroups, dout, out_frame_stride, take_abs, \
                        plane_cap, sc_pitch, dnframes, scatter, nlogos, fade_chunk)
     if (fpi == 2) { if (bits <= 8) AMT_LAUNCH(uint8_t, 2); else AMT_LAUNCH(uint16_t, 2); }
     else { if (bits <= 8) AMT_LAUNCH(uint8_t, 1); else AMT_LAUNCH(uint16_t, 1); }

@@ -697,17 +697,18 @@ __global__ __launch_bounds__(kLinWgThreads) __attribute__((amdgpu_waves_per_eu(A
 void logo_eval_linear_kernel16(const LinLaunch A) { logo_eval_linear_split<uint16_t>(A); }
 
 hipError_t launch_logo_eval_linear(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
-                                   const float* dfades, int nfades, int fade0, const void* dY,
-                                   const int* dframe_map, long long frame_stride_elems, int pitch, int nframes, int G, float* dout,
+                                   const float* dfades, int nfades, int fade0, const FrameBatch& luma,
+                                   const int* dframe_map, int nframes, int G, float* dout,
                                    int out_frame_stride, int take_abs, float bin_eps, int qlog2, int qcap, uint8_t* dforce)
 {
     if (qcap < 1 || qcap > 4096) return hipErrorInvalidValue;
     // (the caller guarantees dfades[fade0] == 0 and dfades[fade0 + nfades - 1] == 1: EvalEngine::run_linear)
     if (nframes <= 0 || nlogos <= 0 || nfades <= 0) return hipSuccess;
+    if (luma.shift || luma.es != (bits <= 8 ? 1 : 2)) return hipErrorInvalidValue;
     if (qlog2 < 4 || qlog2 > 24 || !(bin_eps >= 0.0f) || bin_eps * (float)(1 << qlog2) > 1048576.0f) return hipErrorInvalidValue;
     if (nfades != 11 || G < 1 || G > (bits > 8 ? kLinMaxFrames16 : kLinMaxFrames) || G * nfades > kLinWgThreads) return hipErrorInvalidValue;       // (AMTAnalyzeLogo's fades; anything else keeps the exact kernel)
     LinLaunch A;
-    A.logos = dlogos; A.tls = dtls; A.fades = dfades; A.Y = dY; A.frame_map = dframe_map; A.frame_stride = frame_stride_elems; A.pitch = pitch;
+    A.logos = dlogos; A.tls = dtls; A.fades = dfades; A.Y = luma.Y; A.frame_map = dframe_map; A.frame_stride = luma.strideY / luma.es; A.pitch = luma.pitchY;
     A.maxv = (float)((1 << bits) - 1);
     A.nfades = nfades; A.fade0 = fade0;
     A.nframes = nframes; A.G = G; A.ngroups = (nframes + G - 1) / G;
@@ -884,12 +885,12 @@ void rect_range_flag_kernel(const uint16_t* __restrict__ Y, long long frame_stri
     if (threadIdx.x == 0) flag[blockIdx.x] = any ? 1 : 0;
 }
 
-hipError_t launch_rect_range_flag(hipStream_t st, const void* dY, long long frame_stride_elems, int pitch, int imgx, int imgy, int w, int h, int bits,
-                                  int nframes, uint8_t* dflag)
+hipError_t launch_rect_range_flag(hipStream_t st, const FrameBatch& luma, int imgx, int imgy, int w, int h, int bits, int nframes, uint8_t* dflag)
 {
     if (nframes <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rect_range_flag_kernel, dim3((unsigned)nframes), dim3(256), 0, st, (const uint16_t*)dY, frame_stride_elems, pitch, imgx, imgy, w, h,
-                       (unsigned)((1 << bits) - 1), dflag);
+    if (luma.shift || luma.es != 2 || bits <= 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rect_range_flag_kernel, dim3((unsigned)nframes), dim3(256), 0, st, (const uint16_t*)luma.Y, luma.strideY / luma.es, luma.pitchY,
+                       imgx, imgy, w, h, (unsigned)((1 << bits) - 1), dflag);
     return hipGetLastError();
 }
 

@@ -222,12 +222,13 @@ void logo_eval_pair_ldexp_kernel(const PairLaunch A) { logo_eval_pair_body<pix_t
 
 // ldexp_form: the engine's tables are NOT scaled (EvalEngine::ensure_tiles)
 hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
-                                 const void* dY, const int* dframe_map, long long frame_stride_elems, int pitch,
+                                 const FrameBatch& luma, const int* dframe_map,
                                  int nframes, int G, float* dout, int out_frame_stride, int take_abs, int ldexp_form)
 {
     if (nframes <= 0 || nlogos <= 0) return hipSuccess;
+    if (luma.shift || luma.es != (bits <= 8 ? 1 : 2)) return hipErrorInvalidValue;
     PairLaunch A;
-    A.logos = dlogos; A.tls = dtls; A.Y = dY; A.frame_map = dframe_map; A.frame_stride = frame_stride_elems; A.pitch = pitch;
+    A.logos = dlogos; A.tls = dtls; A.Y = luma.Y; A.frame_map = dframe_map; A.frame_stride = luma.strideY / luma.es; A.pitch = luma.pitchY;
     A.maxv = (float)((1 << bits) - 1);
     A.nframes = nframes; A.G = G; A.ngroups = (nframes + G - 1) / G; A.nlogos = nlogos;
     A.out = dout; A.out_frame_stride = out_frame_stride; A.take_abs = take_abs;

@@ -1,8 +1,10 @@
 // kernels.hpp -- the interface between the kernel files (*_kernels.hip) and the host code that launches them: every launcher is declared
 // here and nowhere else (default arguments too), and so is every struct both sides see.  Each kernel file includes it, so a definition
 // that has drifted from its declaration, or a second definition of a struct passed by value into a kernel, does not compile.
-// A batch of frames crosses it as one struct in one unit convention (FrameBatch: frame strides in bytes), and the lane widths the
-// copy-shaped launchers choose come from one rule (lane_rule.h; the weave's vec flag is still formed in amt_gpu_ingest.hip).
+// (The entries of stats_msb_kernels.hip and logofind_msb_kernels.hip, which only launch_frame_stats and launch_logofind call, are in their body headers.)
+// A batch of frames crosses it as one struct in one unit convention (FrameBatch: frame strides in bytes; null chroma for the passes that read
+// the Y plane alone), and the lane widths the copy-shaped launchers choose come from one rule (lane_rule.h; the weave's vec flag is still
+// formed in amt_gpu_ingest.hip).
 // Kept light on purpose (no <vector>, <string>, <mutex>): it goes into translation units that are all device code.
 #pragma once
 
@@ -21,6 +23,8 @@ struct TileDesc; struct TileBandDesc;     // eval_tiles.hpp
 // pitches (between rows) in containers of es bytes.  interleaved: U is the U0 V0 U1 V1 ... plane and V unused; sample = container >> shift.
 // Planar LSB planes are interleaved = 0, shift = 0.  A kernel whose argument list counts strides in samples gets stride / es on the line
 // that forms that argument, and nowhere else.  Built by plane_batch / surface_batch (api_common.hpp), which refuse what es does not divide.
+// A luma batch (frame metrics, logo finder, evaluation kernels) has U = V = nullptr, strideUV = pitchUV = 0; its launchers read Y, strideY,
+// pitchY, es and shift alone (an NV12 surface's Y plane is a Y plane), and an es that is not their `bits`' container size is hipErrorInvalidValue.
 struct FrameBatch { const void *Y, *U, *V; long long strideY, strideUV; int pitchY, pitchUV; int es, interleaved, shift; };
 // the same batch from frame `frames` on
 inline FrameBatch plane_batch_from(FrameBatch b, long long frames)
@@ -122,20 +126,14 @@ hipError_t launch_kfm_render_adaptive(hipStream_t st, const RenderArgs& a, const
 hipError_t launch_kfm_render_adaptive_surfaces(hipStream_t st, const RenderArgs& a, int interleaved, int shift, const RenderAdaptiveEntry* dplan, int nout);
 
 // ---- stats_kernels.hip, logofind_kernels.hip ----
-hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,
-                              const void* dprevY, int nframes, unsigned long long* dout);
-// stats_msb_kernels.hip: the same metrics of container >> shift (16-bit containers; bits = the depth of the shifted samples, 9..15;
-// shift = 16 - bits); the kernel form is chosen by the rules of launch_frame_stats
-hipError_t launch_frame_stats_msb(hipStream_t st, int bits, int shift, const void* dY, long long frame_stride_bytes, int pitch_elems, int W, int H,
-                                  const void* dprevY, int nframes, unsigned long long* dout);
+// Both take a luma batch of either alignment: b.shift != 0 (16-bit containers, shift = 16 - bits) runs the same sums on container >> shift,
+// `bits` then being the depth of the shifted samples (9..15 metrics, 9..16 finder): the instantiations of stats_msb_ / logofind_msb_kernels.hip.
+hipError_t launch_frame_stats(hipStream_t st, int bits, const FrameBatch& b, int W, int H, const void* dprevY, int nframes, unsigned long long* dout);
 // Largest frame count of one launch_logofind: its uint32 partials hold at most 2 * maxv per frame (SM) below 2^31.
 long long logofind_launch_cap(int bits);
 // nframes <= logofind_launch_cap(bits) (the caller splits); dS1 / dSM: W*H int64 each, added to
-hipError_t launch_logofind(hipStream_t st, int bits, const void* dY, long long frame_stride, int pitch_elems, int W, int H, int nframes,
-                           int num_cus, unsigned long long* dS1, unsigned long long* dSM);
-// logofind_msb_kernels.hip: the same sums of container >> shift (16-bit containers; bits = the depth of the shifted samples)
-hipError_t launch_logofind_msb(hipStream_t st, int bits, int shift, const void* dY, long long frame_stride, int pitch_elems, int W, int H,
-                               int nframes, int num_cus, unsigned long long* dS1, unsigned long long* dSM);
+hipError_t launch_logofind(hipStream_t st, int bits, const FrameBatch& b, int W, int H, int nframes, int num_cus, unsigned long long* dS1,
+                           unsigned long long* dSM);
 
 // ---- audio_kernels.hip ----
 // The audio timeline of a clip: video frame n owns sample-frames [b(n), b(n + 1)) below num_samples, b(n) = n * step_num / fps_num floored
@@ -167,23 +165,23 @@ struct TileLogoDev {
     const char* lin;
     unsigned lin_pq, lin_sinfo, lin_a, lin_b;
 };
+// These three and launch_rect_range_flag take a luma batch of LSB samples (a shift is hipErrorInvalidValue: surfaces_luma_view, api_common.hpp).
 // eval_fused_kernels.hip.  dnframes (device, optional): the number of frames actually present (<= nframes,
 // which then only sizes the grid); scatter != 0: frame i's results go to record dframe_map[i] of dout; fade_chunk > 0 (with dnframes):
 // a workgroup evaluates fade_chunk of the fades, the chunks of a (logo, frame group) run side by side -- a handful of listed frames
 // is a latency problem (one workgroup walking every band for all fades), not a throughput one
 hipError_t launch_logo_eval_fused(hipStream_t st, int bits, const EvalLogoDev* dlogos, int nlogos, const EvalBand* dbands,
-                                  const float* dfades, int nfades, int fade0, const void* dY, const int* dframe_map,
-                                  long long frame_stride_elems, int pitch, int nframes, int G, float* dout, int out_frame_stride,
-                                  int take_abs, int plane_cap, const int* dnframes = nullptr, int scatter = 0, int fade_chunk = 0);
+                                  const float* dfades, int nfades, int fade0, const FrameBatch& luma, const int* dframe_map, int nframes, int G,
+                                  float* dout, int out_frame_stride, int take_abs, int plane_cap, const int* dnframes = nullptr, int scatter = 0,
+                                  int fade_chunk = 0);
 // eval_linear_kernels.hip
 hipError_t launch_logo_eval_linear(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
-                                   const float* dfades, int nfades, int fade0, const void* dY, const int* dframe_map,
-                                   long long frame_stride_elems, int pitch, int nframes, int G, float* dout, int out_frame_stride,
-                                   int take_abs, float bin_eps, int qlog2, int qcap, uint8_t* dforce);
+                                   const float* dfades, int nfades, int fade0, const FrameBatch& luma, const int* dframe_map, int nframes, int G,
+                                   float* dout, int out_frame_stride, int take_abs, float bin_eps, int qlog2, int qcap, uint8_t* dforce);
 // eval_pair_kernels.hip: fades {0, 1} of every logo, bit-exact
 hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
-                                 const void* dY, const int* dframe_map, long long frame_stride_elems, int pitch,
-                                 int nframes, int G, float* dout, int out_frame_stride, int take_abs, int ldexp_form);
+                                 const FrameBatch& luma, const int* dframe_map, int nframes, int G, float* dout, int out_frame_stride, int take_abs,
+                                 int ldexp_form);
 // Sentinel monitor of AMTGPU_ANALYZE_LINEAR_MONITORED: persistent per-analyzer device state.  max_abs_bits: the largest |linear - exact| over
 // every compared score as float bits (non-negative floats order like unsigned ints; NaN counts as +inf); tripped: a comparison failed (sticky
 // until re-armed); frames_checked: sentinel frames compared; batches_tripped: batches in which a comparison failed
@@ -212,7 +210,6 @@ hipError_t launch_analysis_sentinel_check(hipStream_t st, const float* drec, int
                                           MonitorState* dstate, int* host_flag, int epoch);
 // list[i] = i for i < n (the identity list of the gated whole-batch re-evaluation)
 hipError_t launch_analysis_iota(hipStream_t st, int* dlist, int n);
-hipError_t launch_rect_range_flag(hipStream_t st, const void* dY, long long frame_stride_elems, int pitch, int imgx, int imgy, int w, int h, int bits,
-                                  int nframes, uint8_t* dflag);
+hipError_t launch_rect_range_flag(hipStream_t st, const FrameBatch& luma, int imgx, int imgy, int w, int h, int bits, int nframes, uint8_t* dflag);
 
 } // namespace amt

@@ -170,6 +170,10 @@ void logofind_kernel(const uint8_t* __restrict__ Y, long long frame_stride, int 
     }
 }
 
+// logofind_msb_kernels.hip: launch_logofind's batches with b.shift != 0 (bits = the depth of the shifted samples, 9..16; shift = 16 - bits)
+struct FrameBatch;
+hipError_t launch_logofind_msb(hipStream_t st, int bits, const FrameBatch& b, int W, int H, int nframes, int num_cus, unsigned long long* dS1,
+                               unsigned long long* dSM);
 // the grid of a launch over nframes frames: tiles x frame slices
 struct LfGrid { int col_waves, tiles, slice_frames, slices; bool buf; };
 inline LfGrid logofind_grid(int pitch_elems, int W, int H, int nframes, int num_cus)

@@ -33,18 +33,20 @@ namespace amt {
 
 long long logofind_launch_cap(int bits) { return (long long)((2147483647LL) / (2LL * ((1LL << bits) - 1))); }
 
-hipError_t launch_logofind(hipStream_t st, int bits, const void* dY, long long frame_stride, int pitch_elems, int W, int H, int nframes,
-                           int num_cus, unsigned long long* dS1, unsigned long long* dSM)
+hipError_t launch_logofind(hipStream_t st, int bits, const FrameBatch& b, int W, int H, int nframes, int num_cus, unsigned long long* dS1,
+                           unsigned long long* dSM)
 {
     if (nframes <= 0) return hipSuccess;
+    if (b.shift) return launch_logofind_msb(st, bits, b, W, H, nframes, num_cus, dS1, dSM);
     if (nframes > logofind_launch_cap(bits)) return hipErrorInvalidValue;
     const int es = bits <= 8 ? 1 : 2;
-    if ((long long)H * pitch_elems * es >= (1LL << 31)) return hipErrorInvalidValue;      // 32-bit buffer offsets within a frame
-    const LfGrid g = logofind_grid(pitch_elems, W, H, nframes, num_cus);
+    if (b.es != es) return hipErrorInvalidValue;
+    if ((long long)H * b.pitchY * es >= (1LL << 31)) return hipErrorInvalidValue;      // 32-bit buffer offsets within a frame
+    const LfGrid g = logofind_grid(b.pitchY, W, H, nframes, num_cus);
     const bool buf = g.buf;
     dim3 grid((unsigned)g.tiles, (unsigned)g.slices), block(64);
 #define AMT_LF_LAUNCH(E, BF)                                                                                                   \
-    hipLaunchKernelGGL((logofind_kernel<E, BF, false>), grid, block, 0, st, (const uint8_t*)dY, frame_stride, pitch_elems * es, W, H, nframes, \
+    hipLaunchKernelGGL((logofind_kernel<E, BF, false>), grid, block, 0, st, (const uint8_t*)b.Y, b.strideY, b.pitchY * es, W, H, nframes, \
                        g.slice_frames, g.col_waves, dS1, dSM, 0)
     if (es == 1) { if (buf) AMT_LF_LAUNCH(1, true); else AMT_LF_LAUNCH(1, false); }
     else { if (buf) AMT_LF_LAUNCH(2, true); else AMT_LF_LAUNCH(2, false); }

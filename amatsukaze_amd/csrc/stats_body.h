@@ -289,7 +289,10 @@ void frame_stats_kernel(const uint8_t* __restrict__ Y, long long frame_stride /*
     }
 }
 
-// the grid and the kernel form of a launch over nframes frames of es-byte containers: what launch_frame_stats and launch_frame_stats_msb share
+// stats_msb_kernels.hip: launch_frame_stats's batches with b.shift != 0 (bits = the depth of the shifted samples, 9..15; shift = 16 - bits)
+struct FrameBatch;
+hipError_t launch_frame_stats_msb(hipStream_t st, int bits, const FrameBatch& b, int W, int H, const void* dprevY, int nframes, unsigned long long* dout);
+// the grid and the kernel form of a launch over nframes frames of es-byte containers: what the two launchers share
 struct StatGrid { int row_bytes, col_groups, gx, gy; bool buf, ragged, fits; };
 inline StatGrid stat_grid(int es, int pitch_elems, int W, int H, int nframes)
 {

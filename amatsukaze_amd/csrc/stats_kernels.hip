@@ -28,18 +28,19 @@
 
 namespace amt {
 
-hipError_t launch_frame_stats(hipStream_t st, int bits, const void* dY, long long frame_stride_bytes, int pitch_elems, int W,
-                              int H, const void* dprevY, int nframes, unsigned long long* dout)
+hipError_t launch_frame_stats(hipStream_t st, int bits, const FrameBatch& b, int W, int H, const void* dprevY, int nframes, unsigned long long* dout)
 {
     if (nframes <= 0) return hipSuccess;
+    if (b.shift) return launch_frame_stats_msb(st, bits, b, W, H, dprevY, nframes, dout);
     const int es = bits <= 8 ? 1 : 2;
-    const StatGrid g = stat_grid(es, pitch_elems, W, H, nframes);
+    if (b.es != es) return hipErrorInvalidValue;
+    const StatGrid g = stat_grid(es, b.pitchY, W, H, nframes);
     if (!g.fits) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(dout, 0, (size_t)nframes * kStatWords * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
     dim3 grid((unsigned)g.gx, (unsigned)g.gy), block(kStatThreads);
 #define AMT_STATS_LAUNCH(E, RG, BF)                                                                                                          \
-    hipLaunchKernelGGL((frame_stats_kernel<E, RG, BF, false>), grid, block, 0, st, (const uint8_t*)dY, frame_stride_bytes, pitch_elems * es, g.row_bytes, H, \
+    hipLaunchKernelGGL((frame_stats_kernel<E, RG, BF, false>), grid, block, 0, st, (const uint8_t*)b.Y, b.strideY, b.pitchY * es, g.row_bytes, H, \
                        (const uint8_t*)dprevY, nframes, g.col_groups, dout, 0)
     if (es == 1) { if (!g.buf) AMT_STATS_LAUNCH(1, true, false); else if (g.ragged) AMT_STATS_LAUNCH(1, true, true); else AMT_STATS_LAUNCH(1, false, true); }
     else { if (!g.buf) AMT_STATS_LAUNCH(2, true, false); else if (g.ragged) AMT_STATS_LAUNCH(2, true, true); else AMT_STATS_LAUNCH(2, false, true); }
