@@ -1081,3 +1081,27 @@ def kfm_render(ctx: Context, src: "DeviceSurfaces | DeviceClip", plan, dst: "Dev
         return
     ctx.check(ctx.lib.amtgpu_kfm_render(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), _p(pl), len(pl),
                                         int(thresh), C.byref(d)), "kfm_render")
+
+
+def temporal_nr(ctx: Context, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSurfaces | DeviceClip", distance=3, threshold=1, interlaced=False, src_first=0,
+                clip_frames=None, out_first=None, nout=None):
+    """Temporal noise reduction, the reference's TemporalNRFilter byte for byte (amtgpu_temporal_nr): per luma pixel
+    the mean of the window frames clamp(t - distance .. t + distance, 0, clip_frames - 1) whose |dY| + |dU| + |dV| against frame t is at
+    most threshold << (bits - 8).  The defaults are the server's KTemporalNR(3, 1).  src holds frames [src_first, src_first +
+    src.num_frames) of a clip of clip_frames frames (default: the batch ends the clip); output frames out_first .. out_first + nout - 1 go
+    to dst's frames 0 .. nout - 1 (default: every frame whose window lies in the batch).  Planar LSB clips of equal bits only;
+    interlaced picks the chroma row of interlaced 4:2:0 and needs height % 4 == 0.  Synchronises.  Returns (out_first, nout)"""
+    nsrc, d = src.num_frames, int(distance)
+    if clip_frames is None:
+        clip_frames = src_first + nsrc
+    if out_first is None:
+        out_first = src_first if src_first == 0 else src_first + d
+    if nout is None:
+        end = src_first + nsrc                       # one past the last output frame whose window the batch holds
+        nout = max(0, (end if end == clip_frames else end - d) - out_first)
+    if nout > dst.num_frames:
+        raise AmtError(f"temporal_nr: {nout} output frames, dst holds {dst.num_frames}")
+    s, t = _surfaces_ref(src), _surfaces_ref(dst)
+    ctx.check(ctx.lib.amtgpu_temporal_nr(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), int(out_first), int(nout),
+                                         d, int(threshold), 1 if interlaced else 0, C.byref(t)), "temporal_nr")
+    return int(out_first), int(nout)

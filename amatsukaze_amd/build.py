@@ -38,6 +38,8 @@ SOURCES = [
     "render_surface_kernels.hip",
     "render_adaptive_kernels.hip",
     "render_adaptive_surface_kernels.hip",
+    "amt_gpu_tnr.hip",
+    "temporal_nr_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

@@ -125,6 +125,23 @@ hipError_t launch_kfm_render_adaptive(hipStream_t st, const RenderArgs& a, const
 // launch_kfm_render_adaptive's
 hipError_t launch_kfm_render_adaptive_surfaces(hipStream_t st, const RenderArgs& a, int interleaved, int shift, const RenderAdaptiveEntry* dplan, int nout);
 
+// ---- temporal_nr_kernels.hip ----
+// The reference's TemporalNRFilter (VideoFilter.hpp:156-211) on planar LSB planes.  Output frame t (0 .. nout - 1) averages, per luma
+// pixel, the window frames min(max(first + t + k, lo), hi), k = -d .. d, that lie within thresh of the centre frame first + t; all frame
+// numbers are batch-local, lo / hi those of the clip's first and last frame (lo <= 0; the caller has checked that every window frame is
+// inside the batch)
+struct TemporalNRArgs {
+    const uint8_t *srcY, *srcU, *srcV; uint8_t *dstY, *dstU, *dstV;
+    long long src_strideY, src_strideUV, dst_strideY, dst_strideUV;  // bytes between frames
+    int src_pitchY, src_pitchUV, dst_pitchY, dst_pitchUV;            // bytes between rows
+    int W, H;                                                        // luma size in containers; both even, H % 4 == 0 when interlaced
+    int es, vec;                                                     // vec: temporal_nr_vec16 (lane_rule.h)
+    int d, thresh, interlaced;                                       // thresh: threshold << (bits - 8)
+    int first, lo, hi;
+};
+// One launch; none when nout <= 0
+hipError_t launch_temporal_nr(hipStream_t st, const TemporalNRArgs& a, int nout);
+
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 // Both take a luma batch of either alignment: b.shift != 0 (16-bit containers, shift = 16 - bits) runs the same sums on container >> shift,
 // `bits` then being the depth of the shifted samples (9..15 metrics, 9..16 finder): the instantiations of stats_msb_ / logofind_msb_kernels.hip.

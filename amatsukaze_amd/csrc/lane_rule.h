@@ -74,4 +74,12 @@ inline int render_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& d
     return lane_divides(16, srcY.bits() | srcUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
 }
 
+// temporal_nr_kernel: a lane takes 16 bytes of two luma rows and the 8 bytes of each chroma row under them, where every luma row starts
+// 16-byte aligned and every chroma row 8-byte aligned (a row's last containers go two luma columns at a time, so the row length is no
+// operand); otherwise it goes container by container
+inline int temporal_nr_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& dstY, const RowsAt& dstUV)
+{
+    return lane_divides(16, srcY.bits() | dstY.bits()) && lane_divides(8, srcUV.bits() | dstUV.bits()) ? 1 : 0;
+}
+
 } // namespace amt

@@ -719,6 +719,33 @@ int  amtgpu_kfm_render_deint(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int 
  * with one frame of halo on either side of a batch.  Synchronises */
 int  amtgpu_kfm_render_deint_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
                                       const AmtGpuRenderFrame* plan, int nout, int deint, int thresh, const AmtGpuSurfaces* dst);
+/* ---- temporal noise reduction: TemporalNRFilter (VideoFilter.hpp:27-212), the GUI's EnableTemporalNR, which the server turns into
+ *      KTemporalNR(3, 1) (Misc.cs:1425-1428), byte for byte on planar LSB planes.  An addition; the ABI version stays 5. ----
+ * src holds frames [src_first, src_first + nsrc) of a clip of clip_frames frames; width x height is the luma size, both even.  Output
+ * frames out_first .. out_first + nout - 1 go to dst's frames 0 .. nout - 1.  With d = temporal_distance, N = 2 d + 1,
+ * thresh = threshold << (bits - 8), T the container type (uint8_t at bits 8, uint16_t at 9..16; containers as stored, no masking to bits):
+ *   the window of output frame t is W_i = frame clamp(t + i - d, 0, clip_frames - 1), i = 0 .. N - 1, a clamped frame counting as often
+ *   as it appears; C = W_d = frame t.  Per luma pixel (x, y), cx = x >> 1, cy = interlaced ? (((y >> 1) & ~1) | (y & 1)) : (y >> 1):
+ *   diff_i = |C.Y[y][x] - W_i.Y[y][x]| + |C.U[cy][cx] - W_i.U[cy][cx]| + |C.V[cy][cx] - W_i.V[cy][cx]|; W_i passes where diff_i <= thresh;
+ *   count = the passing i (the centre always passes); factor = 1.f / (float)count, correctly rounded;
+ *   dY = 0.5f, and for i = 0 .. N - 1 in order, where W_i passes, dY += factor * (float)W_i.Y[y][x] -- the product rounded to float, then
+ *   the sum, no fused operation; dU, dV likewise from the pixel's chroma samples;  dst.Y[y][x] = (T)dY by truncation;
+ *   where x is even and ((interlaced ? y >> 1 : y) & 1) == 0 also dst.U[cy][cx] = (T)dU and dst.V[cy][cx] = (T)dV: a chroma sample is
+ *   filtered with the pass mask of ONE luma pixel, (2 cx, 2 cy) progressive and (2 cx, 2 (cy & ~1) + (cy & 1)) interlaced.
+ * Every container of the nout output frames is written; none is copied from the source.  The reference's onFrame / finish stream gives
+ * exactly these windows for clip_frames >= 2 d (and clip_frames == 1 with d == 0); for shorter clips it drops frames, which this call
+ * does not mirror: the clamp rule holds for every length.
+ * The bytes depend on the clip and the parameters alone: a clip filtered in batches, each with d frames of halo wherever the clip has
+ * them, gives the bytes of one call.
+ * Returns 0 with a message on ctx, and launches nothing: temporal_distance outside 0..63; threshold outside 0..32767; bits outside 8..16;
+ * src and dst of different bits; a descriptor that is interleaved or MSB-aligned (planar LSB only); width or height odd; interlaced with
+ * height % 4 != 0 (the reference reads chroma row height / 2 there); a pitch below the row; a negative frame stride; a window frame
+ * outside the batch; an output frame outside the clip; destination frames that overlap each other in a plane; a destination plane whose
+ * byte range (first byte of frame 0 .. last byte of frame nout - 1) overlaps a source plane's.  nout == 0 returns 1.
+ * Reads nothing outside a row's width (width / 2 in chroma) containers of a source row, writes nothing outside them in a destination row.
+ * Synchronises, as amtgpu_kfm_render does: dst is complete when the call returns */
+int  amtgpu_temporal_nr(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
+                        int out_first, int nout, int temporal_distance, int threshold, int interlaced, const AmtGpuSurfaces* dst);
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
