@@ -688,7 +688,9 @@ static AmtGpuAnalyze* analyze_new(AmtGpuContext* c, LogoPlanes logo, float maskr
     an->ctx = c;
     an->logo = std::move(logo);
     const LogoPlanes& P = an->logo;
-    if (P.h < 12 || P.w < 6) throw std::runtime_error("logo too small");
+    // (any even w x h, as the reference: a logo too small for a 5 x 5 window -- or whose field logos are -- has no mask pixel there, no
+    //  band is staged for it and its records are 0 / blackScore = 0 / 0; the tile kernels have their own limits, EvalEngine::tiles_usable)
+    if (P.h < 2 || P.w < 2) throw std::runtime_error("logo too small");          // (a field logo needs a row)
     std::vector<EvalLogoSpec> specs(3);
     for (int kind = 0; kind < 3; ++kind) {
         EvalLogoSpec& S = specs[kind];

@@ -333,8 +333,18 @@ void EvalEngine::ensure_tiles()
             fit_response(&T.resp[(size_t)m * 32], pq[s].x, pq[s].y);
             spos[s] = T.pos[m];
             const float* k = &T.kernels[(size_t)m * 25];
+            // The linear kernel multiplies the window mean by the sum of the taps.  The taps nearly cancel, so a sum formed in fp32 is off by
+            // a few ulps of its PARTIAL sums; times the mean of a 16-bit clip (tens of thousands) that was the kernel's largest error on a
+            // term that is not clamped: 4.4e-5 of a score of an 8 x 10 logo, sixty times the reference's own rounding.  Taps of a
+            // logo span far fewer than 29 binary orders, so the 25 of them add up exactly in double; the sum is rounded once.  (The scan keeps the fp32 sum stage4_eligible has checked.)
             float ksum = 0.0f;
-            for (int t = 0; t < 25; ++t) ksum += k[t];
+            if (fades_.size() == 2) {
+                for (int t = 0; t < 25; ++t) ksum += k[t];
+            } else {
+                double ks = 0.0;
+                for (int t = 0; t < 25; ++t) ks += (double)k[t];
+                ksum = (float)ks;
+            }
             for (int j = 0; j < 13; ++j) kp[(size_t)j * ns + s] = float2{kscale * k[2 * j], kscale * (2 * j + 1 < 25 ? k[2 * j + 1] : ksum)};    // [12].y = sum of the taps (linear kernel: kscale is 1)
             for (int c = 0; c < kNumBins; ++c)
                 sc[(size_t)c * ns + s] = float2{T.scales[((size_t)m * 32 + c) * 2], T.scales[((size_t)m * 32 + c) * 2 + 1]};
@@ -433,7 +443,8 @@ void EvalEngine::ensure_linear()
             }
             eformula += devmax;
             // (+ 24 u v sum|k|: the host's fp32 sum of the 25 taps that multiplies the mean, kp[12].y in ensure_tiles, carries up to
-            // 24 roundings of partial sums <= sum|k|, times a mean <= v)
+            // 24 roundings of partial sums <= sum|k|, times a mean <= v.  ensure_tiles forms that sum in double by now and rounds it once;
+            // the allowance stays: the bound may be loose, never tight)
             ecorr += smax * sk * (58.0 + 24.0);
             tsum += s2max;
         }
