@@ -1089,7 +1089,10 @@ def temporal_nr(ctx: Context, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSu
     the mean of the window frames clamp(t - distance .. t + distance, 0, clip_frames - 1) whose |dY| + |dU| + |dV| against frame t is at
     most threshold << (bits - 8).  The defaults are the server's KTemporalNR(3, 1).  src holds frames [src_first, src_first +
     src.num_frames) of a clip of clip_frames frames (default: the batch ends the clip); output frames out_first .. out_first + nout - 1 go
-    to dst's frames 0 .. nout - 1 (default: every frame whose window lies in the batch).  Planar LSB clips of equal bits only;
+    to dst's frames 0 .. nout - 1 (default: every frame whose window lies in the batch).  src and dst are planar clips or decoder
+    surfaces IN KIND -- equal bits, interleaved and msb: NV12 in, NV12 out; P010 in, P010 out (V = None when interleaved); no layout is
+    converted.  Interleaved or MSB-aligned surfaces go through amtgpu_temporal_nr_surfaces: the rule runs on samples (container >>
+    (16 - bits) when msb, which the threshold counts), and every output container is the result << (16 - bits), its low bits zero.
     interlaced picks the chroma row of interlaced 4:2:0 and needs height % 4 == 0.  Synchronises.  Returns (out_first, nout)"""
     nsrc, d = src.num_frames, int(distance)
     if clip_frames is None:
@@ -1102,6 +1105,7 @@ def temporal_nr(ctx: Context, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSu
     if nout > dst.num_frames:
         raise AmtError(f"temporal_nr: {nout} output frames, dst holds {dst.num_frames}")
     s, t = _surfaces_ref(src), _surfaces_ref(dst)
-    ctx.check(ctx.lib.amtgpu_temporal_nr(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), int(out_first), int(nout),
-                                         d, int(threshold), 1 if interlaced else 0, C.byref(t)), "temporal_nr")
+    call = ctx.lib.amtgpu_temporal_nr_surfaces if s.interleaved or s.msb_aligned else ctx.lib.amtgpu_temporal_nr
+    ctx.check(call(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), int(out_first), int(nout),
+                   d, int(threshold), 1 if interlaced else 0, C.byref(t)), "temporal_nr")
     return int(out_first), int(nout)

@@ -181,6 +181,7 @@ SIGNATURES = {
     "amtgpu_kfm_render_deint": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p]),
     "amtgpu_kfm_render_deint_surfaces": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p]),
     "amtgpu_temporal_nr": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "amtgpu_temporal_nr_surfaces": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "amtgpu_cm_write_chapter_exe": (c_i, [c_p, c_i, c_i, c_s]),
     "amtgpu_audiolevels_create": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i64]),
     "amtgpu_audiolevels_destroy": (None, [c_p]),

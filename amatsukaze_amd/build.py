@@ -40,6 +40,7 @@ SOURCES = [
     "render_adaptive_surface_kernels.hip",
     "amt_gpu_tnr.hip",
     "temporal_nr_kernels.hip",
+    "temporal_nr_surface_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

@@ -141,6 +141,11 @@ struct TemporalNRArgs {
 };
 // One launch; none when nout <= 0
 hipError_t launch_temporal_nr(hipStream_t st, const TemporalNRArgs& a, int nout);
+// temporal_nr_surface_kernels.hip: the same frames on decoder surfaces, source and destination in kind (planar LSB planes -- neither
+// interleaved nor shift -- are refused: they are the launcher's above).  interleaved: srcU / dstU are the UV planes, U the even and V the
+// odd container of a row, srcV / dstV unused.  shift != 0 (es 2): MSB-aligned containers; the rule runs on container >> shift, a.thresh
+// counts samples, and every container is stored as result << shift.  a.vec: temporal_nr_surface_vec16 (lane_rule.h)
+hipError_t launch_temporal_nr_surfaces(hipStream_t st, const TemporalNRArgs& a, int interleaved, int shift, int nout);
 
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 // Both take a luma batch of either alignment: b.shift != 0 (16-bit containers, shift = 16 - bits) runs the same sums on container >> shift,

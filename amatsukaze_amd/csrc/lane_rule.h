@@ -82,4 +82,11 @@ inline int temporal_nr_vec16(const RowsAt& srcY, const RowsAt& srcUV, const Rows
     return lane_divides(16, srcY.bits() | dstY.bits()) && lane_divides(8, srcUV.bits() | dstUV.bits()) ? 1 : 0;
 }
 
+// temporal_nr_surfaces_kernel: the same lane on decoder surfaces.  Interleaved, the chroma under a lane's 16 luma bytes is one 16-byte
+// run of the UV row, so every UV row starts 16-byte aligned as well (base2 is 0: there is no V plane); planar, the rule above
+inline int temporal_nr_surface_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& dstY, const RowsAt& dstUV, int interleaved)
+{
+    return lane_divides(16, srcY.bits() | dstY.bits()) && lane_divides(interleaved ? 16 : 8, srcUV.bits() | dstUV.bits()) ? 1 : 0;
+}
+
 } // namespace amt

@@ -746,6 +746,19 @@ int  amtgpu_kfm_render_deint_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* 
  * Synchronises, as amtgpu_kfm_render does: dst is complete when the call returns */
 int  amtgpu_temporal_nr(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
                         int out_first, int nout, int temporal_distance, int threshold, int interlaced, const AmtGpuSurfaces* dst);
+/* The same filter on decoder surfaces where they lie, source and destination IN KIND -- equal bits, equal interleaved, equal MSB shift:
+ * NV12 (8 bits, interleaved), P010 / P012 / P016 (interleaved, MSB-aligned), interleaved LSB at 9..16 bits, planar MSB at 9..16 bits;
+ * a planar LSB pair runs amtgpu_temporal_nr's kernel unchanged.  An addition; the ABI version stays 5.  The parameters are
+ * amtgpu_temporal_nr's.  The rule is the one above, stated on samples: sample = container >> s, s = msb_aligned ? 16 - bits : 0;
+ * thresh = threshold << (bits - 8) counts samples; U is the even and V the odd container of an interleaved UV row (pitchUV >= width).
+ * Every container of the nout output frames is written as result << s, its low bits zero; nothing is copied from the source, so the
+ * source's low bits never survive.  So dst >> s, de-interleaved, equals amtgpu_temporal_nr of src >> s, de-interleaved, byte for byte,
+ * whatever sits in the source's low bits and however the clip is cut into batches with temporal_distance frames of halo.
+ * Every refusal of amtgpu_temporal_nr is kept, with its wording, but "planar LSB only": a mixed pair is refused instead ("not in kind
+ * ... converts no layouts"); an interleaved descriptor needs pitchUV >= width, and the overlap checks cover its two planes with UV rows
+ * of width containers.  Synchronises */
+int  amtgpu_temporal_nr_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
+                                 int out_first, int nout, int temporal_distance, int threshold, int interlaced, const AmtGpuSurfaces* dst);
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
