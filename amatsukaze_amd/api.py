@@ -1109,3 +1109,55 @@ def temporal_nr(ctx: Context, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSu
     ctx.check(call(ctx.h, C.byref(s), int(src_first), nsrc, int(clip_frames), int(src.width), int(src.height), int(out_first), int(nout),
                    d, int(threshold), 1 if interlaced else 0, C.byref(t)), "temporal_nr")
     return int(out_first), int(nout)
+
+
+RESIZE_KERNELS = {"blackman": 0, "lanczos": 1, "bilinear": 2}                                                       # AMTGPU_RESIZE_*
+
+
+class Resizer:
+    """Blackman / Lanczos / bilinear resize of planar clips in HBM (amtgpu_resize_*): the BlackmanResize(w, h) in
+    front of KTemporalNR in the server's chain, integer and exact -- horizontal stage first into an intermediate the object owns, then
+    vertical; every plane on its own, chroma (w/2, h/2) -> (w/2, h/2) with the same kernel.  src_size and dst_size are (width, height)
+    of the luma plane, all four even.  taps None: the kernel's default (blackman 4, lanczos 3).  max_scratch_bytes bounds the
+    intermediate, not the clip: a run works through its frames in rounds (None: the header's default, 64 MiB)."""
+
+    def __init__(self, ctx: Context, src_size, dst_size, bits, kernel="blackman", taps=None, max_scratch_bytes=None):
+        if kernel not in RESIZE_KERNELS:
+            raise AmtError(f"Resizer: kernel is one of {sorted(RESIZE_KERNELS)}, not {kernel!r}")
+        self.ctx, self.bits, self.kernel = ctx, int(bits), kernel
+        (self.src_w, self.src_h), (self.dst_w, self.dst_h) = (int(v) for v in src_size), (int(v) for v in dst_size)
+        self.h = ctx.lib.amtgpu_resize_create(ctx.h, self.src_w, self.src_h, self.dst_w, self.dst_h, self.bits, RESIZE_KERNELS[kernel],
+                                              0 if taps is None else int(taps), 0 if max_scratch_bytes is None else int(max_scratch_bytes))
+        ctx.check(self.h, "Resizer")
+
+    def run(self, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSurfaces | DeviceClip"):
+        """frames 0 .. src.num_frames - 1 of src into the same frames of dst; planar LSB planes of the resizer's bits.  Synchronises.
+        Returns the number of frames"""
+        n = src.num_frames
+        if n > dst.num_frames:
+            raise AmtError(f"Resizer: {n} frames, dst holds {dst.num_frames}")
+        if (int(src.width), int(src.height)) != (self.src_w, self.src_h) or (int(dst.width), int(dst.height)) != (self.dst_w, self.dst_h):
+            raise AmtError(f"Resizer: made for {self.src_w}x{self.src_h} -> {self.dst_w}x{self.dst_h}, got {src.width}x{src.height} -> {dst.width}x{dst.height}")
+        s, t = _surfaces_ref(src), _surfaces_ref(dst)
+        self.ctx.check(self.ctx.lib.amtgpu_resize_run(self.h, C.byref(s), C.byref(t), n), "Resizer")
+        return n
+
+    def program(self, plane, axis):
+        """(K, start[D], coeff[D][K]) of plane 0 (luma) / 1 (chroma), axis 0 (horizontal) / 1 (vertical), as numpy int32"""
+        k = C.c_int()
+        self.ctx.check(self.ctx.lib.amtgpu_resize_get_program(self.h, int(plane), int(axis), C.byref(k), None, None), "Resizer")
+        D = ((self.dst_h if axis else self.dst_w) >> 1) if plane else (self.dst_h if axis else self.dst_w)
+        start, coeff = np.zeros(D, np.int32), np.zeros((D, k.value), np.int32)
+        self.ctx.check(self.ctx.lib.amtgpu_resize_get_program(self.h, int(plane), int(axis), C.byref(k), _p(start), _p(coeff)), "Resizer")
+        return k.value, start, coeff
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.amtgpu_resize_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -41,6 +41,9 @@ SOURCES = [
     "amt_gpu_tnr.hip",
     "temporal_nr_kernels.hip",
     "temporal_nr_surface_kernels.hip",
+    "amt_gpu_resize.hip",
+    "resize_kernels.hip",
+    "resize_plan.cpp",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

@@ -1,0 +1,196 @@
+// amt_gpu_resize.hip -- C ABI part 7: the resize in front of the temporal NR in the server's chain (BlackmanResize, Misc.cs:1423) over
+// frames resident in HBM ("parity unpinned").  The object holds the four programs (luma and chroma, horizontal and
+// vertical: resize_plan.hpp) on the host and on the device, and the intermediate of the horizontal stage, which is bounded by
+// max_scratch_bytes and not by the clip: a call works through its frames in rounds.
+#include "build_knobs.h"
+#include "../../include/amt_gpu.h"
+
+#include <memory>
+#include <string>
+
+#include "api_common.hpp"
+#include "resize_plan.hpp"
+
+using namespace amt;
+
+struct AmtGpuResize {
+    AmtGpuContext* ctx;
+    int src_w, src_h, dst_w, dst_h, bits;
+    ResizeProgram prog[2][2];                  // [plane: luma, chroma][axis: horizontal, vertical]
+    DevBuf<int> dTables;                       // the four programs' start and coeff, one behind the other
+    ResizeProgramDev dprog[2][2];
+    int cpw[2];                                // resize_columns_per_wave of the two horizontal programs
+    int mid_pitch[2];                          // bytes between the intermediate's rows: the row rounded up to 16
+    size_t mid_plane[2], mid_frame;            // bytes of one frame's luma / one chroma plane of the intermediate, and of all three
+    int round_frames;                          // frames whose intermediates fit max_scratch_bytes
+    DevBuf<uint8_t> dMid;
+};
+
+namespace {
+const char* const kWho = "[Resize]";
+
+[[noreturn]] void refuse(const std::string& what) { throw std::runtime_error(std::string(kWho) + " " + what); }
+
+FrameBatch resize_surfaces(const AmtGpuSurfaces* s, const char* which, int width, int bits)
+{
+    const FrameBatch b = surface_batch(s, kWho);
+    if (s->interleaved || s->msb_aligned) refuse(std::string(which) + ": planar, LSB-aligned planes only (interleaved and MSB-aligned surfaces are refused)");
+    if (s->bits != bits) refuse(std::string(which) + ": " + std::to_string(s->bits) + " bits, the resizer was created for " + std::to_string(bits));
+    if (b.strideY < 0 || b.strideUV < 0) refuse(std::string(which) + ": negative frame stride");
+    if (b.pitchY < width || b.pitchUV < width / 2) refuse(std::string(which) + ": pitch smaller than the row");
+    return b;
+}
+
+// [first byte, one past the last byte) that n frames of a plane span
+struct Span { uintptr_t lo, hi; };
+Span plane_span(const void* p, long long stride, long long pitch_bytes, int row_bytes, int rows, int n)
+{
+    const uintptr_t lo = (uintptr_t)p;
+    return Span{lo, lo + (uintptr_t)(n - 1) * (uintptr_t)stride + (uintptr_t)(rows - 1) * (uintptr_t)pitch_bytes + (uintptr_t)row_bytes};
+}
+
+AmtGpuResize* resize_create(AmtGpuContext* c, int src_w, int src_h, int dst_w, int dst_h, int bits, int kernel, int taps, int64_t max_scratch_bytes)
+{
+    if (bits < 8 || bits > 16) refuse("bits must be 8..16");
+    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0 || ((src_w | src_h | dst_w | dst_h) & 1)) refuse("all four sizes must be even and positive (4:2:0)");
+    if (src_w > 32768 || src_h > 32768 || dst_w > 32768 || dst_h > 32768) refuse("sizes above 32768 are not supported");
+    if (kernel != AMTGPU_RESIZE_BLACKMAN && kernel != AMTGPU_RESIZE_LANCZOS && kernel != AMTGPU_RESIZE_BILINEAR)
+        refuse("kernel must be AMTGPU_RESIZE_BLACKMAN, _LANCZOS or _BILINEAR");
+    if (taps > 64) refuse("taps must be at most 64");
+    if (max_scratch_bytes <= 0) max_scratch_bytes = AMTGPU_RESIZE_DEFAULT_SCRATCH_BYTES;
+    std::unique_ptr<AmtGpuResize> r(new AmtGpuResize{});
+    r->ctx = c; r->src_w = src_w; r->src_h = src_h; r->dst_w = dst_w; r->dst_h = dst_h; r->bits = bits;
+    const int es = sample_bytes(bits);
+    std::vector<int> tables;
+    size_t at[2][2][2];
+    for (int p = 0; p < 2; ++p)
+        for (int ax = 0; ax < 2; ++ax) {
+            const int S = (ax ? src_h : src_w) >> p, D = (ax ? dst_h : dst_w) >> p;
+            ResizeProgram& g = r->prog[p][ax];
+            g = resize_program(S, D, kernel, taps);
+            if (!resize_program_fits_int32(g, bits))
+                refuse(std::string("the ") + (p ? "chroma" : "luma") + (ax ? " vertical" : " horizontal") + " program's sums leave the int32 accumulator at " +
+                       std::to_string(bits) + " bits");
+            at[p][ax][0] = tables.size(); tables.insert(tables.end(), g.start.begin(), g.start.end());
+            at[p][ax][1] = tables.size(); tables.insert(tables.end(), g.coeff.begin(), g.coeff.end());
+        }
+    for (int p = 0; p < 2; ++p) {
+        const ResizeProgram& g = r->prog[p][0];
+        r->cpw[p] = resize_columns_per_wave(g.start.data(), g.D, g.K, es);
+        if (!r->cpw[p])
+            refuse("the horizontal window of " + std::to_string(g.K) + " samples does not fit a wave's staging region (" +
+                   std::to_string((kResizeRegionBytes - kResizeRegionSlack) / es) + " samples): the ratio is too small");
+        r->mid_pitch[p] = ((dst_w >> p) * es + 15) & ~15;
+        r->mid_plane[p] = (size_t)r->mid_pitch[p] * (size_t)(src_h >> p);
+    }
+    r->mid_frame = r->mid_plane[0] + 2 * r->mid_plane[1];
+    if ((uint64_t)max_scratch_bytes < r->mid_frame)
+        refuse("max_scratch_bytes " + std::to_string(max_scratch_bytes) + " is below one frame's intermediate of " + std::to_string(r->mid_frame) + " bytes");
+    r->round_frames = (int)std::min<uint64_t>((uint64_t)max_scratch_bytes / r->mid_frame, 65535);
+    c->bind();
+    r->dTables.upload(tables, c->stream);
+    for (int p = 0; p < 2; ++p)
+        for (int ax = 0; ax < 2; ++ax) {
+            const ResizeProgram& g = r->prog[p][ax];
+            r->dprog[p][ax] = ResizeProgramDev{r->dTables.get() + at[p][ax][0], r->dTables.get() + at[p][ax][1], g.S, g.D, g.K, 0};
+        }
+    return r.release();
+}
+
+void resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes)
+{
+    AmtGpuContext* c = r->ctx;
+    if (nframes < 0) refuse("negative frame count");
+    if (nframes == 0) return;
+    const FrameBatch s = resize_surfaces(src, "source", r->src_w, r->bits), t = resize_surfaces(dst, "destination", r->dst_w, r->bits);
+    const int es = s.es;
+    struct Geometry { int w, h; };
+    const Geometry sg[2] = {{r->src_w, r->src_h}, {r->src_w / 2, r->src_h / 2}}, dg[2] = {{r->dst_w, r->dst_h}, {r->dst_w / 2, r->dst_h / 2}};
+    const long long s_stride[2] = {s.strideY, s.strideUV}, t_stride[2] = {t.strideY, t.strideUV};
+    const long long s_pitch[2] = {(long long)s.pitchY * es, (long long)s.pitchUV * es}, t_pitch[2] = {(long long)t.pitchY * es, (long long)t.pitchUV * es};
+    if (s_pitch[0] > INT32_MAX || s_pitch[1] > INT32_MAX || t_pitch[0] > INT32_MAX || t_pitch[1] > INT32_MAX) refuse("pitch above 2 GiB");
+    const void* const sp[3] = {s.Y, s.U, s.V};
+    const void* const tp[3] = {t.Y, t.U, t.V};
+    // destination frames must not overlap each other, and no destination plane's span may touch a source plane's
+    for (int k = 0; k < 2; ++k)
+        if (nframes > 1 && t_stride[k] < (long long)(dg[k].h - 1) * t_pitch[k] + (long long)dg[k].w * es) refuse("destination frames overlap each other");
+    Span sspan[3], dspan[3];
+    for (int p = 0; p < 3; ++p) {
+        const int k = p ? 1 : 0;
+        sspan[p] = plane_span(sp[p], s_stride[k], s_pitch[k], sg[k].w * es, sg[k].h, nframes);
+        dspan[p] = plane_span(tp[p], t_stride[k], t_pitch[k], dg[k].w * es, dg[k].h, nframes);
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place resize)");
+
+    c->bind();
+    const int round = std::min(r->round_frames, nframes);
+    const size_t need = r->mid_frame * (size_t)round;
+    if (r->dMid.size() < need) r->dMid.alloc(need);      // (hipFree waits for the kernels that still use the old intermediate)
+    // one round's intermediate: [round] luma planes, then [round] U planes, then [round] V planes
+    uint8_t* const mid[3] = {r->dMid.get(), r->dMid.get() + r->mid_plane[0] * round, r->dMid.get() + (r->mid_plane[0] + r->mid_plane[1]) * round};
+    const RowsAt srcY{lane_addr(s.Y), 0, s_stride[0], s_pitch[0]}, srcUV{lane_addr(s.U), lane_addr(s.V), s_stride[1], s_pitch[1]};
+    const RowsAt dstY{lane_addr(t.Y), 0, t_stride[0], t_pitch[0]}, dstUV{lane_addr(t.U), lane_addr(t.V), t_stride[1], t_pitch[1]};
+    const RowsAt midY{lane_addr(mid[0]), 0, (long long)r->mid_plane[0], r->mid_pitch[0]}, midUV{lane_addr(mid[1]), lane_addr(mid[2]), (long long)r->mid_plane[1], r->mid_pitch[1]};
+    ResizeStageArgs h{}, v{};
+    h.es = v.es = es;
+    h.maxv = v.maxv = (1 << r->bits) - 1;
+    h.vec = v.vec = resize_vec16(srcY, srcUV, midY, midUV, dstY, dstUV);
+    for (int k = 0; k < 2; ++k) {
+        h.prog[k] = r->dprog[k][0]; v.prog[k] = r->dprog[k][1];
+        h.lines[k] = sg[k].h; v.lines[k] = dg[k].w;
+        h.cpw[k] = r->cpw[k]; v.cpw[k] = 0;
+    }
+    for (int first = 0; first < nframes; first += round) {
+        const int n = std::min(round, nframes - first);
+        for (int p = 0; p < 3; ++p) {
+            const int k = p ? 1 : 0;
+            h.plane[p] = ResizePlaneArgs{(const uint8_t*)sp[p] + (long long)first * s_stride[k], mid[p], s_stride[k], (long long)r->mid_plane[k], (int)s_pitch[k], r->mid_pitch[k]};
+            v.plane[p] = ResizePlaneArgs{mid[p], (uint8_t*)tp[p] + (long long)first * t_stride[k], (long long)r->mid_plane[k], t_stride[k], r->mid_pitch[k], (int)t_pitch[k]};
+        }
+        const int s1 = c->prof_begin("resize_h_kernel");
+        AMT_HIP(launch_resize_h(c->stream, h, n));
+        c->prof_end(s1);
+        const int s2 = c->prof_begin("resize_v_kernel");
+        AMT_HIP(launch_resize_v(c->stream, v, n));
+        c->prof_end(s2);
+    }
+    AMT_HIP(hipStreamSynchronize(c->stream));            // as amtgpu_temporal_nr: dst is ready when the call returns
+}
+
+void resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int* start, int* coeff)
+{
+    if (plane < 0 || plane > 1 || axis < 0 || axis > 1) refuse("plane is 0 (luma) or 1 (chroma), axis 0 (horizontal) or 1 (vertical)");
+    const ResizeProgram& g = r->prog[plane][axis];
+    if (K) *K = g.K;
+    if (start) std::copy(g.start.begin(), g.start.end(), start);
+    if (coeff) std::copy(g.coeff.begin(), g.coeff.end(), coeff);
+}
+} // namespace
+
+extern "C" {
+
+AmtGpuResize* amtgpu_resize_create(AmtGpuContext* c, int src_w, int src_h, int dst_w, int dst_h, int bits, int kernel, int taps, int64_t max_scratch_bytes)
+{
+    if (!c) return nullptr;
+    AmtGpuResize* r = nullptr;
+    guard(c, [&] { r = resize_create(c, src_w, src_h, dst_w, dst_h, bits, kernel, taps, max_scratch_bytes); });
+    return r;
+}
+
+void amtgpu_resize_destroy(AmtGpuResize* r) { delete r; }
+
+int amtgpu_resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes)
+{
+    if (!r) return 0;
+    return guard(r->ctx, [&] { resize_run(r, src, dst, nframes); });
+}
+
+int amtgpu_resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int* start, int* coeff)
+{
+    if (!r) return 0;
+    return guard(r->ctx, [&] { resize_get_program(r, plane, axis, K, start, coeff); });
+}
+
+} // extern "C"

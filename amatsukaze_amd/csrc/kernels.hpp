@@ -147,6 +147,35 @@ hipError_t launch_temporal_nr(hipStream_t st, const TemporalNRArgs& a, int nout)
 // counts samples, and every container is stored as result << shift.  a.vec: temporal_nr_surface_vec16 (lane_rule.h)
 hipError_t launch_temporal_nr_surfaces(hipStream_t st, const TemporalNRArgs& a, int interleaved, int shift, int nout);
 
+// ---- resize_kernels.hip ----
+// The resize of DESIGN.md section 6e on planar LSB planes: two stages, horizontal into the caller's intermediate, then vertical, one
+// launch each for luma and both chroma planes of all nframes frames.  A stage resamples the axis its programs describe
+// (resize_plan.hpp, on the device): out[i] = clamp((sum_j coeff[i * K + j] * s[start[i] + j] + 8192) >> 14, 0, maxv), int32 throughout.
+struct ResizeProgramDev { const int* start; const int* coeff; int S, D, K, pad_; };
+struct ResizePlaneArgs {
+    const uint8_t* src; uint8_t* dst;
+    long long src_stride, dst_stride;          // bytes between frames
+    int src_pitch, dst_pitch;                  // bytes between rows
+};
+constexpr int kResizeWaves = 4;                // waves of a workgroup; each works on its own
+constexpr int kResizeRegionBytes = 2048;       // LDS of one wave of the horizontal stage: the source span of its run of output columns
+constexpr int kResizeRegionSlack = 48;         // ... less the bytes in front of an aligned-down span (15) and behind it for zero taps (16 samples)
+constexpr int kResizeRows = 16;                // rows a wave of the horizontal stage walks with its coefficients in registers
+struct ResizeStageArgs {
+    ResizePlaneArgs plane[3];                  // Y, U, V
+    ResizeProgramDev prog[2];                  // luma, chroma: the axis this stage resamples
+    int lines[2];                              // luma, chroma: the lines the stage resamples -- rows of the source (horizontal: its height),
+                                               // columns of the intermediate (vertical: the destination's width)
+    int cpw[2];                                // horizontal: output columns of a wave's run, 1..64 (resize_columns_per_wave)
+    int es, vec, maxv;                         // vec: resize_vec16 (lane_rule.h)
+};
+// The largest run of output columns (64 at the most) whose source span, start[last] + K - start[first], fits a wave's LDS region for
+// every run of the row; 0: not even one column's window fits (the caller refuses)
+int resize_columns_per_wave(const int* start, int D, int K, int es);
+// One launch each; none when nframes <= 0.  a.plane[].src of the vertical stage is the horizontal stage's dst
+hipError_t launch_resize_h(hipStream_t st, const ResizeStageArgs& a, int nframes);
+hipError_t launch_resize_v(hipStream_t st, const ResizeStageArgs& a, int nframes);
+
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 // Both take a luma batch of either alignment: b.shift != 0 (16-bit containers, shift = 16 - bits) runs the same sums on container >> shift,
 // `bits` then being the depth of the shifted samples (9..15 metrics, 9..16 finder): the instantiations of stats_msb_ / logofind_msb_kernels.hip.

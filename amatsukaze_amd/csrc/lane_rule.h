@@ -89,4 +89,13 @@ inline int temporal_nr_surface_vec16(const RowsAt& srcY, const RowsAt& srcUV, co
     return lane_divides(16, srcY.bits() | dstY.bits()) && lane_divides(interleaved ? 16 : 8, srcUV.bits() | dstUV.bits()) ? 1 : 0;
 }
 
+// resize_h_kernel / resize_v_kernel: every plane goes on its own, so chroma rows are held to what luma rows are.  The horizontal stage
+// stages a wave's source span with aligned 16-byte loads and the vertical stage gives a lane 16 bytes of an output row and of each
+// intermediate row under it, where every row of the source, of the intermediate (`mid`, the object's own) and of the destination starts
+// 16-byte aligned (a row's last containers go narrower, so the row length is no operand); otherwise both go container by container
+inline int resize_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& midY, const RowsAt& midUV, const RowsAt& dstY, const RowsAt& dstUV)
+{
+    return lane_divides(16, srcY.bits() | srcUV.bits() | midY.bits() | midUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
+}
+
 } // namespace amt

@@ -759,6 +759,49 @@ int  amtgpu_temporal_nr(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_f
  * of width containers.  Synchronises */
 int  amtgpu_temporal_nr_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
                                  int out_first, int nout, int temporal_distance, int threshold, int interlaced, const AmtGpuSurfaces* dst);
+
+/* ---- resize: the BlackmanResize(w, h) in front of KTemporalNR in the server's chain (Misc.cs:1423; the GUI's "resize" checkbox), on
+ *      planar LSB planes in HBM.  Self-specified, "parity unpinned" (BlackmanResize is a built-in of the AviSynth host; its arithmetic
+ *      is not in the reference tree): integer and exact, so the bytes are those of the rule below wherever it
+ *      runs.  An addition; the ABI version stays 5. ----
+ * One axis, S source samples to D destination samples, kernel k with `taps`, everything in double on the host:
+ *   scale = D / S, fstep = min(scale, 1), support = taps / fstep, K0 = ceil(2 * support), K = min(K0, S);
+ *   k(x) = 0 for |x| >= taps, 1 at 0, else with px = pi |x|:  blackman (default taps 4) sin(px)/px * (0.42 + 0.5 cos(px/taps) + 0.08 cos(2 px/taps));
+ *   lanczos (default taps 3) sin(px)/px * sin(px/taps)/(px/taps);  bilinear max(0, 1 - |x|), taps 1.
+ *   Output sample i: c = (i + 0.5) / scale - 0.5, lo = floor(c - support) + 1; for p = lo .. lo + K0 - 1 the weight k((p - c) * fstep) is
+ *   added to position clamp(p, 0, S - 1) (the edge sample replicated, folded on the host); the weights are divided by their sum; each
+ *   becomes C = floor(w * 16384 + 0.5); the residual 16384 - sum(C) is added to the largest C, the lowest position among equals;
+ *   start = clamp(lo, 0, S - K).  The axis' program is start[D] and C[D][K], C[i][j] belonging to source position start[i] + j.
+ * Sample rule: out = clamp((sum_j C[i][j] * s[start[i] + j] + 8192) >> 14, 0, maxv), int32 accumulator, arithmetic shift,
+ *   maxv = (1 << bits) - 1.
+ * Frame rule: the horizontal stage runs on every source row into an intermediate of dst_w x src_h samples, rounded and clamped as above,
+ *   at the clip's depth; the vertical stage runs on the intermediate.  Every plane on its own: chroma is S/2 -> D/2 with the same kernel,
+ *   chroma siting is ignored.  Frames are independent: the bytes do not depend on how a clip is cut into calls.  Equal sizes copy.
+ * amtgpu_resize_create: all four sizes even and positive, bits 8..16, kernel one of AMTGPU_RESIZE_*; taps <= 0 takes the kernel's default
+ *   (at most 64).  max_scratch_bytes bounds the intermediate the object owns, whatever the clip's length: a call works through its
+ *   frames in rounds of as many frames as fit it, at least one; <= 0 takes AMTGPU_RESIZE_DEFAULT_SCRATCH_BYTES.  Returns NULL with a
+ *   message on ctx: a figure below one frame's intermediate (rows of dst_w samples rounded up to 16 bytes, src_h of them, plus the two
+ *   chroma planes'); a program whose largest sum of positive coefficients times maxv plus 8192, or likewise of negative ones, leaves
+ *   int32; a horizontal window (K samples) that does not fit the kernel's staging region (2000 bytes).
+ * amtgpu_resize_run: frames 0 .. nframes - 1 of src (src_w x src_h) into frames 0 .. nframes - 1 of dst (dst_w x dst_h), planar LSB planes
+ *   of the resizer's bits.  Returns 0 with a message on ctx, and launches nothing: an interleaved or MSB-aligned descriptor; bits that
+ *   are not the resizer's (so unequal bits); a pitch smaller than the row; a negative frame stride; destination frames that overlap each
+ *   other in a plane; a destination plane whose byte range (first byte of frame 0 .. last byte of frame nframes - 1) overlaps a source
+ *   plane's.  nframes == 0 returns 1.  Reads nothing outside a row's width of a source row, writes nothing outside it in a destination
+ *   row; the source is never written.  All rounds run in the context's stream.  Synchronises, as amtgpu_temporal_nr does.
+ * amtgpu_resize_get_program: K, start[D] and coeff[D * K] of plane 0 (luma) / 1 (chroma), axis 0 (horizontal) / 1 (vertical); start and
+ *   coeff may be NULL, so that a caller can ask for K first (D is the destination size of that plane and axis) */
+typedef struct AmtGpuResize AmtGpuResize;
+#define AMTGPU_RESIZE_BLACKMAN 0
+#define AMTGPU_RESIZE_LANCZOS  1
+#define AMTGPU_RESIZE_BILINEAR 2
+#define AMTGPU_RESIZE_DEFAULT_SCRATCH_BYTES (64ll << 20)     /* 64 MiB: a quarter of the 256 MiB last-level cache of an MI355X */
+AmtGpuResize* amtgpu_resize_create(AmtGpuContext* ctx, int src_w, int src_h, int dst_w, int dst_h, int bits, int kernel, int taps,
+                                   int64_t max_scratch_bytes);
+void amtgpu_resize_destroy(AmtGpuResize* r);
+int  amtgpu_resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes);
+int  amtgpu_resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int* start, int* coeff);
+
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
