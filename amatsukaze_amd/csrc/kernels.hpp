@@ -13,6 +13,7 @@
 
 #include "eval_plan.h"
 #include "lane_rule.h"
+#include "resize_region.h"
 
 namespace amt {
 
@@ -158,9 +159,8 @@ struct ResizePlaneArgs {
     int src_pitch, dst_pitch;                  // bytes between rows
 };
 constexpr int kResizeWaves = 4;                // waves of a workgroup; each works on its own
-constexpr int kResizeRegionBytes = 2048;       // LDS of one wave of the horizontal stage: the source span of its run of output columns
-constexpr int kResizeRegionSlack = 48;         // ... less the bytes in front of an aligned-down span (15) and behind it for zero taps (16 samples)
-constexpr int kResizeRows = 16;                // rows a wave of the horizontal stage walks with its coefficients in registers
+                                               // (kResizeRegionBytes, kResizeRegionSlack: a wave's LDS region, resize_region.h)
+constexpr int kResizeRows = 16;               // rows a wave of the horizontal stage walks with its coefficients in registers
 struct ResizeStageArgs {
     ResizePlaneArgs plane[3];                  // Y, U, V
     ResizeProgramDev prog[2];                  // luma, chroma: the axis this stage resamples
@@ -169,9 +169,7 @@ struct ResizeStageArgs {
     int cpw[2];                                // horizontal: output columns of a wave's run, 1..64 (resize_columns_per_wave)
     int es, vec, maxv;                         // vec: resize_vec16 (lane_rule.h)
 };
-// The largest run of output columns (64 at the most) whose source span, start[last] + K - start[first], fits a wave's LDS region for
-// every run of the row; 0: not even one column's window fits (the caller refuses)
-int resize_columns_per_wave(const int* start, int D, int K, int es);
+// (a.cpw[] comes from resize_columns_per_wave, declared in resize_region.h and defined with the plan in resize_plan.cpp)
 // One launch each; none when nframes <= 0.  a.plane[].src of the vertical stage is the horizontal stage's dst
 hipError_t launch_resize_h(hipStream_t st, const ResizeStageArgs& a, int nframes);
 hipError_t launch_resize_v(hipStream_t st, const ResizeStageArgs& a, int nframes);

@@ -112,19 +112,6 @@ void resize_h_kernel(ResizeStageArgs a, int runsY, int bandsY, int runsC, int ba
     }
 }
 
-int resize_columns_per_wave(const int* start, int D, int K, int es)
-{
-    for (int cpw = 64; cpw >= 1; cpw >>= 1) {
-        bool fits = true;
-        for (int c0 = 0; c0 < D && fits; c0 += cpw) {
-            const int last = (c0 + cpw < D ? c0 + cpw : D) - 1;
-            fits = (long long)(start[last] + K - start[c0]) * es + kResizeRegionSlack <= kResizeRegionBytes;
-        }
-        if (fits) return cpw;
-    }
-    return 0;
-}
-
 static bool resize_args_ok(const ResizeStageArgs& a)
 {
     if ((a.es != 1 && a.es != 2) || a.maxv < 255 || a.maxv > 65535) return false;

@@ -102,4 +102,17 @@ bool resize_program_fits_int32(const ResizeProgram& p, int bits)
     return hi <= (long double)INT_MAX && lo >= (long double)INT_MIN;
 }
 
+int resize_columns_per_wave(const int* start, int D, int K, int es)
+{
+    for (int cpw = 64; cpw >= 1; cpw >>= 1) {
+        bool fits = true;
+        for (int c0 = 0; c0 < D && fits; c0 += cpw) {
+            const int last = (c0 + cpw < D ? c0 + cpw : D) - 1;
+            fits = (long long)(start[last] + K - start[c0]) * es + kResizeRegionSlack <= kResizeRegionBytes;
+        }
+        if (fits) return cpw;
+    }
+    return 0;
+}
+
 } // namespace amt

@@ -8,6 +8,8 @@
 
 #include <vector>
 
+#include "resize_region.h"      // resize_columns_per_wave: which run of output columns a wave of the horizontal stage takes
+
 namespace amt {
 
 enum ResizeKernel { kResizeBlackman = 0, kResizeLanczos = 1, kResizeBilinear = 2 };   // AMTGPU_RESIZE_*

@@ -4,9 +4,12 @@
 //                                                    16 bits, and its refusal of programs made to exceed it; prints "resize plan ok"
 //          resize_plan_test S D kernel taps [...]    one line per quadruple: "S D kernel taps K | start[0..D) | coeff[0..D*K)"
 //                                                    (kernel 0 blackman, 1 lanczos, 2 bilinear; taps 0: the kernel's default)
+//          resize_plan_test cpw S D kernel taps es [...]   one line per quintuple: "S D kernel taps es K cpw", cpw being
+//                                                    resize_columns_per_wave of the program at containers of es bytes (0: refused)
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 
 #include "resize_plan.hpp"
@@ -66,6 +69,15 @@ static int self_checks()
 int main(int argc, char** argv)
 {
     if (argc == 1) return self_checks();
+    if (!strcmp(argv[1], "cpw")) {
+        if ((argc - 2) % 5) { fprintf(stderr, "usage: resize_plan_test cpw [S D kernel taps es]...\n"); return 2; }
+        for (int a = 2; a + 4 < argc; a += 5) {
+            const int S = atoi(argv[a]), D = atoi(argv[a + 1]), kernel = atoi(argv[a + 2]), taps = atoi(argv[a + 3]), es = atoi(argv[a + 4]);
+            const ResizeProgram p = resize_program(S, D, kernel, taps);
+            printf("%d %d %d %d %d %d %d\n", S, D, kernel, taps, es, p.K, resize_columns_per_wave(p.start.data(), p.D, p.K, es));
+        }
+        return 0;
+    }
     if ((argc - 1) % 4) { fprintf(stderr, "usage: resize_plan_test [S D kernel taps]...\n"); return 2; }
     for (int a = 1; a + 3 < argc; a += 4) {
         const int S = atoi(argv[a]), D = atoi(argv[a + 1]), kernel = atoi(argv[a + 2]), taps = atoi(argv[a + 3]);

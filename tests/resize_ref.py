@@ -79,6 +79,35 @@ def float_program(S, D, kernel="blackman", taps=None):
     return K, start, W
 
 
+REGION_BYTES, REGION_SLACK = 2048, 48
+
+
+def windows(S, D, kernel="blackman", taps=None):
+    """(K, start[D]) of one axis without its coefficients: the windows alone, which is all the horizontal stage's staging depends on
+    (tests/test_resize_host.py holds them against program()'s)"""
+    taps = DEFAULT_TAPS[kernel] if not taps or taps <= 0 or kernel == "bilinear" else taps
+    scale = D / S
+    support = taps / min(scale, 1.0)
+    K = min(math.ceil(2 * support), S)
+    start = [min(max(math.floor((i + 0.5) / scale - 0.5 - support) + 1, 0), S - K) for i in range(D)]
+    return K, np.array(start, np.int64)
+
+
+def columns_per_wave(S, D, es, kernel="blackman", taps=None):
+    """(cpw, K, spans): the run of output columns a wave of the horizontal stage takes, from the rule's text: a
+    wave stages the source span of its run, start[last] + K - start[first] samples of es bytes, in a region of 2048 bytes of which 48
+    are kept for the aligned-down front and the zero taps behind; the run is halved from 64 until every run of the row fits.  spans:
+    each run's span in bytes, in the row's order.  cpw 0, spans (): not even single columns fit, which the create refuses"""
+    K, start = windows(S, D, kernel, taps)
+    cpw = 64
+    while cpw >= 1:
+        spans = tuple(int(start[min(c0 + cpw, D) - 1] + K - start[c0]) * es for c0 in range(0, D, cpw))
+        if all(s + REGION_SLACK <= REGION_BYTES for s in spans):
+            return cpw, K, spans
+        cpw //= 2
+    return 0, K, ()
+
+
 def stage(lines, prog, maxv):
     """the sample rule along the LAST axis of `lines` (any leading shape): int64 in, int64 out"""
     K, start, C = prog

@@ -50,7 +50,7 @@ def noise_case(n, sw, sh, dw, dh, bits, kernel="blackman"):
     return planes, want
 
 
-def run_resize(gpu, what, planes, bits, dst_size, layouts, want, kernel="blackman", max_scratch_bytes=None):
+def run_resize(gpu, what, planes, bits, dst_size, layouts, want, kernel="blackman", max_scratch_bytes=None, taps=None):
     """resizes the whole clip in one call and compares every destination container; the sources must stay as they were.  Returns the
     destination's flat buffers as they came back"""
     from amatsukaze_amd import Resizer
@@ -62,13 +62,13 @@ def run_resize(gpu, what, planes, bits, dst_size, layouts, want, kernel="blackma
     dst_host = sentinel_buf(n, dw, dh, bits, dl)
     src, src_flat = upload(gpu, src_host)
     dst, dst_flat = upload(gpu, dst_host)
-    rz = Resizer(ctx, (sw, sh), (dw, dh), bits, kernel=kernel, max_scratch_bytes=max_scratch_bytes)
+    rz = Resizer(ctx, (sw, sh), (dw, dh), bits, kernel=kernel, taps=taps, max_scratch_bytes=max_scratch_bytes)
     try:
         assert rz.run(src, dst) == n
         for plane, (S_w, S_h, D_w, D_h) in enumerate(((sw, sh, dw, dh), (sw // 2, sh // 2, dw // 2, dh // 2))):
             for axis, (S, D) in enumerate(((S_w, D_w), (S_h, D_h))):
                 K, start, coeff = rz.program(plane, axis)
-                rK, rstart, rC = R.program(S, D, kernel)
+                rK, rstart, rC = R.program(S, D, kernel, taps)
                 assert K == rK and np.array_equal(start, rstart) and np.array_equal(coeff, rC), (what, "program", plane, axis)
     finally:
         rz.close()

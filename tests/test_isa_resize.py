@@ -10,7 +10,7 @@ import pytest
 from test_isa_guards import kernels_of
 from test_isa_surfaces import compile_file, lean
 
-WAVES, REGION_BYTES = 4, 2048                    # kResizeWaves, kResizeRegionBytes (csrc/kernels.hpp)
+WAVES, REGION_BYTES = 4, 2048                    # kResizeWaves (csrc/kernels.hpp), kResizeRegionBytes (csrc/resize_region.h)
 # VGPRs the compiler reports today (ROCm 7.2, -O3)
 VGPR_TODAY = {"resize_h_kernelIhLi8E": 57, "resize_h_kernelIhLi12E": 61, "resize_h_kernelIhLi16E": 64, "resize_h_kernelIhLi0E": 50,
               "resize_h_kernelItLi8E": 38, "resize_h_kernelItLi12E": 42, "resize_h_kernelItLi16E": 46, "resize_h_kernelItLi0E": 42,

@@ -61,6 +61,47 @@ def test_cpp_and_numpy_tables_are_equal_entry_for_entry(cpp_programs, kernel):
         assert np.array_equal(Cf, rC), (S, D, "coefficients differ at", np.argwhere(Cf != rC)[:3].tolist())
 
 
+# ... and the luma (S, D) of every frame tests/test_gpu_resize_spans.py resizes, widths and heights, with the two widths it must see refused
+SPAN_FRAMES = [((1000, 8), (32, 8)), ((2000, 8), (66, 8)), ((1760, 8), (66, 8)), ((2048, 4), (32, 4)), ((2000, 8), (2, 8)), ((2002, 8), (2, 8)),
+               ((1000, 8), (2, 8)), ((1002, 8), (2, 8)), ((2176, 12), (2080, 8)), ((1088, 12), (1040, 8)), ((1094, 12), (1046, 8)), ((100, 100), (38, 38)),
+               ((48, 36), (32, 24)), ((272, 48), (182, 34))]
+SPAN_PAIRS = sorted({(s >> p, d >> p) for src, dst in SPAN_FRAMES for s, d in zip(src, dst) for p in (0, 1)})
+
+
+def test_the_columns_per_wave_port_is_the_cpp_rule(plan_test):
+    """R.columns_per_wave, written from the rule's text, against resize_columns_per_wave as the library compiles it: every axis of the
+    span tests and of the older ones, and S = 4 D .. 40 D in steps of 2 for D = 16, 34, 66 (ratios from where a run of 64 columns
+    still fits to where not one column does), at containers of 1 and 2 bytes; and the explicit taps the span tests pass"""
+    cases = [(S, D, "blackman", 0) for S, D in sorted(set(SPAN_PAIRS) | set(PAIRS))]
+    cases += [(S, D, "blackman", 0) for D in (16, 34, 66) for S in range(4 * D, 40 * D + 1, 2)]
+    cases += [(r * 66, 66, "blackman", 0) for r in (150, 200, 240, 250)]         # at 1 byte: runs of 4, 2 and 1 columns, and none
+    cases += [(S, D, k, 0) for S, D in ((2000, 66), (1760, 66), (2048, 32), (272, 182)) for k in ("lanczos", "bilinear")]
+    cases += [(S, D, "blackman", 8) for S, D in ((48, 32), (36, 24), (24, 16), (18, 12), (1000, 66))]
+    cases = [c + (es,) for c in cases for es in (1, 2)]
+    args = [str(v) for S, D, k, taps, es in cases for v in (S, D, R.KERNELS[k], taps, es)]
+    out = subprocess.run([plan_test, "cpw"] + args, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(cases) >= 2 * 2091
+    seen = set()
+    for line, (S, D, k, taps, es) in zip(out, cases):
+        cS, cD, ck, ctaps, ces, cK, ccpw = (int(v) for v in line.split())
+        assert (cS, cD, ck, ctaps, ces) == (S, D, R.KERNELS[k], taps, es)
+        cpw, K, spans = R.columns_per_wave(S, D, es, k, taps)
+        assert (cpw, K) == (ccpw, cK), (S, D, k, taps, es, "port", cpw, K, "C++", ccpw, cK)
+        assert (len(spans) == -(-D // cpw) and max(spans) + 48 <= 2048) if cpw else spans == ()
+        seen.add(cpw)
+    assert seen == {0, 1, 2, 4, 8, 16, 32, 64}                       # the sweep meets every answer the rule has
+
+
+def test_the_ports_windows_are_the_programs():
+    for S, D in SPAN_PAIRS + [(48, 32), (272, 182), (32, 50), (1920, 1280)]:
+        for kernel, taps in (("blackman", None), ("lanczos", None), ("bilinear", None), ("blackman", 8)):
+            if S * D > 300000 and kernel != "blackman":
+                continue                                             # (the programs of the widest pairs once)
+            K, start = R.windows(S, D, kernel, taps)
+            pK, pstart, _ = R.program(S, D, kernel, taps)
+            assert K == pK and np.array_equal(start, pstart), (S, D, kernel, taps)
+
+
 def test_explicit_taps_reach_the_cpp_plan(plan_test):
     out = subprocess.run([plan_test, "48", "32", "1", "4", "48", "32", "0", "2"], capture_output=True, text=True, check=True).stdout.splitlines()
     for line, (kernel, taps) in zip(out, (("lanczos", 4), ("blackman", 2))):
