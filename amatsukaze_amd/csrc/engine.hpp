@@ -212,7 +212,8 @@ private:
     static bool stage4_eligible(const EvalLogoSpec& S);
     bool tiles_stage4_ = false;                    // the taps carry the 0.25; otherwise the pair kernel's ldexp form runs on plain taps
     std::vector<DevBuf<float2>> d_tkp_, d_tsc_, d_tpq_;
-    std::vector<DevBuf<uint32_t>> d_tinfo_, d_tpos_;
+    bool tiles_units_ = false;                     // the scan's plans are single-pass ones and its pair kernel the one-unit form (ensure_tiles)
+    std::vector<DevBuf<uint32_t>> d_tinfo_, d_tpos_, d_tunits_;
     std::vector<DevBuf<char>> d_tlin_;
     int lin_queue_ = 256;
     std::vector<DevBuf<TileDesc>> d_tiles_;

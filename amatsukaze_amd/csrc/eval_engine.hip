@@ -202,8 +202,10 @@ void EvalEngine::run(const FrameBatch& luma, int bits, int nframes, float* dout,
         const std::string suffix = dot == std::string::npos ? std::string() : prof_name_.substr(dot);
         const int Gp = group_frames_ > 0 ? group_frames_ : (int)std::max(1LL, std::min((long long)kTileMaxFrames, (long long)nframes * nl / 2048));
         // (tables that carry DeintY's 0.25 -- every engine, in practice -- or the kernel's ldexp form on unscaled ones: ensure_tiles)
+        // (single-pass plans for every logo -- the bench's and most drawn logos -- run the one-unit form: ensure_tiles)
+        // (the profile names the pass, whichever of its two staging forms runs: bench.py and tools read it by this name)
         const int sp = ctx_->prof_begin(((tiles_stage4_ ? "logo_eval_pair_kernel" : "logo_eval_pair_ldexp_kernel") + suffix).c_str());
-        AMT_HIP(launch_logo_eval_pair(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, luma, dframe_map, nframes, Gp, dout, out_frame_stride_,
+        AMT_HIP((tiles_units_ ? launch_logo_eval_pair1 : launch_logo_eval_pair)(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, luma, dframe_map, nframes, Gp, dout, out_frame_stride_,
                                       take_abs_ ? 1 : 0, tiles_stage4_ ? 0 : 1));
         ctx_->prof_end(sp);
         return;
@@ -313,13 +315,31 @@ void EvalEngine::ensure_tiles()
     // profiles/stage_unscaled_notes.md.)
     tiles_stage4_ = fades_.size() == 2;
     for (const EvalLogoSpec& S : specs_) tiles_stage4_ = tiles_stage4_ && stage4_eligible(S);
+    // The scan's pair kernel also comes with one staging unit per lane, on plans whose tiles list the at most 64 units their windows
+    // read (eval_tiles.hpp kTileCutUnits).  Forcing every tile under that limit costs tiles on masks that are dense, tall or very
+    // wide, so each logo's single-pass plan is set against its best existing cut by the plans' own model, and the engine takes the
+    // one-unit form only when no logo loses by it (tile_plans_single_pass): one kernel per launch, as above.  The records are the
+    // same bits under every plan -- the kernel sums in raster order.
+    std::vector<TilePlan> plans(nl);
+    for (int i = 0; i < nl; ++i)
+        plans[i] = build_tile_plan(specs_[i].tables.pos, specs_[i].tables.count, specs_[i].planes.w, specs_[i].planes.h,
+                                   fades_.size() == 2 ? kTileCutBest : kTileCutCoarse);
+    tiles_units_ = false;
+    if (fades_.size() == 2) {
+        std::vector<TilePlan> single(nl);
+        for (int i = 0; i < nl; ++i)
+            single[i] = build_tile_plan(specs_[i].tables.pos, specs_[i].tables.count, specs_[i].planes.w, specs_[i].planes.h, kTileCutUnits);
+        tiles_units_ = tile_plans_single_pass(plans, single);
+        if (tiles_units_) plans.swap(single);
+    }
+    d_tunits_.resize(nl);
     d_tkp_.resize(nl); d_tsc_.resize(nl); d_tpq_.resize(nl); d_tinfo_.resize(nl); d_tpos_.resize(nl); d_tlin_.resize(nl); d_tiles_.resize(nl); d_tbands_.resize(nl); d_tlist_.resize(nl);
     for (int i = 0; i < nl; ++i) {
         const EvalLogoSpec& S = specs_[i];
         const MaskTables& T = S.tables;
         // (the scan -- fades {0, 1}: the pair kernel, raster-order sums -- takes the cut with the lower modelled critical path; every
         //  other engine keeps the coarse cut: the linear kernel's summation order follows the tiles)
-        const TilePlan P = build_tile_plan(T.pos, T.count, S.planes.w, S.planes.h, fades_.size() == 2 ? kTileCutBest : kTileCutCoarse);
+        const TilePlan& P = plans[i];
         // (a sparse mask spends a whole tile of 64 slots on a few pixels: the slot count is bounded by nothing but this check.  Beyond the
         //  limit no table is built and both tile kernels are off for this engine: pair_eligible, run_linear)
         if (!tile_slots_ok(P.nslots())) { tile_slots_ok_ = false; continue; }
@@ -374,6 +394,10 @@ void EvalEngine::ensure_tiles()
         hl[i] = TileLogoDev{d_tkp_[i].get(), d_tsc_[i].get(), d_tpq_[i].get(), d_tinfo_[i].get(), d_tpos_[i].get(), d_tiles_[i].get(), d_tbands_[i].get(), d_tlist_[i].get(),
                             (int)P.bands.size(), (int)ns, (int)tlist.size(), T.floorResp};
         hl[i].lin = d_tlin_[i].get();
+        if (tiles_units_) {
+            d_tunits_[i].upload(P.units, ctx_->stream);
+            hl[i].units = d_tunits_[i].get();
+        }
         hl[i].lin_pq = (unsigned)o_pq; hl[i].lin_sinfo = (unsigned)o_si; hl[i].lin_a = (unsigned)o_a; hl[i].lin_b = (unsigned)o_b;
     }
     d_tls_.upload(hl, ctx_->stream);

@@ -350,6 +350,63 @@ template <typename pix_t, bool STAGE4> struct TileStager {
     }
 };
 
+// The staging state of a wave on a single-pass plan (eval_tiles.hpp kTileCutUnits): every lane holds ONE unit, the one the plan's list
+// names for it -- `word` = tile_unit_word(row, c4), lanes past the tile's last needed unit hold that unit again.  Half the registers and
+// half the raw loads of TileStager, no second pass; cells of the box that no listed unit covers are never written and never read.
+template <typename pix_t, bool STAGE4> struct TileStager1 {
+    static constexpr int ES = (int)sizeof(pix_t);
+    // (wave-uniform)
+    int w, h, deint, srow0, srow_step, scol0, pitchB;
+    float maxv;
+    gptr_t gA, gB;
+    f2* plane;
+    // (per lane)
+    int ulds;                        // pair offset in the tile plane
+    int ug[3];                       // byte offsets in a frame of the rows above / at / below the unit
+    unsigned ubias;
+    f4 ua, ubmv;                     // the unit's logo coefficients: a, b * maxv (b until coefs_landed())
+    Quad<pix_t> raw[3];
+
+    __device__ __forceinline__ void init(const EvalLogoDev* Lp, int pitch, float maxv_, f2* plane_)
+    {
+        w = Lp->w; h = Lp->h; deint = Lp->deint;
+        srow0 = Lp->imgy + Lp->row0; srow_step = Lp->row_step; scol0 = Lp->imgx;
+        gA = (gptr_t)Lp->a; gB = (gptr_t)Lp->b;
+        pitchB = pitch * ES; maxv = STAGE4 ? times4_uniform(maxv_) : maxv_; plane = plane_;
+    }
+    __device__ __forceinline__ void setup_units(const TileDesc& T, unsigned word)
+    {
+        const TileUnit U = tile_unit_listed(T, word, w);
+        const bool blend = deint && U.y > 0 && U.y < h - 1;           // DeintY copies the first and the last row (LogoScan.hpp:763-780)
+        ulds = U.lds;
+        ubias = blend ? Quad<pix_t>::kBias : 0u;
+        // (24-bit multiplies as in TileStager::setup_units)
+        ug[1] = (int)mul24((unsigned)srow0 + mul24_opaque((unsigned)U.y, (unsigned)srow_step), (unsigned)pitchB) + (scol0 + U.xs) * ES;
+        ug[0] = blend ? ug[1] - pitchB : ug[1];
+        ug[2] = blend ? ug[1] + pitchB : ug[1];
+        typedef f4 __attribute__((aligned(8))) f4a8;
+        const unsigned ocoef = (mul24((unsigned)U.y, (unsigned)w) + (unsigned)U.xs) * 4u;
+        ua = gld<f4a8>(gA, ocoef);
+        ubmv = gld<f4a8>(gB, ocoef);
+    }
+    // b -> b * maxv, where the coefficient loads have had time to land (TileStager::coefs_landed)
+    __device__ __forceinline__ void coefs_landed() { ubmv = ubmv * maxv; }
+    __device__ __forceinline__ void request(const __amdgpu_buffer_rsrc_t frame)
+    {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) raw[j].load(frame, ug[j]);
+    }
+    // raw samples -> {s, bg = a*s + b*maxv} pairs (LogoScan.hpp:247)
+    __device__ __forceinline__ void convert()
+    {
+        float sv[4];
+        Quad<pix_t>::template blend<!STAGE4>(raw[0], raw[1], raw[2], ubias, sv);
+        f2* dst = plane + ulds;
+        reinterpret_cast<f4*>(dst)[0] = f4{sv[0], ua[0] * sv[0] + ubmv[0], sv[1], ua[1] * sv[1] + ubmv[1]};
+        reinterpret_cast<f4*>(dst)[1] = f4{sv[2], ua[2] * sv[2] + ubmv[2], sv[3], ua[3] * sv[3] + ubmv[3]};
+    }
+};
+
 template <typename pix_t>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const void* Y, const int* frame_map, long long frame_stride, int frame)
 {

@@ -88,6 +88,17 @@ AMT_TILE_HD TileUnit tile_unit(const TileDesc& T, int u, int w)
     const int xs = x < w - 4 ? x : w - 4;             // a ragged right edge: the last unit moves left
     return TileUnit{T.y0 + row, xs, (int)mul24((unsigned)row, (unsigned)T.tp) + (xs - T.x0)};
 }
+// The same for a LISTED unit (TilePlan::units, the single-pass plans): tile row and four-column index packed in one word.  The unit of
+// column X of the tile is (X - x0) / 4 whether or not the ragged edge moves it: a moved unit covers [w - 4, w), which holds every
+// column from its unmoved origin to the logo's last.
+AMT_TILE_HD unsigned tile_unit_word(int row, int c4) { return ((unsigned)row << 8) | (unsigned)c4; }
+AMT_TILE_HD TileUnit tile_unit_listed(const TileDesc& T, unsigned word, int w)
+{
+    const int row = (int)(word >> 8), c4 = (int)(word & 0xFFu);
+    const int x = T.x0 + 4 * c4;
+    const int xs = x < w - 4 ? x : w - 4;
+    return TileUnit{T.y0 + row, xs, (int)mul24((unsigned)row, (unsigned)T.tp) + (xs - T.x0)};
+}
 
 // Workgroup -> (logo, frame group) of the scan's tile kernel.  Workgroups are dealt to the 8 XCDs round-robin by their linear id, each XCD
 // has its own 4 MB L2, and the candidate logos of a scan all read the same rectangle of the same frames: the workgroups of ONE frame group
@@ -119,13 +130,23 @@ struct TilePlan {
     std::vector<int> slot_pixel;          // per slot: mask pixel m, -1 for an idle lane
     long long model_cost = 0;             // modelled critical path: per band the busiest SIMD's sum of its tiles' 131 + 31 * passes
     int nslots() const { return (int)sinfo.size(); }
+    // kTileCutUnits only: per tile the units some window of a valid slot reads, in raster order -- kTileLanes words (tile_unit_word)
+    // per tile, entries from nunits[tile] on repeat the last needed unit (a tile without pixels: unit 0 throughout, nunits 0)
+    std::vector<uint32_t> units;
+    std::vector<int> nunits;              // per tile, <= kTileLanes
+    bool single_pass = false;
 };
 // How the bands are cut.  Coarse: an over-full band (more than kTileWaves tiles) loses an eighth of its pixels at a time.  Fine: four
 // at a time -- the largest band on that grid that fits -- and a last band of less than one tile's pixels joins the one before it
 // where that still fits.  Best: whichever of the two has the lower modelled critical path (the coarse one when they tie).
 // A kernel that adds its terms in raster order (the scan's) computes the same records under every cut; the linear analysis kernel's
 // summation order follows the tiles, so it keeps the coarse cut its records were established with.
-enum TileCut { kTileCutCoarse, kTileCutFine, kTileCutBest };
+//
+// Units: the fine cut with tiles that grow only while the units they NEED -- those that hold an element of one of their pixels' windows,
+// about four fifths of the box on a logo's strokes -- number at most kTileLanes: every tile is staged in one pass by a kernel that
+// holds one unit per lane and takes it from the plan's list (eval_pair1_kernels.hip).  The box still fits kTileCap and the two-unit
+// kernels' 128 units, so such a plan also runs on them.  Never what Best returns.
+enum TileCut { kTileCutCoarse, kTileCutFine, kTileCutBest, kTileCutUnits };
 
 namespace tiles_detail {
 
@@ -187,13 +208,24 @@ inline Geometry bbox(const std::vector<Px>& g, size_t a, size_t b)
     return G;
 }
 inline bool fits(const Geometry& G) { return G.nrows * G.ncol4 * 4 <= kTileCap && G.nrows * G.ncol4 <= kTileLanes * kTileUnits; }
+// the units pixel p's window reads, as (y << 8) | c4 with c4 counted from the tile's x0 (fixed by the tile's first pixel: they come by
+// column), appended to keys where missing
+inline void add_needed_units(std::vector<uint32_t>& keys, int x0, const Px& p)
+{
+    for (int y = p.y - 2; y <= p.y + 2; ++y)
+        for (int c4 = (p.x - 2 - x0) / 4; c4 <= (p.x + 2 - x0) / 4; ++c4) {
+            const uint32_t key = ((uint32_t)y << 8) | (uint32_t)c4;
+            if (std::find(keys.begin(), keys.end(), key) == keys.end()) keys.push_back(key);
+        }
+}
 
 } // namespace tiles_detail
 
 namespace tiles_detail {
 
 // the band's pixels [m, m + n) by column, then row, dealt 64 at a time: a wave's pixels cover few columns and all of the band's rows
-inline std::vector<std::vector<Px>> deal_band(const std::vector<uint32_t>& pos, int m, int n)
+// (units: a tile also stops growing where its needed units would exceed kTileLanes)
+inline std::vector<std::vector<Px>> deal_band(const std::vector<uint32_t>& pos, int m, int n, bool units = false)
 {
     std::vector<Px> px(n);
     for (int i = 0; i < n; ++i) px[i] = Px{(int)(pos[m + i] & 0xFFFFu), (int)(pos[m + i] >> 16), m + i};
@@ -201,26 +233,35 @@ inline std::vector<std::vector<Px>> deal_band(const std::vector<uint32_t>& pos, 
     std::vector<std::vector<Px>> groups;
     for (size_t a = 0; a < px.size();) {
         size_t b = a + 1;
-        while (b < px.size() && b - a < (size_t)kTileLanes && fits(bbox(px, a, b + 1))) ++b;
+        std::vector<uint32_t> keys;
+        const int x0 = (px[a].x - 2) & ~1;
+        if (units) add_needed_units(keys, x0, px[a]);
+        while (b < px.size() && b - a < (size_t)kTileLanes && fits(bbox(px, a, b + 1))) {
+            if (units) {
+                add_needed_units(keys, x0, px[b]);
+                if (keys.size() > (size_t)kTileLanes) break;
+            }
+            ++b;
+        }
         groups.emplace_back(px.begin() + a, px.begin() + b);
         a = b;
     }
     return groups;
 }
 // pixels per band
-inline std::vector<int> cut_bands(const std::vector<uint32_t>& pos, int count, bool fine)
+inline std::vector<int> cut_bands(const std::vector<uint32_t>& pos, int count, bool fine, bool units = false)
 {
     std::vector<int> cuts;
     for (int m = 0; m < count;) {
         int n = std::min(kTileBandPix, count - m);
-        while ((int)deal_band(pos, m, n).size() > kTileWaves)          // sparse stretch: a shorter band
+        while ((int)deal_band(pos, m, n, units).size() > kTileWaves)          // sparse stretch: a shorter band
             n = fine ? std::max(1, n - 4) : std::max(1, n - std::max(1, n / 8));
         cuts.push_back(n);
         m += n;
     }
     if (fine && cuts.size() >= 2 && cuts.back() < kTileLanes) {
         const int n = cuts[cuts.size() - 2] + cuts.back();
-        if (n <= kTileBandPix && (int)deal_band(pos, count - n, n).size() <= kTileWaves) { cuts.pop_back(); cuts.back() = n; }
+        if (n <= kTileBandPix && (int)deal_band(pos, count - n, n, units).size() <= kTileWaves) { cuts.pop_back(); cuts.back() = n; }
     }
     return cuts;
 }
@@ -238,9 +279,11 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
         return fine.model_cost < coarse.model_cost ? fine : coarse;
     }
     TilePlan P;
+    const bool units = cut == kTileCutUnits;
+    P.single_pass = units;
     int m = 0;
-    for (const int n : cut_bands(pos, count, cut == kTileCutFine)) {
-        std::vector<std::vector<Px>> groups = deal_band(pos, m, n);
+    for (const int n : cut_bands(pos, count, cut == kTileCutFine || units, units)) {
+        std::vector<std::vector<Px>> groups = deal_band(pos, m, n, units);
         // Which wave takes which tile is free.  Waves are dealt to the CU's four SIMDs round-robin (wave w on SIMD w % 4: with eleven
         // evaluation waves three each on SIMDs 0-2, two and the summing wave on SIMD 3), a SIMD issues for one wave at a time, and a
         // tile with more than 64 staging units costs a second staging pass: the tiles go heaviest first to the SIMD with the least
@@ -248,7 +291,7 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
         {
             std::vector<size_t> order(groups.size());
             for (size_t i = 0; i < order.size(); ++i) order[i] = i;
-            auto cost = [&](size_t i) { const Geometry G = bbox(groups[i], 0, groups[i].size()); return 131 + 31 * (G.nrows * G.ncol4 > kTileLanes ? 2 : 1); };
+            auto cost = [&](size_t i) { const Geometry G = bbox(groups[i], 0, groups[i].size()); return 131 + 31 * (!units && G.nrows * G.ncol4 > kTileLanes ? 2 : 1); };   // (units: at most kTileLanes NEEDED units, by deal_band's rule)
             std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return cost(a) > cost(b); });
             int load[4] = {0, 0, 0, 0}, used[4] = {0, 0, 0, 0}, cap[4] = {0, 0, 0, 0};
             for (int w = 0; w < kTileWaves; ++w) ++cap[w % 4];
@@ -268,6 +311,10 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
         P.tiles.resize((size_t)(band + 1) * kTileWaves, TileDesc{0, 0, 0, 1, 4, 0, 65536, 0});
         P.sinfo.resize((size_t)(band + 1) * kTileBandPix, tile_slot_info(0, 0, false));
         P.slot_pixel.resize((size_t)(band + 1) * kTileBandPix, -1);
+        if (units) {
+            P.units.resize((size_t)(band + 1) * kTileBandPix, tile_unit_word(0, 0));
+            P.nunits.resize((size_t)(band + 1) * kTileWaves, 0);
+        }
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             const std::vector<Px>& g = groups[gi];
             if (g.empty()) continue;
@@ -303,10 +350,31 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
                 for (int l = next[hf]; l < kTileLanes / 2 * (hf + 1); ++l)
                     P.sinfo[((size_t)band * kTileWaves + gi) * kTileLanes + l] = tile_slot_info(woff, 0, false);
             }
+            if (units) {
+                // (lanes without a pixel read a valid pixel's window: they need no unit of their own)
+                std::vector<uint32_t> keys;
+                for (const Px& p : g) add_needed_units(keys, G.x0, p);
+                if (keys.empty() || keys.size() > (size_t)kTileLanes) throw std::runtime_error("tile plan: needed units");
+                for (uint32_t& k : keys) k = tile_unit_word((int)(k >> 8) - G.y0, (int)(k & 0xFFu));     // row-major: sorts in raster order
+                std::sort(keys.begin(), keys.end());
+                const size_t tile = (size_t)band * kTileWaves + gi;
+                P.nunits[tile] = (int)keys.size();
+                for (int l = 0; l < kTileLanes; ++l) P.units[tile * kTileLanes + l] = keys[std::min((size_t)l, keys.size() - 1)];
+            }
         }
         m += n;
     }
     return P;
+}
+
+// The scan engine's choice between its logos' best two-unit plans and their single-pass plans: one kernel per launch, so the single-pass
+// form runs when EVERY logo has a single-pass plan whose modelled cost is not above that of its best existing plan.
+inline bool tile_plans_single_pass(const std::vector<TilePlan>& best, const std::vector<TilePlan>& units)
+{
+    if (best.empty() || best.size() != units.size()) return false;
+    for (size_t i = 0; i < best.size(); ++i)
+        if (!units[i].single_pass || units[i].model_cost > best[i].model_cost || !tile_slots_ok(units[i].nslots())) return false;
+    return true;
 }
 
 } // namespace amt

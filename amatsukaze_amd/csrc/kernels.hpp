@@ -213,6 +213,9 @@ struct TileLogoDev {
     // scalar registers): kp at 0, then pq, sinfo, the evaluation logo's a and b planes at these byte offsets
     const char* lin;
     unsigned lin_pq, lin_sinfo, lin_a, lin_b;
+    // (new fields go here, at the end: the linear kernel reads the struct with scalar loads at fixed offsets)
+    const uint32_t* units;       // [nslots]      tile_unit_word of the staging unit a lane holds, when the engine's plans are single-pass ones
+                                 //               (eval_tiles.hpp kTileCutUnits; the scan's one-unit pair kernel); null otherwise
 };
 // These three and launch_rect_range_flag take a luma batch of LSB samples (a shift is hipErrorInvalidValue: surfaces_luma_view, api_common.hpp).
 // eval_fused_kernels.hip.  dnframes (device, optional): the number of frames actually present (<= nframes,
@@ -231,6 +234,10 @@ hipError_t launch_logo_eval_linear(hipStream_t st, int bits, const EvalLogoDev* 
 hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
                                  const FrameBatch& luma, const int* dframe_map, int nframes, int G, float* dout, int out_frame_stride, int take_abs,
                                  int ldexp_form);
+// eval_pair1_kernels.hip: the same on single-pass plans (every logo's TileLogoDev::units set), one staging unit per lane
+hipError_t launch_logo_eval_pair1(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
+                                  const FrameBatch& luma, const int* dframe_map, int nframes, int G, float* dout, int out_frame_stride, int take_abs,
+                                  int ldexp_form);
 // Sentinel monitor of AMTGPU_ANALYZE_LINEAR_MONITORED: persistent per-analyzer device state.  max_abs_bits: the largest |linear - exact| over
 // every compared score as float bits (non-negative floats order like unsigned ints; NaN counts as +inf); tripped: a comparison failed (sticky
 // until re-armed); frames_checked: sentinel frames compared; batches_tripped: batches in which a comparison failed
