@@ -1115,9 +1115,9 @@ RESIZE_KERNELS = {"blackman": 0, "lanczos": 1, "bilinear": 2}                   
 
 
 class Resizer:
-    """Blackman / Lanczos / bilinear resize of planar clips in HBM (amtgpu_resize_*): the BlackmanResize(w, h) in
-    front of KTemporalNR in the server's chain, integer and exact -- horizontal stage first into an intermediate the object owns, then
-    vertical; every plane on its own, chroma (w/2, h/2) -> (w/2, h/2) with the same kernel.  src_size and dst_size are (width, height)
+    """Blackman / Lanczos / bilinear resize of clips in HBM, planar or decoder surfaces in kind (amtgpu_resize_*): the
+    BlackmanResize(w, h) in front of KTemporalNR in the server's chain, integer and exact -- horizontal stage first into an intermediate
+    the object owns, then vertical; every plane on its own, chroma (w/2, h/2) -> (w/2, h/2) with the same kernel.  src_size and dst_size are (width, height)
     of the luma plane, all four even.  taps None: the kernel's default (blackman 4, lanczos 3).  max_scratch_bytes bounds the
     intermediate, not the clip: a run works through its frames in rounds (None: the header's default, 64 MiB)."""
 
@@ -1131,15 +1131,19 @@ class Resizer:
         ctx.check(self.h, "Resizer")
 
     def run(self, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSurfaces | DeviceClip"):
-        """frames 0 .. src.num_frames - 1 of src into the same frames of dst; planar LSB planes of the resizer's bits.  Synchronises.
-        Returns the number of frames"""
+        """frames 0 .. src.num_frames - 1 of src into the same frames of dst, both of the resizer's bits.  Planar LSB planes go to
+        amtgpu_resize_run; where either is interleaved or MSB-aligned (NV12, P010 / P012 / P016, interleaved LSB, planar MSB) the pair
+        goes to amtgpu_resize_run_surfaces and must be in kind: the rule runs on container >> shift, U and V each on its own, and every
+        destination container is result << shift with zero low bits.  Synchronises.  Returns the number of frames"""
         n = src.num_frames
         if n > dst.num_frames:
             raise AmtError(f"Resizer: {n} frames, dst holds {dst.num_frames}")
         if (int(src.width), int(src.height)) != (self.src_w, self.src_h) or (int(dst.width), int(dst.height)) != (self.dst_w, self.dst_h):
             raise AmtError(f"Resizer: made for {self.src_w}x{self.src_h} -> {self.dst_w}x{self.dst_h}, got {src.width}x{src.height} -> {dst.width}x{dst.height}")
         s, t = _surfaces_ref(src), _surfaces_ref(dst)
-        self.ctx.check(self.ctx.lib.amtgpu_resize_run(self.h, C.byref(s), C.byref(t), n), "Resizer")
+        in_kind = s.interleaved or s.msb_aligned or t.interleaved or t.msb_aligned
+        run = self.ctx.lib.amtgpu_resize_run_surfaces if in_kind else self.ctx.lib.amtgpu_resize_run
+        self.ctx.check(run(self.h, C.byref(s), C.byref(t), n), "Resizer")
         return n
 
     def program(self, plane, axis):

@@ -185,6 +185,7 @@ SIGNATURES = {
     "amtgpu_resize_create": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i64]),
     "amtgpu_resize_destroy": (None, [c_p]),
     "amtgpu_resize_run": (c_i, [c_p, c_p, c_p, c_i]),
+    "amtgpu_resize_run_surfaces": (c_i, [c_p, c_p, c_p, c_i]),
     "amtgpu_resize_get_program": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
     "amtgpu_cm_write_chapter_exe": (c_i, [c_p, c_i, c_i, c_s]),
     "amtgpu_audiolevels_create": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i64]),

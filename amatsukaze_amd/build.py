@@ -44,6 +44,7 @@ SOURCES = [
     "temporal_nr_surface_kernels.hip",
     "amt_gpu_resize.hip",
     "resize_kernels.hip",
+    "resize_surface_kernels.hip",
     "resize_plan.cpp",
     "logo_model.cpp",
     "logo_fit.cpp",

@@ -1,7 +1,9 @@
 // amt_gpu_resize.hip -- C ABI part 7: the resize in front of the temporal NR in the server's chain (BlackmanResize, Misc.cs:1423) over
 // frames resident in HBM ("parity unpinned").  The object holds the four programs (luma and chroma, horizontal and
 // vertical: resize_plan.hpp) on the host and on the device, and the intermediate of the horizontal stage, which is bounded by
-// max_scratch_bytes and not by the clip: a call works through its frames in rounds.
+// max_scratch_bytes and not by the clip: a call works through its frames in rounds.  Two entry points over one set of argument checks:
+// amtgpu_resize_run takes planar LSB planes and nothing else; amtgpu_resize_run_surfaces takes every pair of descriptors in kind and runs
+// the rule on samples (container >> shift in, result << shift out).
 #include "build_knobs.h"
 #include "../../include/amt_gpu.h"
 
@@ -20,6 +22,8 @@ struct AmtGpuResize {
     DevBuf<int> dTables;                       // the four programs' start and coeff, one behind the other
     ResizeProgramDev dprog[2][2];
     int cpw[2];                                // resize_columns_per_wave of the two horizontal programs
+    int pair_cpw;                              // resize_pair_columns_per_wave of the chroma one, for interleaved surfaces (the object's bits
+                                               // fix its container size); 0: an interleaved chroma row cannot be staged, planar ones can
     int mid_pitch[2];                          // bytes between the intermediate's rows: the row rounded up to 16
     size_t mid_plane[2], mid_frame;            // bytes of one frame's luma / one chroma plane of the intermediate, and of all three
     int round_frames;                          // frames whose intermediates fit max_scratch_bytes
@@ -31,13 +35,16 @@ const char* const kWho = "[Resize]";
 
 [[noreturn]] void refuse(const std::string& what) { throw std::runtime_error(std::string(kWho) + " " + what); }
 
-FrameBatch resize_surfaces(const AmtGpuSurfaces* s, const char* which, int width, int bits)
+// surfaces with rows of at least width (chroma: width / 2 planar, 2 * (width / 2) interleaved) containers; any_layout: of every layout
+// (amtgpu_resize_run_surfaces), else planar LSB planes only
+FrameBatch resize_surfaces(const AmtGpuSurfaces* s, const char* which, int width, int bits, bool any_layout)
 {
     const FrameBatch b = surface_batch(s, kWho);
-    if (s->interleaved || s->msb_aligned) refuse(std::string(which) + ": planar, LSB-aligned planes only (interleaved and MSB-aligned surfaces are refused)");
+    if (!any_layout && (s->interleaved || s->msb_aligned))
+        refuse(std::string(which) + ": planar, LSB-aligned planes only (interleaved and MSB-aligned surfaces are refused)");
     if (s->bits != bits) refuse(std::string(which) + ": " + std::to_string(s->bits) + " bits, the resizer was created for " + std::to_string(bits));
     if (b.strideY < 0 || b.strideUV < 0) refuse(std::string(which) + ": negative frame stride");
-    if (b.pitchY < width || b.pitchUV < width / 2) refuse(std::string(which) + ": pitch smaller than the row");
+    if (b.pitchY < width || b.pitchUV < (b.interleaved ? width : width / 2)) refuse(std::string(which) + ": pitch smaller than the row");
     return b;
 }
 
@@ -80,6 +87,7 @@ AmtGpuResize* resize_create(AmtGpuContext* c, int src_w, int src_h, int dst_w, i
         if (!r->cpw[p])
             refuse("the horizontal window of " + std::to_string(g.K) + " samples does not fit a wave's staging region (" +
                    std::to_string((kResizeRegionBytes - kResizeRegionSlack) / es) + " samples): the ratio is too small");
+        if (p) r->pair_cpw = resize_pair_columns_per_wave(g.start.data(), g.D, g.K, es);
         r->mid_pitch[p] = ((dst_w >> p) * es + 15) & ~15;
         r->mid_plane[p] = (size_t)r->mid_pitch[p] * (size_t)(src_h >> p);
     }
@@ -97,15 +105,25 @@ AmtGpuResize* resize_create(AmtGpuContext* c, int src_w, int src_h, int dst_w, i
     return r.release();
 }
 
-void resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes)
+// both entry points: any_layout is amtgpu_resize_run_surfaces, which takes every pair in kind
+void resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes, bool any_layout)
 {
     AmtGpuContext* c = r->ctx;
     if (nframes < 0) refuse("negative frame count");
     if (nframes == 0) return;
-    const FrameBatch s = resize_surfaces(src, "source", r->src_w, r->bits), t = resize_surfaces(dst, "destination", r->dst_w, r->bits);
-    const int es = s.es;
+    const FrameBatch s = resize_surfaces(src, "source", r->src_w, r->bits, any_layout), t = resize_surfaces(dst, "destination", r->dst_w, r->bits, any_layout);
+    if (s.interleaved != t.interleaved || s.shift != t.shift)
+        refuse("source and destination are not in kind (equal bits, interleaved and MSB shift): the resizer converts no layouts");
+    const int es = s.es, il = s.interleaved;
+    const bool planes = !il && !s.shift;                                               // planar LSB: the planar kernels, as before
+    if (il && !r->pair_cpw)
+        refuse("the interleaved chroma window of " + std::to_string(r->prog[1][0].K) + " pairs does not fit a wave's staging region (" +
+               std::to_string((kResizeRegionBytes - kResizePairSlack) / (2 * es)) + " pairs): the ratio is too small for interleaved surfaces");
+    // the planes of a frame: Y, U, V -- or Y and the one UV plane, whose rows are as many containers as luma rows
+    const int nplanes = il ? 2 : 3;
     struct Geometry { int w, h; };
-    const Geometry sg[2] = {{r->src_w, r->src_h}, {r->src_w / 2, r->src_h / 2}}, dg[2] = {{r->dst_w, r->dst_h}, {r->dst_w / 2, r->dst_h / 2}};
+    const Geometry sg[2] = {{r->src_w, r->src_h}, {il ? r->src_w : r->src_w / 2, r->src_h / 2}};
+    const Geometry dg[2] = {{r->dst_w, r->dst_h}, {il ? r->dst_w : r->dst_w / 2, r->dst_h / 2}};
     const long long s_stride[2] = {s.strideY, s.strideUV}, t_stride[2] = {t.strideY, t.strideUV};
     const long long s_pitch[2] = {(long long)s.pitchY * es, (long long)s.pitchUV * es}, t_pitch[2] = {(long long)t.pitchY * es, (long long)t.pitchUV * es};
     if (s_pitch[0] > INT32_MAX || s_pitch[1] > INT32_MAX || t_pitch[0] > INT32_MAX || t_pitch[1] > INT32_MAX) refuse("pitch above 2 GiB");
@@ -115,45 +133,49 @@ void resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces
     for (int k = 0; k < 2; ++k)
         if (nframes > 1 && t_stride[k] < (long long)(dg[k].h - 1) * t_pitch[k] + (long long)dg[k].w * es) refuse("destination frames overlap each other");
     Span sspan[3], dspan[3];
-    for (int p = 0; p < 3; ++p) {
+    for (int p = 0; p < nplanes; ++p) {
         const int k = p ? 1 : 0;
         sspan[p] = plane_span(sp[p], s_stride[k], s_pitch[k], sg[k].w * es, sg[k].h, nframes);
         dspan[p] = plane_span(tp[p], t_stride[k], t_pitch[k], dg[k].w * es, dg[k].h, nframes);
     }
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
+    for (int i = 0; i < nplanes; ++i)
+        for (int j = 0; j < nplanes; ++j)
             if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place resize)");
 
     c->bind();
     const int round = std::min(r->round_frames, nframes);
     const size_t need = r->mid_frame * (size_t)round;
     if (r->dMid.size() < need) r->dMid.alloc(need);      // (hipFree waits for the kernels that still use the old intermediate)
-    // one round's intermediate: [round] luma planes, then [round] U planes, then [round] V planes
-    uint8_t* const mid[3] = {r->dMid.get(), r->dMid.get() + r->mid_plane[0] * round, r->dMid.get() + (r->mid_plane[0] + r->mid_plane[1]) * round};
+    // one round's intermediate: [round] luma planes, then [round] U planes, then [round] V planes -- or, interleaved, [round] UV planes of
+    // the luma pitch, which is at most two chroma pitches: a frame's intermediate is no larger than the planar one
+    const int mid_pitch[2] = {r->mid_pitch[0], il ? r->mid_pitch[0] : r->mid_pitch[1]};
+    const size_t mid_plane[2] = {r->mid_plane[0], il ? (size_t)r->mid_pitch[0] * (size_t)(r->src_h / 2) : r->mid_plane[1]};
+    uint8_t* const mid[3] = {r->dMid.get(), r->dMid.get() + mid_plane[0] * round, il ? nullptr : r->dMid.get() + (mid_plane[0] + mid_plane[1]) * round};
     const RowsAt srcY{lane_addr(s.Y), 0, s_stride[0], s_pitch[0]}, srcUV{lane_addr(s.U), lane_addr(s.V), s_stride[1], s_pitch[1]};
     const RowsAt dstY{lane_addr(t.Y), 0, t_stride[0], t_pitch[0]}, dstUV{lane_addr(t.U), lane_addr(t.V), t_stride[1], t_pitch[1]};
-    const RowsAt midY{lane_addr(mid[0]), 0, (long long)r->mid_plane[0], r->mid_pitch[0]}, midUV{lane_addr(mid[1]), lane_addr(mid[2]), (long long)r->mid_plane[1], r->mid_pitch[1]};
+    const RowsAt midY{lane_addr(mid[0]), 0, (long long)mid_plane[0], mid_pitch[0]}, midUV{lane_addr(mid[1]), lane_addr(mid[2]), (long long)mid_plane[1], mid_pitch[1]};
     ResizeStageArgs h{}, v{};
     h.es = v.es = es;
     h.maxv = v.maxv = (1 << r->bits) - 1;
-    h.vec = v.vec = resize_vec16(srcY, srcUV, midY, midUV, dstY, dstUV);
+    // (an interleaved batch has null V planes, which count as aligned: surface_batch drops whatever the descriptor holds there)
+    h.vec = v.vec = planes ? resize_vec16(srcY, srcUV, midY, midUV, dstY, dstUV) : resize_surface_vec16(srcY, srcUV, midY, midUV, dstY, dstUV);
     for (int k = 0; k < 2; ++k) {
         h.prog[k] = r->dprog[k][0]; v.prog[k] = r->dprog[k][1];
         h.lines[k] = sg[k].h; v.lines[k] = dg[k].w;
-        h.cpw[k] = r->cpw[k]; v.cpw[k] = 0;
+        h.cpw[k] = k && il ? r->pair_cpw : r->cpw[k]; v.cpw[k] = 0;
     }
     for (int first = 0; first < nframes; first += round) {
         const int n = std::min(round, nframes - first);
-        for (int p = 0; p < 3; ++p) {
+        for (int p = 0; p < nplanes; ++p) {
             const int k = p ? 1 : 0;
-            h.plane[p] = ResizePlaneArgs{(const uint8_t*)sp[p] + (long long)first * s_stride[k], mid[p], s_stride[k], (long long)r->mid_plane[k], (int)s_pitch[k], r->mid_pitch[k]};
-            v.plane[p] = ResizePlaneArgs{mid[p], (uint8_t*)tp[p] + (long long)first * t_stride[k], (long long)r->mid_plane[k], t_stride[k], r->mid_pitch[k], (int)t_pitch[k]};
+            h.plane[p] = ResizePlaneArgs{(const uint8_t*)sp[p] + (long long)first * s_stride[k], mid[p], s_stride[k], (long long)mid_plane[k], (int)s_pitch[k], mid_pitch[k]};
+            v.plane[p] = ResizePlaneArgs{mid[p], (uint8_t*)tp[p] + (long long)first * t_stride[k], (long long)mid_plane[k], t_stride[k], mid_pitch[k], (int)t_pitch[k]};
         }
-        const int s1 = c->prof_begin("resize_h_kernel");
-        AMT_HIP(launch_resize_h(c->stream, h, n));
+        const int s1 = c->prof_begin(planes ? "resize_h_kernel" : "resize_surface_h_kernel");
+        AMT_HIP(planes ? launch_resize_h(c->stream, h, n) : launch_resize_surfaces_h(c->stream, h, il, s.shift, n));
         c->prof_end(s1);
-        const int s2 = c->prof_begin("resize_v_kernel");
-        AMT_HIP(launch_resize_v(c->stream, v, n));
+        const int s2 = c->prof_begin(planes ? "resize_v_kernel" : "resize_surface_v_kernel");
+        AMT_HIP(planes ? launch_resize_v(c->stream, v, n) : launch_resize_surfaces_v(c->stream, v, il, s.shift, n));
         c->prof_end(s2);
     }
     AMT_HIP(hipStreamSynchronize(c->stream));            // as amtgpu_temporal_nr: dst is ready when the call returns
@@ -184,7 +206,13 @@ void amtgpu_resize_destroy(AmtGpuResize* r) { delete r; }
 int amtgpu_resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes)
 {
     if (!r) return 0;
-    return guard(r->ctx, [&] { resize_run(r, src, dst, nframes); });
+    return guard(r->ctx, [&] { resize_run(r, src, dst, nframes, false); });
+}
+
+int amtgpu_resize_run_surfaces(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes)
+{
+    if (!r) return 0;
+    return guard(r->ctx, [&] { resize_run(r, src, dst, nframes, true); });
 }
 
 int amtgpu_resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int* start, int* coeff)

@@ -173,6 +173,14 @@ struct ResizeStageArgs {
 // One launch each; none when nframes <= 0.  a.plane[].src of the vertical stage is the horizontal stage's dst
 hipError_t launch_resize_h(hipStream_t st, const ResizeStageArgs& a, int nframes);
 hipError_t launch_resize_v(hipStream_t st, const ResizeStageArgs& a, int nframes);
+// resize_surface_kernels.hip: the same stages on decoder surfaces, source and destination in kind (planar LSB planes -- neither
+// interleaved nor shift -- are refused: they are the launchers' above).  The intermediate holds LSB samples.  interleaved: a frame is
+// two planes, plane[0] = Y and plane[1] = UV, whose rows are pairs -- the horizontal stage's prog[1] and lines[1] are the chroma plane's
+// as above and its cpw[1] is resize_pair_columns_per_wave's (1..32); the vertical stage's lines[1] is the UV row's containers, twice the
+// chroma width.  shift = 16 - bits where MSB-aligned: the horizontal stage reads container >> shift, the vertical stage stores
+// result << shift.  a.vec: resize_surface_vec16 (lane_rule.h)
+hipError_t launch_resize_surfaces_h(hipStream_t st, const ResizeStageArgs& a, int interleaved, int shift, int nframes);
+hipError_t launch_resize_surfaces_v(hipStream_t st, const ResizeStageArgs& a, int interleaved, int shift, int nframes);
 
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 // Both take a luma batch of either alignment: b.shift != 0 (16-bit containers, shift = 16 - bits) runs the same sums on container >> shift,

@@ -98,4 +98,13 @@ inline int resize_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& m
     return lane_divides(16, srcY.bits() | srcUV.bits() | midY.bits() | midUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
 }
 
+// resize_surface_h_kernel / resize_surface_v_kernel: the same two stages on decoder surfaces.  Interleaved, the UV plane is one plane
+// whose rows are staged and walked 16 bytes at a time like any other (base2 is 0: there is no V plane, and a null plane counts as
+// aligned); planar MSB, the rule above.  So: every row of every plane of the source, the intermediate and the destination 16-byte
+// aligned, else container by container
+inline int resize_surface_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& midY, const RowsAt& midUV, const RowsAt& dstY, const RowsAt& dstUV)
+{
+    return lane_divides(16, srcY.bits() | srcUV.bits() | midY.bits() | midUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
+}
+
 } // namespace amt

@@ -115,4 +115,17 @@ int resize_columns_per_wave(const int* start, int D, int K, int es)
     return 0;
 }
 
+int resize_pair_columns_per_wave(const int* start, int D, int K, int es)
+{
+    for (int cpw = 32; cpw >= 1; cpw >>= 1) {
+        bool fits = true;
+        for (int c0 = 0; c0 < D && fits; c0 += cpw) {
+            const int last = (c0 + cpw < D ? c0 + cpw : D) - 1;
+            fits = (long long)(start[last] + K - start[c0]) * 2 * es + kResizePairSlack <= kResizeRegionBytes;
+        }
+        if (fits) return cpw;
+    }
+    return 0;
+}
+
 } // namespace amt

@@ -789,6 +789,17 @@ int  amtgpu_temporal_nr_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* src, 
  *   other in a plane; a destination plane whose byte range (first byte of frame 0 .. last byte of frame nframes - 1) overlaps a source
  *   plane's.  nframes == 0 returns 1.  Reads nothing outside a row's width of a source row, writes nothing outside it in a destination
  *   row; the source is never written.  All rounds run in the context's stream.  Synchronises, as amtgpu_temporal_nr does.
+ * amtgpu_resize_run_surfaces: the same object, rounds, scratch bound and checks on decoder surfaces where they lie, source and
+ *   destination IN KIND: equal bits (the resizer's), interleaved and msb_aligned -- NV12, interleaved LSB, P010 / P012 / P016, planar MSB.
+ *   With s = msb_aligned ? 16 - bits : 0, U the even and V the odd container of a UV row: a sample is container >> s (the source's low
+ *   bits are dropped on the way in); the rule above runs on the samples, every plane on its own, chroma per component with the chroma
+ *   programs; every destination container is result << s.  The resize copies no row, so no low bit survives, at equal sizes either (the
+ *   program is then a single 16384).  Hence dst >> s, de-interleaved, is amtgpu_resize_run of src >> s, de-interleaved, byte for byte,
+ *   whatever the low bits hold and however the call is cut into rounds.  A planar LSB pair runs amtgpu_resize_run's kernels and gives
+ *   its bytes.  An interleaved UV row is `width` containers, and pitchUV at least that.  Returns 0 with a message on ctx, and launches
+ *   nothing: what amtgpu_resize_run refuses, the layout apart; a pair that is not in kind (no layout is converted); on interleaved
+ *   surfaces, a chroma window whose K pairs of 2 containers do not fit the staging region (2000 bytes: half the samples a planar chroma
+ *   row may take -- such an object still runs planar surfaces).  An addition; the ABI version stays 5.
  * amtgpu_resize_get_program: K, start[D] and coeff[D * K] of plane 0 (luma) / 1 (chroma), axis 0 (horizontal) / 1 (vertical); start and
  *   coeff may be NULL, so that a caller can ask for K first (D is the destination size of that plane and axis) */
 typedef struct AmtGpuResize AmtGpuResize;
@@ -800,6 +811,7 @@ AmtGpuResize* amtgpu_resize_create(AmtGpuContext* ctx, int src_w, int src_h, int
                                    int64_t max_scratch_bytes);
 void amtgpu_resize_destroy(AmtGpuResize* r);
 int  amtgpu_resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes);
+int  amtgpu_resize_run_surfaces(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes);
 int  amtgpu_resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int* start, int* coeff);
 
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
