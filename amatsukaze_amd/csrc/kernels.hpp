@@ -140,7 +140,20 @@ struct TemporalNRArgs {
     int d, thresh, interlaced;                                       // thresh: threshold << (bits - 8)
     int first, lo, hi;
 };
-// One launch; none when nout <= 0
+// The grid of both launchers below: a cell is one lane's columns (16 bytes where a.vec, else two) of a chroma row and of the two luma
+// rows that map to it, a block 256 consecutive cells of one output frame.  False where an argument or the grid is out of range
+struct TemporalNRGrid { int cells_per_row, blocks_per_frame; unsigned blocks; };
+inline bool temporal_nr_grid(const TemporalNRArgs& a, int nout, TemporalNRGrid& g)
+{
+    if ((a.es != 1 && a.es != 2) || a.d < 0 || a.d > 63 || a.W <= 0 || a.H <= 0 || (a.W & 1) || (a.H & 1)) return false;
+    const int px = a.vec ? 16 / a.es : 2;
+    const long long cells_per_row = (a.W + px - 1) / px, cells = cells_per_row * (a.H >> 1);
+    const long long blocks_per_frame = (cells + 255) / 256;
+    if (cells > 0x7FFFFF00LL || blocks_per_frame * nout > 0x7FFFFFFFLL) return false;
+    g = TemporalNRGrid{(int)cells_per_row, (int)blocks_per_frame, (unsigned)(blocks_per_frame * nout)};
+    return true;
+}
+// One launch; none when nout <= 0.  The cell both kernel files instantiate is temporal_nr_body.h's
 hipError_t launch_temporal_nr(hipStream_t st, const TemporalNRArgs& a, int nout);
 // temporal_nr_surface_kernels.hip: the same frames on decoder surfaces, source and destination in kind (planar LSB planes -- neither
 // interleaved nor shift -- are refused: they are the launcher's above).  interleaved: srcU / dstU are the UV planes, U the even and V the
@@ -174,7 +187,8 @@ struct ResizeStageArgs {
 hipError_t launch_resize_h(hipStream_t st, const ResizeStageArgs& a, int nframes);
 hipError_t launch_resize_v(hipStream_t st, const ResizeStageArgs& a, int nframes);
 // resize_surface_kernels.hip: the same stages on decoder surfaces, source and destination in kind (planar LSB planes -- neither
-// interleaved nor shift -- are refused: they are the launchers' above).  The intermediate holds LSB samples.  interleaved: a frame is
+// interleaved nor shift -- are refused: they are the launchers' above; what the two files share, the four launchers' argument check
+// and grids included, is resize_body.h).  The intermediate holds LSB samples.  interleaved: a frame is
 // two planes, plane[0] = Y and plane[1] = UV, whose rows are pairs -- the horizontal stage's prog[1] and lines[1] are the chroma plane's
 // as above and its cpw[1] is resize_pair_columns_per_wave's (1..32); the vertical stage's lines[1] is the UV row's containers, twice the
 // chroma width.  shift = 16 - bits where MSB-aligned: the horizontal stage reads container >> shift, the vertical stage stores

@@ -74,19 +74,18 @@ inline int render_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& d
     return lane_divides(16, srcY.bits() | srcUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
 }
 
-// temporal_nr_kernel: a lane takes 16 bytes of two luma rows and the 8 bytes of each chroma row under them, where every luma row starts
-// 16-byte aligned and every chroma row 8-byte aligned (a row's last containers go two luma columns at a time, so the row length is no
-// operand); otherwise it goes container by container
-inline int temporal_nr_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& dstY, const RowsAt& dstUV)
-{
-    return lane_divides(16, srcY.bits() | dstY.bits()) && lane_divides(8, srcUV.bits() | dstUV.bits()) ? 1 : 0;
-}
-
-// temporal_nr_surfaces_kernel: the same lane on decoder surfaces.  Interleaved, the chroma under a lane's 16 luma bytes is one 16-byte
-// run of the UV row, so every UV row starts 16-byte aligned as well (base2 is 0: there is no V plane); planar, the rule above
+// temporal_nr_surfaces_kernel: a lane takes 16 bytes of two luma rows and the chroma under them, where every luma row starts 16-byte
+// aligned and so does what the lane takes of a chroma row: planar, an 8-byte run of the U and of the V row, so 8 bytes; interleaved, one
+// 16-byte run of the UV row (base2 is 0: there is no V plane).  A row's last containers go two luma columns at a time, so the row length
+// is no operand; otherwise the kernel goes container by container
 inline int temporal_nr_surface_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& dstY, const RowsAt& dstUV, int interleaved)
 {
     return lane_divides(16, srcY.bits() | dstY.bits()) && lane_divides(interleaved ? 16 : 8, srcUV.bits() | dstUV.bits()) ? 1 : 0;
+}
+// temporal_nr_kernel: planar planes
+inline int temporal_nr_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& dstY, const RowsAt& dstUV)
+{
+    return temporal_nr_surface_vec16(srcY, srcUV, dstY, dstUV, 0);
 }
 
 // resize_h_kernel / resize_v_kernel: every plane goes on its own, so chroma rows are held to what luma rows are.  The horizontal stage
@@ -98,13 +97,11 @@ inline int resize_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& m
     return lane_divides(16, srcY.bits() | srcUV.bits() | midY.bits() | midUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
 }
 
-// resize_surface_h_kernel / resize_surface_v_kernel: the same two stages on decoder surfaces.  Interleaved, the UV plane is one plane
-// whose rows are staged and walked 16 bytes at a time like any other (base2 is 0: there is no V plane, and a null plane counts as
-// aligned); planar MSB, the rule above.  So: every row of every plane of the source, the intermediate and the destination 16-byte
-// aligned, else container by container
+// resize_surface_h_kernel / resize_surface_v_kernel: the same rule.  An interleaved UV plane is one plane whose rows are staged and
+// walked 16 bytes at a time like any other (base2 is 0: there is no V plane, and a null plane counts as aligned)
 inline int resize_surface_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& midY, const RowsAt& midUV, const RowsAt& dstY, const RowsAt& dstUV)
 {
-    return lane_divides(16, srcY.bits() | srcUV.bits() | midY.bits() | midUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
+    return resize_vec16(srcY, srcUV, midY, midUV, dstY, dstUV);
 }
 
 } // namespace amt

@@ -14,26 +14,15 @@
 // Vertical: a wave owns 64 lanes' worth of one output row, so the row's start and coefficients are wave-uniform and come through the
 // scalar unit; a lane owns 16 bytes of the row and walks the K intermediate rows under it with 16-byte loads (a row's last containers,
 // and everything where resize_vec16 does not hold, go container by container).  No LDS.
-// Frame offsets are 64-bit.
+// Frame offsets are 64-bit.  What the decoder-surface kernels share with these is in resize_body.h.
 #include "build_knobs.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "kernels.hpp"
+#include "resize_body.h"
 
 namespace amt {
-
-__device__ __forceinline__ int resize_mad(int c, unsigned s, int acc) { return __mul24(c, (int)s) + acc; }
-__device__ __forceinline__ int resize_round(int acc, int maxv) { return min(max((acc + 8192) >> 14, 0), maxv); }
-
-// which plane, and which of its items, the item `r` of a frame is: luma items first, then U's, then V's
-struct ResizeItem { int plane, r; };
-__device__ __forceinline__ ResizeItem resize_item(int r, int itemsY, int itemsC)
-{
-    // (wave-uniform, and said so: the plane number indexes the kernel's arguments, which is then scalar address arithmetic)
-    const int plane = r < itemsY ? 0 : r < itemsY + itemsC ? 1 : 2;
-    return ResizeItem{__builtin_amdgcn_readfirstlane(plane), __builtin_amdgcn_readfirstlane(r - (plane == 0 ? 0 : plane == 1 ? itemsY : itemsY + itemsC))};
-}
 
 // ---- horizontal ----
 // KR: taps a lane keeps in registers (K <= KR, the rest zero); 0: the lane reads its coefficients from the table, tap by tap
@@ -97,6 +86,7 @@ void resize_h_kernel(ResizeStageArgs a, int runsY, int bandsY, int runsC, int ba
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // (the tap loop stays written out: through resize_surface_kernels.hip's resize_taps it compiled to other instructions)
         int acc = 0;
         if constexpr (KR > 0) {
 #pragma unroll
@@ -112,33 +102,14 @@ void resize_h_kernel(ResizeStageArgs a, int runsY, int bandsY, int runsC, int ba
     }
 }
 
-static bool resize_args_ok(const ResizeStageArgs& a)
-{
-    if ((a.es != 1 && a.es != 2) || a.maxv < 255 || a.maxv > 65535) return false;
-    for (int k = 0; k < 2; ++k)
-        if (!a.prog[k].start || !a.prog[k].coeff || a.prog[k].S <= 0 || a.prog[k].D <= 0 || a.prog[k].K <= 0 || a.prog[k].K > a.prog[k].S || a.lines[k] <= 0 ||
-            a.prog[k].S >= (1 << 23) || a.prog[k].D >= (1 << 23))
-            return false;
-    for (int p = 0; p < 3; ++p)
-        if (!a.plane[p].src || !a.plane[p].dst || a.plane[p].src_pitch <= 0 || a.plane[p].dst_pitch <= 0) return false;
-    return true;
-}
-
 hipError_t launch_resize_h(hipStream_t st, const ResizeStageArgs& a, int nframes)
 {
     if (nframes <= 0) return hipSuccess;
-    if (!resize_args_ok(a) || nframes > 65535) return hipErrorInvalidValue;
-    long long runs[2], bands[2];
-    for (int k = 0; k < 2; ++k) {
-        if (a.cpw[k] < 1 || a.cpw[k] > 64) return hipErrorInvalidValue;
-        runs[k] = (a.prog[k].D + a.cpw[k] - 1) / a.cpw[k];
-        bands[k] = (a.lines[k] + kResizeRows - 1) / kResizeRows;
-    }
-    const long long items = runs[0] * bands[0] + 2 * runs[1] * bands[1];
-    if (items > 0x7FFFFF00LL) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((items + kResizeWaves - 1) / kResizeWaves), (unsigned)nframes), block(64 * kResizeWaves);
+    ResizeGrid g;
+    if (!resize_grid(a, true, 2, 0, nframes, g)) return hipErrorInvalidValue;
+    const dim3 block(64 * kResizeWaves);
     const int K = a.prog[0].K > a.prog[1].K ? a.prog[0].K : a.prog[1].K;
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, (int)runs[0], (int)bands[0], (int)runs[1], (int)bands[1]); };
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, g.grid, block, 0, st, a, g.per[0], g.across[0], g.per[1], g.across[1]); };
     with_sample_type(a.es == 1 ? 8 : 16, [&](auto pix) {
         using T = decltype(pix);
         if (K <= 8) go(resize_h_kernel<T, 8>);
@@ -150,52 +121,6 @@ hipError_t launch_resize_h(hipStream_t st, const ResizeStageArgs& a, int nframes
 }
 
 // ---- vertical ----
-// N containers at p as integers: one 16-byte access (VEC) or one container
-template <typename T, int N>
-__device__ __forceinline__ void resize_load(const uint8_t* p, unsigned (&o)[N])
-{
-    if constexpr (N == 1) {
-        o[0] = *reinterpret_cast<const T*>(p);
-    } else {
-        static_assert(N * sizeof(T) == 16, "a vector lane moves 16 bytes");
-        constexpr int PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < N; ++j) o[j] = (w[j / PER] >> (BITS * (j % PER))) & ((1u << BITS) - 1);
-    }
-}
-
-template <typename T, int N>
-__device__ __forceinline__ void resize_store(uint8_t* p, const int (&acc)[N], int maxv)
-{
-    if constexpr (N == 1) {
-        *reinterpret_cast<T*>(p) = (T)resize_round(acc[0], maxv);
-    } else {
-        constexpr int PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
-        unsigned w[4] = {};
-#pragma unroll
-        for (int j = 0; j < N; ++j) w[j / PER] |= (unsigned)resize_round(acc[j], maxv) << (BITS * (j % PER));
-        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-// N containers of an output row from the K rows at src, src_pitch apart; cf: the row's coefficients (wave-uniform)
-template <typename T, int N>
-__device__ __forceinline__ void resize_v_cell(const uint8_t* src, int src_pitch, const int* cf, int K, int maxv, uint8_t* dst)
-{
-    int acc[N] = {};
-#pragma unroll 4
-    for (int j = 0; j < K; ++j, src += src_pitch) {
-        const int c = cf[j];
-        unsigned s[N];
-        resize_load<T, N>(src, s);
-#pragma unroll
-        for (int n = 0; n < N; ++n) acc[n] = resize_mad(c, s[n], acc[n]);
-    }
-    resize_store<T, N>(dst, acc, maxv);
-}
-
 // VEC: resize_vec16 (lane_rule.h).  chunks: waves per output row of the luma / chroma planes
 template <typename T, bool VEC>
 __global__ __launch_bounds__(64 * kResizeWaves)
@@ -220,25 +145,21 @@ void resize_v_kernel(ResizeStageArgs a, int chunksY, int chunksC)
     const uint8_t* src = pa.src + f * pa.src_stride + (long long)P.start[y] * pa.src_pitch + (long long)x0 * ES;
     uint8_t* dst = pa.dst + f * pa.dst_stride + (long long)y * pa.dst_pitch + (long long)x0 * ES;
     if constexpr (VEC) {
-        if (x0 + PX <= W) { resize_v_cell<T, PX>(src, pa.src_pitch, cf, K, a.maxv, dst); return; }
+        if (x0 + PX <= W) { resize_v_cell<T, PX, false>(src, pa.src_pitch, cf, K, a.maxv, dst, 0); return; }
 #pragma unroll 1
-        for (int x = x0; x < W; ++x, src += ES, dst += ES) resize_v_cell<T, 1>(src, pa.src_pitch, cf, K, a.maxv, dst);
+        for (int x = x0; x < W; ++x, src += ES, dst += ES) resize_v_cell<T, 1, false>(src, pa.src_pitch, cf, K, a.maxv, dst, 0);
     } else {
-        resize_v_cell<T, 1>(src, pa.src_pitch, cf, K, a.maxv, dst);
+        resize_v_cell<T, 1, false>(src, pa.src_pitch, cf, K, a.maxv, dst, 0);
     }
 }
 
 hipError_t launch_resize_v(hipStream_t st, const ResizeStageArgs& a, int nframes)
 {
     if (nframes <= 0) return hipSuccess;
-    if (!resize_args_ok(a) || nframes > 65535) return hipErrorInvalidValue;
-    const int px = a.vec ? 16 / a.es : 1;
-    long long chunks[2];
-    for (int k = 0; k < 2; ++k) chunks[k] = ((a.lines[k] + px - 1) / px + 63) / 64;
-    const long long items = chunks[0] * a.prog[0].D + 2 * chunks[1] * a.prog[1].D;
-    if (items > 0x7FFFFF00LL) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((items + kResizeWaves - 1) / kResizeWaves), (unsigned)nframes), block(64 * kResizeWaves);
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, (int)chunks[0], (int)chunks[1]); };
+    ResizeGrid g;
+    if (!resize_grid(a, false, 2, 0, nframes, g)) return hipErrorInvalidValue;
+    const dim3 block(64 * kResizeWaves);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, g.grid, block, 0, st, a, g.per[0], g.per[1]); };
     with_sample_type(a.es == 1 ? 8 : 16, [&](auto pix) {
         using T = decltype(pix);
         if (a.vec) go(resize_v_kernel<T, true>);

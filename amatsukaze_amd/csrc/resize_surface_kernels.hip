@@ -11,40 +11,31 @@
 // once, packed, before the LDS write (the container-by-container path shifts per container), so the taps are read as samples.
 // Vertical: layout-agnostic -- an interleaved frame is two planes, Y and UV of dst_w containers under the chroma program.  It is the
 // planar cell with one packed left shift per stored dword where MSB.
-// The bodies below repeat resize_kernels.hip's, as temporal_nr_surface_kernels.hip repeats its planar kernel's and for the same reason:
-// the planar file is to compile to the instructions it had.
+// The rounding, the dealing of items, the vertical cell and the launchers' checks are resize_body.h's.  The two kernel bodies below
+// repeat resize_kernels.hip's line for line where they can: one body called from both files' kernels changed the planar instructions.
 #include "build_knobs.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "kernels.hpp"
 #include "pack16.h"
+#include "resize_body.h"
 
 namespace amt {
 
-__device__ __forceinline__ int resize_surface_mad(int c, unsigned s, int acc) { return __mul24(c, (int)s) + acc; }
-__device__ __forceinline__ int resize_surface_round(int acc, int maxv) { return min(max((acc + 8192) >> 14, 0), maxv); }
-
-// which plane, and which of its items, the item `r` of a frame is: luma items first, then U's (or UV's), then V's
-struct ResizeSurfaceItem { int plane, r; };
-__device__ __forceinline__ ResizeSurfaceItem resize_surface_item(int r, int itemsY, int itemsC)
-{
-    const int plane = r < itemsY ? 0 : r < itemsY + itemsC ? 1 : 2;
-    return ResizeSurfaceItem{__builtin_amdgcn_readfirstlane(plane), __builtin_amdgcn_readfirstlane(r - (plane == 0 ? 0 : plane == 1 ? itemsY : itemsY + itemsC))};
-}
-
 // ---- horizontal ----
-// the K taps of a lane, STEP containers apart in the staged span (2: one component of an interleaved row)
+// the K taps of a lane, STEP containers apart in the staged span (2: one component of an interleaved row).  (resize_h_kernel keeps its
+// loop written out: sharing this helper changed the planar instructions)
 template <typename T, int KR, int STEP>
-__device__ __forceinline__ int resize_surface_taps(const T* taps, const int (&c)[KR > 0 ? KR : 1], const int* cf, int K)
+__device__ __forceinline__ int resize_taps(const T* taps, const int (&c)[KR > 0 ? KR : 1], const int* cf, int K)
 {
     int acc = 0;
     if constexpr (KR > 0) {
 #pragma unroll
-        for (int j = 0; j < KR; ++j) acc = resize_surface_mad(c[j], taps[j * STEP], acc);
+        for (int j = 0; j < KR; ++j) acc = resize_mad(c[j], taps[j * STEP], acc);
     } else {
 #pragma unroll 4
-        for (int j = 0; j < K; ++j) acc = resize_surface_mad(cf[j], taps[j * STEP], acc);
+        for (int j = 0; j < K; ++j) acc = resize_mad(cf[j], taps[j * STEP], acc);
     }
     return acc;
 }
@@ -63,7 +54,7 @@ void resize_surface_h_kernel(ResizeStageArgs a, int runsY, int bandsY, int runsC
     const int itemsY = runsY * bandsY, itemsC = runsC * bandsC;
     const int item = blockIdx.x * kResizeWaves + wave;
     if (item >= itemsY + NC * itemsC) return;
-    const ResizeSurfaceItem it = resize_surface_item(item, itemsY, itemsC);
+    const ResizeItem it = resize_item(item, itemsY, itemsC);
     const bool chroma = it.plane != 0, pairs = IL && chroma;             // (wave-uniform)
     const int runs = chroma ? runsC : runsY;
     const int band = it.r / runs, run = it.r - band * runs;
@@ -124,47 +115,26 @@ void resize_surface_h_kernel(ResizeStageArgs a, int runsY, int bandsY, int runsC
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         int acc;
         if constexpr (IL) {
-            acc = pairs ? resize_surface_taps<T, KR, 2>(taps, c, cf, K) : resize_surface_taps<T, KR, 1>(taps, c, cf, K);
+            acc = pairs ? resize_taps<T, KR, 2>(taps, c, cf, K) : resize_taps<T, KR, 1>(taps, c, cf, K);
         } else {
-            acc = resize_surface_taps<T, KR, 1>(taps, c, cf, K);
+            acc = resize_taps<T, KR, 1>(taps, c, cf, K);
         }
-        if (active) *reinterpret_cast<T*>(drow) = (T)resize_surface_round(acc, a.maxv);           // (the intermediate holds LSB samples)
+        if (active) *reinterpret_cast<T*>(drow) = (T)resize_round(acc, a.maxv);           // (the intermediate holds LSB samples)
         // ... and the next row's staging must stay behind these reads
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-// (an interleaved frame has two planes, Y and UV: plane[2] is not looked at)
-static bool resize_surface_args_ok(const ResizeStageArgs& a, int interleaved, int shift)
-{
-    if ((a.es != 1 && a.es != 2) || a.maxv < 255 || a.maxv > 65535) return false;
-    if (shift < 0 || shift > 7 || (shift && a.es != 2)) return false;
-    if (!interleaved && !shift) return false;                                            // planar LSB planes are launch_resize_h's and _v's
-    for (int k = 0; k < 2; ++k)
-        if (!a.prog[k].start || !a.prog[k].coeff || a.prog[k].S <= 0 || a.prog[k].D <= 0 || a.prog[k].K <= 0 || a.prog[k].K > a.prog[k].S || a.lines[k] <= 0 ||
-            a.prog[k].S >= (1 << 23) || a.prog[k].D >= (1 << 23))
-            return false;
-    for (int p = 0; p < (interleaved ? 2 : 3); ++p)
-        if (!a.plane[p].src || !a.plane[p].dst || a.plane[p].src_pitch <= 0 || a.plane[p].dst_pitch <= 0) return false;
-    return true;
-}
-
 hipError_t launch_resize_surfaces_h(hipStream_t st, const ResizeStageArgs& a, int interleaved, int shift, int nframes)
 {
     if (nframes <= 0) return hipSuccess;
-    if (!resize_surface_args_ok(a, interleaved, shift) || nframes > 65535) return hipErrorInvalidValue;
-    long long runs[2], bands[2];
-    for (int k = 0; k < 2; ++k) {
-        if (a.cpw[k] < 1 || a.cpw[k] > (k && interleaved ? 32 : 64)) return hipErrorInvalidValue;
-        runs[k] = (a.prog[k].D + a.cpw[k] - 1) / a.cpw[k];
-        bands[k] = (a.lines[k] + kResizeRows - 1) / kResizeRows;
-    }
-    const long long items = runs[0] * bands[0] + (interleaved ? 1 : 2) * runs[1] * bands[1];
-    if (items > 0x7FFFFF00LL) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((items + kResizeWaves - 1) / kResizeWaves), (unsigned)nframes), block(64 * kResizeWaves);
+    if (!interleaved && !shift) return hipErrorInvalidValue;                             // planar LSB planes are launch_resize_h's
+    ResizeGrid g;
+    if (!resize_grid(a, true, interleaved ? 1 : 2, shift, nframes, g)) return hipErrorInvalidValue;
+    const dim3 block(64 * kResizeWaves);
     const int K = a.prog[0].K > a.prog[1].K ? a.prog[0].K : a.prog[1].K;
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, (int)runs[0], (int)bands[0], (int)runs[1], (int)bands[1], shift); };
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, g.grid, block, 0, st, a, g.per[0], g.across[0], g.per[1], g.across[1], shift); };
 #define AMT_RESIZE_SURFACE_H(T, MSB, IL)                                  \
     do {                                                                  \
         if (K <= 8) go(resize_surface_h_kernel<T, 8, MSB, IL>);           \
@@ -181,58 +151,6 @@ hipError_t launch_resize_surfaces_h(hipStream_t st, const ResizeStageArgs& a, in
 }
 
 // ---- vertical ----
-// N containers of the intermediate (LSB samples) at p as integers: one 16-byte access (VEC) or one container
-template <typename T, int N>
-__device__ __forceinline__ void resize_surface_load(const uint8_t* p, unsigned (&o)[N])
-{
-    if constexpr (N == 1) {
-        o[0] = *reinterpret_cast<const T*>(p);
-    } else {
-        static_assert(N * sizeof(T) == 16, "a vector lane moves 16 bytes");
-        constexpr int PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < N; ++j) o[j] = (w[j / PER] >> (BITS * (j % PER))) & ((1u << BITS) - 1);
-    }
-}
-
-// ... and N results as containers, result << shift where MSB: one packed shift per stored dword
-template <typename T, int N, bool MSB>
-__device__ __forceinline__ void resize_surface_store(uint8_t* p, const int (&acc)[N], int maxv, int shift)
-{
-    if constexpr (N == 1) {
-        const int v = resize_surface_round(acc[0], maxv);
-        *reinterpret_cast<T*>(p) = MSB ? (T)(v << shift) : (T)v;
-    } else {
-        constexpr int PER = 4 / (int)sizeof(T), BITS = 8 * (int)sizeof(T);
-        unsigned w[4] = {};
-#pragma unroll
-        for (int j = 0; j < N; ++j) w[j / PER] |= (unsigned)resize_surface_round(acc[j], maxv) << (BITS * (j % PER));
-        if constexpr (MSB) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) w[i] = pk_shl16(w[i], shift);
-        }
-        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-// N containers of an output row from the K rows at src, src_pitch apart; cf: the row's coefficients (wave-uniform)
-template <typename T, int N, bool MSB>
-__device__ __forceinline__ void resize_surface_v_cell(const uint8_t* src, int src_pitch, const int* cf, int K, int maxv, int shift, uint8_t* dst)
-{
-    int acc[N] = {};
-#pragma unroll 4
-    for (int j = 0; j < K; ++j, src += src_pitch) {
-        const int c = cf[j];
-        unsigned s[N];
-        resize_surface_load<T, N>(src, s);
-#pragma unroll
-        for (int n = 0; n < N; ++n) acc[n] = resize_surface_mad(c, s[n], acc[n]);
-    }
-    resize_surface_store<T, N, MSB>(dst, acc, maxv, shift);
-}
-
 // VEC: resize_surface_vec16 (lane_rule.h).  chunks: waves per output row of the luma / chroma planes; nc: chroma planes (1: the UV plane)
 template <typename T, bool VEC, bool MSB>
 __global__ __launch_bounds__(64 * kResizeWaves)
@@ -244,7 +162,7 @@ void resize_surface_v_kernel(ResizeStageArgs a, int chunksY, int chunksC, int nc
     const int itemsY = a.prog[0].D * chunksY, itemsC = a.prog[1].D * chunksC;
     const int item = blockIdx.x * kResizeWaves + wave;
     if (item >= itemsY + nc * itemsC) return;
-    const ResizeSurfaceItem it = resize_surface_item(item, itemsY, itemsC);
+    const ResizeItem it = resize_item(item, itemsY, itemsC);
     const bool chroma = it.plane != 0;
     const int chunks = chroma ? chunksC : chunksY;
     const int y = it.r / chunks, chunk = it.r - y * chunks;
@@ -258,25 +176,23 @@ void resize_surface_v_kernel(ResizeStageArgs a, int chunksY, int chunksC, int nc
     const uint8_t* src = pa.src + f * pa.src_stride + (long long)P.start[y] * pa.src_pitch + (long long)x0 * ES;
     uint8_t* dst = pa.dst + f * pa.dst_stride + (long long)y * pa.dst_pitch + (long long)x0 * ES;
     if constexpr (VEC) {
-        if (x0 + PX <= W) { resize_surface_v_cell<T, PX, MSB>(src, pa.src_pitch, cf, K, a.maxv, shift, dst); return; }
+        if (x0 + PX <= W) { resize_v_cell<T, PX, MSB>(src, pa.src_pitch, cf, K, a.maxv, dst, shift); return; }
 #pragma unroll 1
-        for (int x = x0; x < W; ++x, src += ES, dst += ES) resize_surface_v_cell<T, 1, MSB>(src, pa.src_pitch, cf, K, a.maxv, shift, dst);
+        for (int x = x0; x < W; ++x, src += ES, dst += ES) resize_v_cell<T, 1, MSB>(src, pa.src_pitch, cf, K, a.maxv, dst, shift);
     } else {
-        resize_surface_v_cell<T, 1, MSB>(src, pa.src_pitch, cf, K, a.maxv, shift, dst);
+        resize_v_cell<T, 1, MSB>(src, pa.src_pitch, cf, K, a.maxv, dst, shift);
     }
 }
 
 hipError_t launch_resize_surfaces_v(hipStream_t st, const ResizeStageArgs& a, int interleaved, int shift, int nframes)
 {
     if (nframes <= 0) return hipSuccess;
-    if (!resize_surface_args_ok(a, interleaved, shift) || nframes > 65535) return hipErrorInvalidValue;
-    const int px = a.vec ? 16 / a.es : 1, nc = interleaved ? 1 : 2;
-    long long chunks[2];
-    for (int k = 0; k < 2; ++k) chunks[k] = ((a.lines[k] + px - 1) / px + 63) / 64;
-    const long long items = chunks[0] * a.prog[0].D + nc * chunks[1] * a.prog[1].D;
-    if (items > 0x7FFFFF00LL) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((items + kResizeWaves - 1) / kResizeWaves), (unsigned)nframes), block(64 * kResizeWaves);
-    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a, (int)chunks[0], (int)chunks[1], nc, shift); };
+    if (!interleaved && !shift) return hipErrorInvalidValue;                             // planar LSB planes are launch_resize_v's
+    const int nc = interleaved ? 1 : 2;
+    ResizeGrid g;
+    if (!resize_grid(a, false, nc, shift, nframes, g)) return hipErrorInvalidValue;
+    const dim3 block(64 * kResizeWaves);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, g.grid, block, 0, st, a, g.per[0], g.per[1], nc, shift); };
 #define AMT_RESIZE_SURFACE_V(T, MSB)                                      \
     do {                                                                  \
         if (a.vec) go(resize_surface_v_kernel<T, true, MSB>);             \

@@ -63,6 +63,22 @@ def test_the_launchers_are_declared_once_and_defined_once():
     assert "kResizeRegionBytes" in files["resize_surface_kernels.hip"] and "kResizePairSlack" in files["amt_gpu_resize.hip"]
 
 
+def test_the_rounding_the_item_rule_and_the_vertical_cell_are_defined_once():
+    files = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if os.path.isfile(os.path.join(CSRC, f))}
+    for name in ("resize_mad", "resize_round", "resize_item", "resize_load", "resize_store", "resize_v_cell", "resize_args_ok"):
+        defs = [f for f, t in files.items() if re.search(rf"\b(?:int|void|bool|ResizeItem)\s+{name}\s*\(", t)]       # (a return type in front: no call)
+        assert defs == ["resize_body.h"], (name, defs)
+    # the rounding's constants appear where it is defined and nowhere else
+    assert [f for f, t in files.items() if re.search(r"\+\s*8192\s*\)\s*>>\s*14", re.sub(r"//.*", "", t))] == ["resize_body.h"]
+    both = ("resize_kernels.hip", "resize_surface_kernels.hip")
+    assert [f for f, t in files.items() if re.search(r'^#include "resize_body\.h"', t, re.M)] == list(both)
+    for f in both:
+        assert all(re.search(rf"\b{name}\s*[<(]", files[f]) for name in ("resize_round", "resize_item", "resize_v_cell", "resize_grid")), f
+    assert re.search(r"^#pragma once", files["resize_body.h"], re.M) and not re.search(r"^\s*__global__", files["resize_body.h"], re.M)
+    left = [(f, m) for f, t in files.items() for m in re.findall(r"\bresize_surface_(?:mad|round|item|load|store|v_cell)\b|\bResizeSurfaceItem\b", t)]
+    assert not left, left
+
+
 def test_the_lane_rule_against_brute_force(rules_test):
     r = subprocess.run([rules_test], capture_output=True, text=True)
     print(r.stdout)

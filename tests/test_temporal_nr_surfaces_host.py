@@ -65,6 +65,21 @@ def test_the_launcher_is_declared_once_and_defined_once():
     assert len(re.findall(r"refuse\(\"temporal_distance must be", host)) == 1 and len(re.findall(r"\btemporal_nr\(c, src,", host)) == 2
 
 
+def test_the_cell_and_the_reciprocal_table_are_defined_once():
+    files = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if os.path.isfile(os.path.join(CSRC, f))}
+    # the cell: a function template whose name ends in _cell and whose first argument is the kernel's arguments
+    cell = [(f, name) for f, t in files.items() for name in re.findall(r"\bvoid\s+(\w*_cell)\s*\(\s*const TemporalNRArgs&", t)]
+    assert cell == [("temporal_nr_body.h", "tnr_cell")], cell
+    table = [f for f, t in files.items() if re.search(r"__device__\s+const\s+\w+\s+k\w*Recip\w*\s*=", t)]
+    loops = [f for f, t in files.items() if re.search(r"=\s*1\.f\s*/\s*\(float\)", t)]
+    assert table == loops == ["temporal_nr_body.h"], (table, loops)
+    both = ("temporal_nr_kernels.hip", "temporal_nr_surface_kernels.hip")
+    assert [f for f, t in files.items() if re.search(r'^#include "temporal_nr_body\.h"', t, re.M)] == list(both)
+    for f in both:
+        assert re.search(r"\btnr_cell<", files[f]) and "__usad" not in files[f], f      # ... and use it, with no arithmetic of their own
+    assert re.search(r"^#pragma once", files["temporal_nr_body.h"], re.M) and not re.search(r"^\s*__global__", files["temporal_nr_body.h"], re.M)
+
+
 def test_the_lane_rule_against_brute_force(tmp_path):
     out = str(tmp_path / "temporal_nr_surface_lane_rule_test")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "temporal_nr_surface_lane_rule_test.cpp"), "-o", out])
