@@ -3,10 +3,10 @@
 Product code only: HIP kernels + C ABI (csrc/, libamt_gpu.so) and the Python mirror of the reference's
 filter interface (api.py).  Nothing here imports the CPU oracle.
 """
-from .api import (DEINT_ADAPTIVE, DEINT_LINE, AMTAnalyzeLogo, AMTEraseLogo, AmtError, AmtsFile, AudioLevels, Context, DeviceClip, DeviceSurfaces, FrameStats, Logo, LogoCandidate, LogoFinder,
+from .api import (DEINT_ADAPTIVE, DEINT_LINE, AMTAnalyzeLogo, AMTEraseLogo, AmtError, AmtsFile, AudioLevels, Context, Debander, DeviceClip, DeviceSurfaces, FrameStats, Logo, LogoCandidate, LogoFinder,
                   LogoFrame, LogoScan, Resizer, ScanLogo, ScanLogoAuto, ScanLogoAutoStream, ScanLogoFile, ScanLogoFileAuto, ScanLogoStream,
                   extract_rect, kfm_render, kfm_render_plan, mute_sections, temporal_nr, weave_fields, write_chapter_exe)
 
-__all__ = ["DEINT_ADAPTIVE", "DEINT_LINE", "AMTAnalyzeLogo", "AMTEraseLogo", "AmtError", "AmtsFile", "AudioLevels", "Context", "DeviceClip", "DeviceSurfaces", "FrameStats", "Logo", "LogoCandidate",
+__all__ = ["DEINT_ADAPTIVE", "DEINT_LINE", "AMTAnalyzeLogo", "AMTEraseLogo", "AmtError", "AmtsFile", "AudioLevels", "Context", "Debander", "DeviceClip", "DeviceSurfaces", "FrameStats", "Logo", "LogoCandidate",
            "LogoFinder", "LogoFrame", "LogoScan", "Resizer", "ScanLogo", "ScanLogoAuto", "ScanLogoAutoStream", "ScanLogoFile", "ScanLogoFileAuto",
            "ScanLogoStream", "extract_rect", "kfm_render", "kfm_render_plan", "mute_sections", "temporal_nr", "weave_fields", "write_chapter_exe"]

@@ -1165,3 +1165,61 @@ class Resizer:
             self.close()
         except Exception:
             pass
+
+
+class Debander:
+    """Deband of clips in HBM, planar LSB planes (amtgpu_deband_*): the KDeband(25, 1, 2, true) behind KTemporalNR
+    in the server's chain, integer and exact.  Per pixel up to four references at the offsets of a table that is static over frames
+    (a hash of the position, the plane and `seed`; |dx|, |dy| <= min(radius, distance to the plane's edge), chroma at radius >> 1):
+    sample 0 takes the first reference, 1 the mean of a pair, 2 the mean of two pairs at right angles; blur_first compares the mean with
+    the pixel, otherwise every reference must lie within threshold << (bits - 8) of it.  Every plane and every frame on its own.  size
+    is (width, height) of the luma plane, both even.  The arguments' order and defaults are the server's call."""
+
+    def __init__(self, ctx: Context, size, bits, radius=25, threshold=1, sample=2, blur_first=True, seed=0):
+        self.ctx, self.bits = ctx, int(bits)
+        self.width, self.height = (int(v) for v in size)
+        self.h = ctx.lib.amtgpu_deband_create(ctx.h, self.width, self.height, self.bits, int(radius), int(threshold), int(sample), 1 if blur_first else 0,
+                                              int(seed) & 0xFFFFFFFF)
+        ctx.check(self.h, "Debander")
+
+    def run(self, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSurfaces | DeviceClip"):
+        """frames 0 .. src.num_frames - 1 of src into the same frames of dst, planar LSB planes of the debander's size and bits; dst
+        must not overlap src.  Synchronises.  Returns the number of frames"""
+        n = src.num_frames
+        if n > dst.num_frames:
+            raise AmtError(f"Debander: {n} frames, dst holds {dst.num_frames}")
+        for c in (src, dst):
+            if (int(c.width), int(c.height)) != (self.width, self.height):
+                raise AmtError(f"Debander: made for {self.width}x{self.height}, got {c.width}x{c.height}")
+        s, t = _surfaces_ref(src), _surfaces_ref(dst)
+        self.ctx.check(self.ctx.lib.amtgpu_deband_run(self.h, C.byref(s), C.byref(t), n), "Debander")
+        return n
+
+    def _plane_shape(self, plane):
+        return (self.height >> 1, self.width >> 1) if plane else (self.height, self.width)
+
+    def offsets(self, plane):
+        """(dx, dy) of plane 0 (Y) / 1 (U) / 2 (V), each (Hp, Wp) numpy int8"""
+        dx, dy = np.zeros(self._plane_shape(plane), np.int8), np.zeros(self._plane_shape(plane), np.int8)
+        self.ctx.check(self.ctx.lib.amtgpu_deband_get_offsets(self.h, int(plane), _p(dx), _p(dy)), "Debander")
+        return dx, dy
+
+    def set_offsets(self, plane, dx, dy):
+        """replaces one plane's table; refused where an entry exceeds min(radius, distance to the plane's edge)"""
+        if plane not in (0, 1, 2):
+            raise AmtError(f"Debander: plane is 0 (Y), 1 (U) or 2 (V), not {plane!r}")
+        dx, dy = np.ascontiguousarray(dx, np.int8), np.ascontiguousarray(dy, np.int8)
+        if dx.shape != self._plane_shape(plane) or dy.shape != dx.shape:
+            raise AmtError(f"Debander: plane {plane} takes tables of {self._plane_shape(plane)}, got {dx.shape} and {dy.shape}")
+        self.ctx.check(self.ctx.lib.amtgpu_deband_set_offsets(self.h, int(plane), _p(dx), _p(dy)), "Debander")
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.amtgpu_deband_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -46,6 +46,9 @@ SOURCES = [
     "resize_kernels.hip",
     "resize_surface_kernels.hip",
     "resize_plan.cpp",
+    "amt_gpu_deband.hip",
+    "deband_kernels.hip",
+    "deband_plan.cpp",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

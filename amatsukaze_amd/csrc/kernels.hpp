@@ -196,6 +196,54 @@ hipError_t launch_resize_v(hipStream_t st, const ResizeStageArgs& a, int nframes
 hipError_t launch_resize_surfaces_h(hipStream_t st, const ResizeStageArgs& a, int interleaved, int shift, int nframes);
 hipError_t launch_resize_surfaces_v(hipStream_t st, const ResizeStageArgs& a, int interleaved, int shift, int nframes);
 
+// ---- deband_kernels.hip ----
+// The deband of DESIGN.md section 6f on planar LSB planes: per pixel up to four references at the offsets a static table holds, every
+// plane and every frame on its own.  A 256-thread workgroup owns a tile of kDebandTileW x kDebandTileH output samples of one plane of
+// one frame and stages it, with the plane's radius of halo clipped to the plane, into LDS; a lane then takes 16 bytes of an output row.
+constexpr int kDebandTileW = 128, kDebandTileH = 96;
+constexpr int kDebandHalo = 31;                // the largest radius (deband_plan.hpp kDebandMaxRadius)
+// Bytes between the staged rows of containers of es bytes: the tile and both halos, the up to 15 bytes by which the staged span begins
+// in front of the halo (its first column is a multiple of 16 bytes), rounded up to 16 -- 208 and 400
+constexpr int deband_lds_pitch(int es) { return ((kDebandTileW + 2 * kDebandHalo) * es + 15 + 15) & ~15; }
+// ... and of the staged rows: 32 864 and 63 200, so two workgroups of the 16-bit form share a CU's 160 KiB
+constexpr int deband_lds_bytes(int es) { return deband_lds_pitch(es) * (kDebandTileH + 2 * kDebandHalo); }
+struct DebandPlaneArgs {
+    const uint8_t* src; uint8_t* dst;
+    const int8_t *dx, *dy;                     // the plane's offsets, rows table_pitch bytes apart; |dx|, |dy| <= lim(x, y), which the
+                                               // host has checked: a reference outside the staged span would be an LDS read out of bounds
+    long long src_stride, dst_stride;          // bytes between frames
+    int src_pitch, dst_pitch;                  // bytes between rows
+    int W, H, R;                               // the plane's size in containers and its radius (0..kDebandHalo)
+    int table_pitch;                           // a multiple of 16, at least W rounded up to 16: a lane loads its 16 / es entries at once
+};
+struct DebandArgs {
+    DebandPlaneArgs plane[3];                  // Y, U, V
+    int es, vec;                               // vec: deband_vec16 (lane_rule.h)
+    int thresh;                                // threshold << (bits - 8)
+    int sample, blur_first;                    // 0..2; zero or not
+};
+// The grid of the launcher below: x walks a frame's tiles, luma first, then U's, then V's; y the frames, a block taking every
+// gridDim.y-th where there are more than 65 535.  False where an argument or the grid is out of range
+struct DebandGrid { int tiles_x[2], tiles[2]; dim3 grid; };
+inline bool deband_grid(const DebandArgs& a, int nframes, DebandGrid& g)
+{
+    if ((a.es != 1 && a.es != 2) || a.sample < 0 || a.sample > 2 || a.thresh < 0 || nframes <= 0) return false;
+    for (int p = 0; p < 3; ++p) {
+        const DebandPlaneArgs& q = a.plane[p];
+        if (!q.src || !q.dst || !q.dx || !q.dy || q.W <= 0 || q.H <= 0 || q.W > 65534 || q.H > 65534 || q.R < 0 || q.R > kDebandHalo) return false;
+        if (q.src_pitch < q.W * a.es || q.dst_pitch < q.W * a.es || q.table_pitch % 16 || q.table_pitch < ((q.W + 15) & ~15)) return false;
+        if (p && (q.W != a.plane[1].W || q.H != a.plane[1].H)) return false;
+    }
+    for (int k = 0; k < 2; ++k) {
+        g.tiles_x[k] = (a.plane[k].W + kDebandTileW - 1) / kDebandTileW;
+        g.tiles[k] = g.tiles_x[k] * ((a.plane[k].H + kDebandTileH - 1) / kDebandTileH);
+    }
+    g.grid = dim3((unsigned)(g.tiles[0] + 2 * g.tiles[1]), (unsigned)(nframes < 65535 ? nframes : 65535));
+    return true;
+}
+// One launch for all planes and frames; none when nframes <= 0
+hipError_t launch_deband(hipStream_t st, const DebandArgs& a, int nframes);
+
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 // Both take a luma batch of either alignment: b.shift != 0 (16-bit containers, shift = 16 - bits) runs the same sums on container >> shift,
 // `bits` then being the depth of the shifted samples (9..15 metrics, 9..16 finder): the instantiations of stats_msb_ / logofind_msb_kernels.hip.

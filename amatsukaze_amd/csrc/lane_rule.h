@@ -104,4 +104,12 @@ inline int resize_surface_vec16(const RowsAt& srcY, const RowsAt& srcUV, const R
     return resize_vec16(srcY, srcUV, midY, midUV, dstY, dstUV);
 }
 
+// deband_kernel: every plane goes on its own.  A workgroup stages its tile's rows with aligned 16-byte loads and a lane stores 16 bytes
+// of an output row, where every row of every plane of the source and of the destination starts 16-byte aligned (a row's last containers
+// go narrower, so the row length is no operand); otherwise both go container by container
+inline int deband_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& dstY, const RowsAt& dstUV)
+{
+    return lane_divides(16, srcY.bits() | srcUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
+}
+
 } // namespace amt

@@ -814,6 +814,48 @@ int  amtgpu_resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuS
 int  amtgpu_resize_run_surfaces(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes);
 int  amtgpu_resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int* start, int* coeff);
 
+/* ---- deband: the KDeband(25, 1, 2, true) behind KTemporalNR in the server's chain (Misc.cs:1431; the GUI's "banding reduction"
+ *      checkbox, which the reference's README pairs with the temporal NR), on planar LSB planes in HBM.  Self-specified, "parity
+ *      unpinned" (KDeband belongs to AviSynthCUDAFilters; its source is not in the reference tree): integer and
+ *      exact, so the bytes are those of the rule below wherever it runs and depend on the clip and the parameters alone.  The argument
+ *      order (range, threshold, sample, blur_first) and the defaults 25, 1, 2, true are the server's call.  An addition; the ABI
+ *      version stays 5. ----
+ * Planes of 8..16 bits, 4:2:0, width and height even.  Every plane is filtered on its own and every frame on its own; there is no halo
+ * in time, so a clip cut into calls gives the bytes of one call.  For plane p (0 Y, 1 U, 2 V) of Wp x Hp containers, radius the caller's
+ * figure (KDeband's range, 1..31), Rp = radius for luma and radius >> 1 for chroma:
+ *   lim(x, y) = min(Rp, x, Wp - 1 - x, y, Hp - 1 - y): no reference sample ever lies outside the plane.
+ *   The offset table is static over frames and built on the host, once per object, everything uint32 with wrap-around:
+ *     mix(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16;
+ *     key_p = mix(seed + 0x9e3779b9 * (p + 1));  h = mix(key_p ^ (y << 16 | x));  a = h & 255, b = (h >> 8) & 255;
+ *     dx = ((a * (2 lim + 1)) >> 8) - lim,  dy = ((b * (2 lim + 1)) >> 8) - lim: both int8 in [-lim, lim].
+ *   The references of a pixel: p0 = s[y + dy][x + dx], p1 = s[y - dy][x - dx], p2 = s[y + dx][x - dy], p3 = s[y - dx][x + dy] -- p2, p3
+ *     are the pair p0, p1 turned by 90 degrees; |dx|, |dy| <= lim keeps all four inside the plane.
+ *   With c = s[y][x] and thresh = threshold << (bits - 8) (the temporal NR's scaling; threshold 0..32767):
+ *     sample 0: out = p0 if |p0 - c| <= thresh, else c;
+ *     sample 1: avg = (p0 + p1 + 1) >> 1;  sample 2: avg = (p0 + p1 + p2 + p3 + 2) >> 2;
+ *     blur_first non-zero: out = avg if |avg - c| <= thresh, else c;  zero: out = avg if every |p_i - c| <= thresh, else c.
+ *   Containers are taken as stored (no masking to bits), as in the temporal NR.  There is no grain and no dither.
+ * amtgpu_deband_create: the object owns the three planes' offset tables on the device.  Returns NULL with a message on ctx: an odd or
+ *   non-positive size, or one above 65534 (the hash key packs y << 16 | x); bits outside 8..16; radius outside 1..31; threshold outside
+ *   0..32767; sample outside 0..2.
+ * amtgpu_deband_run: frames 0 .. nframes - 1 of src into frames 0 .. nframes - 1 of dst, planar LSB planes of the object's size and
+ *   bits, in one launch.  Returns 0 with a message on ctx, and launches nothing: an interleaved or MSB-aligned descriptor (planar LSB
+ *   only); bits that are not the object's; a pitch below the row; a negative frame stride; destination frames that overlap each other
+ *   in a plane; a destination plane whose byte range (first byte of frame 0 .. last byte of frame nframes - 1) overlaps a source
+ *   plane's -- in-place is impossible here, the filter reads neighbours.  nframes == 0 returns 1.  Reads nothing outside the first Wp
+ *   containers of a source row and writes nothing outside them in a destination row; every container of the output frames is written;
+ *   the source is never written.  Synchronises, as amtgpu_resize_run does.
+ * amtgpu_deband_get_offsets: plane p's table, Wp * Hp int8 each, row-major (either pointer may be NULL).
+ * amtgpu_deband_set_offsets: replaces one plane's table with the caller's -- a pattern of the caller's own, or a test's planted one.
+ *   Refused, the table staying as it was, if any |dx| or |dy| exceeds lim(x, y).  Synchronises */
+typedef struct AmtGpuDeband AmtGpuDeband;
+AmtGpuDeband* amtgpu_deband_create(AmtGpuContext* ctx, int width, int height, int bits, int radius, int threshold, int sample, int blur_first,
+                                   uint32_t seed);
+void amtgpu_deband_destroy(AmtGpuDeband* d);
+int  amtgpu_deband_run(AmtGpuDeband* d, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes);
+int  amtgpu_deband_get_offsets(AmtGpuDeband* d, int plane, int8_t* dx, int8_t* dy);          /* Wp * Hp each, row-major */
+int  amtgpu_deband_set_offsets(AmtGpuDeband* d, int plane, const int8_t* dx, const int8_t* dy);
+
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
 int  amtgpu_cm_write_chapter_exe(const int* scene_changes, int nsc, int nframes, const char* path);
