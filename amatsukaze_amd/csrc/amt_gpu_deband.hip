@@ -9,6 +9,7 @@
 #include <string>
 
 #include "api_common.hpp"
+#include "plane_pair.hpp"
 #include "deband_plan.hpp"
 
 using namespace amt;
@@ -25,28 +26,10 @@ struct AmtGpuDeband {
 };
 
 namespace {
-const char* const kWho = "[Deband]";
+const PlanePairRule& kPair = kDebandPair;
+const char* const kWho = kPair.who;
 
 [[noreturn]] void refuse(const std::string& what) { throw std::runtime_error(std::string(kWho) + " " + what); }
-
-// planar LSB surfaces of the object's bits with rows of at least width (chroma: width / 2) containers
-FrameBatch deband_surfaces(const AmtGpuSurfaces* s, const char* which, int width, int bits)
-{
-    const FrameBatch b = surface_batch(s, kWho);
-    if (s->interleaved || s->msb_aligned) refuse(std::string(which) + ": planar, LSB-aligned planes only (interleaved and MSB-aligned surfaces are refused)");
-    if (s->bits != bits) refuse(std::string(which) + ": " + std::to_string(s->bits) + " bits, the debander was created for " + std::to_string(bits));
-    if (b.strideY < 0 || b.strideUV < 0) refuse(std::string(which) + ": negative frame stride");
-    if (b.pitchY < width || b.pitchUV < width / 2) refuse(std::string(which) + ": pitch smaller than the row");
-    return b;
-}
-
-// [first byte, one past the last byte) that n frames of a plane span
-struct Span { uintptr_t lo, hi; };
-Span plane_span(const void* p, long long stride, long long pitch_bytes, int row_bytes, int rows, int n)
-{
-    const uintptr_t lo = (uintptr_t)p;
-    return Span{lo, lo + (uintptr_t)(n - 1) * (uintptr_t)stride + (uintptr_t)(rows - 1) * (uintptr_t)pitch_bytes + (uintptr_t)row_bytes};
-}
 
 // one plane's table to the device, rows padded with zeros
 void upload_table(AmtGpuDeband* d, int plane)
@@ -94,39 +77,20 @@ void deband_run(AmtGpuDeband* d, const AmtGpuSurfaces* src, const AmtGpuSurfaces
     AmtGpuContext* c = d->ctx;
     if (nframes < 0) refuse("negative frame count");
     if (nframes == 0) return;
-    const FrameBatch s = deband_surfaces(src, "source", d->width, d->bits), t = deband_surfaces(dst, "destination", d->width, d->bits);
-    const int es = s.es;
-    struct Geometry { int w, h; };
-    const Geometry g[2] = {{d->width, d->height}, {d->width / 2, d->height / 2}};
-    const long long s_stride[2] = {s.strideY, s.strideUV}, t_stride[2] = {t.strideY, t.strideUV};
-    const long long s_pitch[2] = {(long long)s.pitchY * es, (long long)s.pitchUV * es}, t_pitch[2] = {(long long)t.pitchY * es, (long long)t.pitchUV * es};
-    if (s_pitch[0] > INT32_MAX || s_pitch[1] > INT32_MAX || t_pitch[0] > INT32_MAX || t_pitch[1] > INT32_MAX) refuse("pitch above 2 GiB");
-    const void* const sp[3] = {s.Y, s.U, s.V};
-    const void* const tp[3] = {t.Y, t.U, t.V};
-    // destination frames must not overlap each other, and no destination plane's span may touch a source plane's
-    for (int k = 0; k < 2; ++k)
-        if (nframes > 1 && t_stride[k] < (long long)(g[k].h - 1) * t_pitch[k] + (long long)g[k].w * es) refuse("destination frames overlap each other");
-    Span sspan[3], dspan[3];
-    for (int p = 0; p < 3; ++p) {
-        const int k = p ? 1 : 0;
-        sspan[p] = plane_span(sp[p], s_stride[k], s_pitch[k], g[k].w * es, g[k].h, nframes);
-        dspan[p] = plane_span(tp[p], t_stride[k], t_pitch[k], g[k].w * es, g[k].h, nframes);
-    }
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi)
-                refuse("the destination's byte range overlaps the source's (no in-place filtering: the filter reads neighbours)");
+    // the source/destination rule (plane_pair.hpp), planar LSB planes only
+    const FrameBatch s = kPair.side("source", src, surface_batch(src, kWho), d->width, false, d->bits),
+                     t = kPair.side("destination", dst, surface_batch(dst, kWho), d->width, false, d->bits);
+    const PlaneBytes sb = kPair.bytes(s, d->width, d->height), tb = kPair.bytes(t, d->width, d->height);
+    kPair.disjoint(sb, nframes, tb, nframes);
 
     DebandArgs a{};
     for (int p = 0; p < 3; ++p) {
         const int k = p ? 1 : 0;
-        a.plane[p] = DebandPlaneArgs{(const uint8_t*)sp[p], (uint8_t*)tp[p], d->dTables.get() + d->table_at[p][0], d->dTables.get() + d->table_at[p][1],
-                                     s_stride[k], t_stride[k], (int)s_pitch[k], (int)t_pitch[k], g[k].w, g[k].h, d->table[p].R, d->table_pitch[p]};
+        a.plane[p] = DebandPlaneArgs{(const uint8_t*)sb.p[p], (uint8_t*)tb.p[p], d->dTables.get() + d->table_at[p][0], d->dTables.get() + d->table_at[p][1],
+                                     sb.stride[k], tb.stride[k], sb.pitch[k], tb.pitch[k], d->table[p].W, d->table[p].H, d->table[p].R, d->table_pitch[p]};
     }
-    const RowsAt srcY{lane_addr(s.Y), 0, s_stride[0], s_pitch[0]}, srcUV{lane_addr(s.U), lane_addr(s.V), s_stride[1], s_pitch[1]};
-    const RowsAt dstY{lane_addr(t.Y), 0, t_stride[0], t_pitch[0]}, dstUV{lane_addr(t.U), lane_addr(t.V), t_stride[1], t_pitch[1]};
-    a.es = es;
-    a.vec = deband_vec16(srcY, srcUV, dstY, dstUV);
+    a.es = s.es;
+    a.vec = deband_vec16(sb.luma(), sb.chroma(), tb.luma(), tb.chroma());
     a.thresh = d->threshold << (d->bits - 8);
     a.sample = d->sample; a.blur_first = d->blur_first;
     c->bind();

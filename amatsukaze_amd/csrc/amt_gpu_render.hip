@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "api_common.hpp"
+#include "plane_pair.hpp"
 #include "stats_decisions.hpp"
 
 using namespace amt;
@@ -17,26 +18,10 @@ static_assert(AMTGPU_RENDER_WEAVE == kRenderWeave && AMTGPU_RENDER_BOB_TOP == kR
               "the kinds of the ABI are the planner's");
 
 namespace {
-const char* const kWho = "[KFMRender]";
+const PlanePairRule& kPair = kRenderPair;
+const char* const kWho = kPair.who;
 
 [[noreturn]] void refuse(const std::string& what) { throw std::runtime_error(std::string(kWho) + " " + what); }
-
-// surfaces of `bits` in any layout, rows of at least width containers (chroma: width / 2 planar, 2 * (width / 2) interleaved)
-FrameBatch render_surfaces(const AmtGpuSurfaces* s, const char* which, int width)
-{
-    const FrameBatch b = surface_batch(s, kWho);
-    if (b.strideY < 0 || b.strideUV < 0) refuse(std::string(which) + ": negative frame stride");
-    if (b.pitchY < width || b.pitchUV < (b.interleaved ? width : width / 2)) refuse(std::string(which) + ": pitch smaller than the row");
-    return b;
-}
-
-// [first byte, one past the last byte) that n frames of a plane span
-struct Span { uintptr_t lo, hi; };
-Span plane_span(const void* p, long long stride, int pitch_bytes, int row_bytes, int rows, int n)
-{
-    const uintptr_t lo = (uintptr_t)p;
-    return Span{lo, lo + (uintptr_t)(n - 1) * (uintptr_t)stride + (uintptr_t)(rows - 1) * (uintptr_t)pitch_bytes + (uintptr_t)row_bytes};
-}
 
 // all entry points: deint LINE is amtgpu_kfm_render, ADAPTIVE the edge-directed, motion-adaptive rule -- on planes, and with
 // adaptive_surfaces (amtgpu_kfm_render_deint_surfaces) on every pair in kind
@@ -50,15 +35,13 @@ void render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc
     if (nout == 0) return;
     if (!plan) refuse("null plan");
     if (width <= 0 || height < 4 || (width & 1) || (height & 1)) refuse("width and height must be even and height at least 4 (4:2:0 field pairs)");
-    const FrameBatch s = render_surfaces(src, "source", width), d = render_surfaces(dst, "destination", width);
+    // the source/destination rule (plane_pair.hpp), surfaces in any layout
+    const FrameBatch s = kPair.side("source", src, surface_batch(src, kWho), width, true), d = kPair.side("destination", dst, surface_batch(dst, kWho), width, true);
     if (src->bits != dst->bits) refuse("source and destination differ in bits");
-    if (s.interleaved != d.interleaved || s.shift != d.shift)
-        refuse("source and destination are not in kind (equal bits, interleaved and MSB shift): the renderer converts no layouts");
+    kPair.in_kind(s, d);
     if (adaptive && !adaptive_surfaces && (s.interleaved || s.shift)) refuse("the adaptive rule takes planes only (planar, LSB-aligned): interleaved and MSB-aligned surfaces are refused");
     if (src_first < 0 || nsrc <= 0 || (long long)src_first + nsrc > clip_frames) refuse("the source batch does not lie inside the clip");
-    const int es = s.es, wUV = width >> 1, hUV = height >> 1;
-    const int maxv = s.shift ? (1 << src->bits) - 1 : es == 1 ? 255 : 65535;        // of a sample: MSB-aligned ones are compared shifted
-    const int nplanes = s.interleaved ? 2 : 3;                                       // Y, then U and V or the one UV plane
+    const int maxv = s.shift ? (1 << src->bits) - 1 : s.es == 1 ? 255 : 65535;      // of a sample: MSB-aligned ones are compared shifted
 
     std::vector<RenderEntry> entries((size_t)(adaptive ? 0 : nout));
     std::vector<RenderAdaptiveEntry> aentries((size_t)(adaptive ? nout : 0));
@@ -92,28 +75,15 @@ void render(AmtGpuContext* c, const AmtGpuSurfaces* src, int src_first, int nsrc
         if (thresh >= 0 && f.kind == AMTGPU_RENDER_BOB_BOTTOM && (long long)f.top + 1 < clip_frames) e.other = local((long long)f.top + 1, i, "the temporal neighbour");
     }
 
+    const PlaneBytes sb = kPair.bytes(s, width, height), db = kPair.bytes(d, width, height);
+    kPair.disjoint(sb, nsrc, db, nout);
     RenderArgs a;
-    a.srcY = (const uint8_t*)s.Y; a.srcU = (const uint8_t*)s.U; a.srcV = (const uint8_t*)s.V;
-    a.dstY = (uint8_t*)d.Y; a.dstU = (uint8_t*)d.U; a.dstV = (uint8_t*)d.V;
-    a.src_strideY = s.strideY; a.src_strideUV = s.strideUV; a.dst_strideY = d.strideY; a.dst_strideUV = d.strideUV;
-    a.src_pitchY = s.pitchY * es; a.src_pitchUV = s.pitchUV * es; a.dst_pitchY = d.pitchY * es; a.dst_pitchUV = d.pitchUV * es;
-    a.rowY = width * es; a.rowUV = (s.interleaved ? 2 * wUV : wUV) * es;
-    a.H = height; a.HUV = hUV;
-    a.es = es;
+    pair_args(a, sb, db);
+    a.rowY = sb.row[0]; a.rowUV = sb.row[1];
+    a.H = height; a.HUV = sb.rows[1];
+    a.es = s.es;
     a.thresh = thresh < 0 ? -1 : std::min(thresh, maxv);
-    // destination frames must not overlap each other, and no destination plane's span may touch a source plane's
-    if (nout > 1 && (a.dst_strideY < (long long)(height - 1) * a.dst_pitchY + a.rowY || a.dst_strideUV < (long long)(hUV - 1) * a.dst_pitchUV + a.rowUV))
-        refuse("destination frames overlap each other");
-    const Span sspan[3] = {plane_span(a.srcY, a.src_strideY, a.src_pitchY, a.rowY, height, nsrc), plane_span(a.srcU, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc),
-                           plane_span(a.srcV, a.src_strideUV, a.src_pitchUV, a.rowUV, hUV, nsrc)};
-    const Span dspan[3] = {plane_span(a.dstY, a.dst_strideY, a.dst_pitchY, a.rowY, height, nout), plane_span(a.dstU, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout),
-                           plane_span(a.dstV, a.dst_strideUV, a.dst_pitchUV, a.rowUV, hUV, nout)};
-    for (int i = 0; i < nplanes; ++i)
-        for (int j = 0; j < nplanes; ++j)
-            if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place rendering)");
-    // (an interleaved batch has null V planes, which count as aligned: surface_batch drops whatever the descriptor holds there)
-    a.vec = render_vec16(RowsAt{lane_addr(a.srcY), 0, a.src_strideY, a.src_pitchY}, RowsAt{lane_addr(a.srcU), lane_addr(a.srcV), a.src_strideUV, a.src_pitchUV},
-                         RowsAt{lane_addr(a.dstY), 0, a.dst_strideY, a.dst_pitchY}, RowsAt{lane_addr(a.dstU), lane_addr(a.dstV), a.dst_strideUV, a.dst_pitchUV});
+    a.vec = render_vec16(sb.luma(), sb.chroma(), db.luma(), db.chroma());
     c->bind();
     if (adaptive) {
         DevBuf<RenderAdaptiveEntry> dplan;

@@ -11,6 +11,7 @@
 #include <string>
 
 #include "api_common.hpp"
+#include "plane_pair.hpp"
 #include "resize_plan.hpp"
 
 using namespace amt;
@@ -31,30 +32,10 @@ struct AmtGpuResize {
 };
 
 namespace {
-const char* const kWho = "[Resize]";
+const PlanePairRule& kPair = kResizePair;
+const char* const kWho = kPair.who;
 
 [[noreturn]] void refuse(const std::string& what) { throw std::runtime_error(std::string(kWho) + " " + what); }
-
-// surfaces with rows of at least width (chroma: width / 2 planar, 2 * (width / 2) interleaved) containers; any_layout: of every layout
-// (amtgpu_resize_run_surfaces), else planar LSB planes only
-FrameBatch resize_surfaces(const AmtGpuSurfaces* s, const char* which, int width, int bits, bool any_layout)
-{
-    const FrameBatch b = surface_batch(s, kWho);
-    if (!any_layout && (s->interleaved || s->msb_aligned))
-        refuse(std::string(which) + ": planar, LSB-aligned planes only (interleaved and MSB-aligned surfaces are refused)");
-    if (s->bits != bits) refuse(std::string(which) + ": " + std::to_string(s->bits) + " bits, the resizer was created for " + std::to_string(bits));
-    if (b.strideY < 0 || b.strideUV < 0) refuse(std::string(which) + ": negative frame stride");
-    if (b.pitchY < width || b.pitchUV < (b.interleaved ? width : width / 2)) refuse(std::string(which) + ": pitch smaller than the row");
-    return b;
-}
-
-// [first byte, one past the last byte) that n frames of a plane span
-struct Span { uintptr_t lo, hi; };
-Span plane_span(const void* p, long long stride, long long pitch_bytes, int row_bytes, int rows, int n)
-{
-    const uintptr_t lo = (uintptr_t)p;
-    return Span{lo, lo + (uintptr_t)(n - 1) * (uintptr_t)stride + (uintptr_t)(rows - 1) * (uintptr_t)pitch_bytes + (uintptr_t)row_bytes};
-}
 
 AmtGpuResize* resize_create(AmtGpuContext* c, int src_w, int src_h, int dst_w, int dst_h, int bits, int kernel, int taps, int64_t max_scratch_bytes)
 {
@@ -111,36 +92,17 @@ void resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces
     AmtGpuContext* c = r->ctx;
     if (nframes < 0) refuse("negative frame count");
     if (nframes == 0) return;
-    const FrameBatch s = resize_surfaces(src, "source", r->src_w, r->bits, any_layout), t = resize_surfaces(dst, "destination", r->dst_w, r->bits, any_layout);
-    if (s.interleaved != t.interleaved || s.shift != t.shift)
-        refuse("source and destination are not in kind (equal bits, interleaved and MSB shift): the resizer converts no layouts");
+    // the source/destination rule (plane_pair.hpp)
+    const FrameBatch s = kPair.side("source", src, surface_batch(src, kWho), r->src_w, any_layout, r->bits),
+                     t = kPair.side("destination", dst, surface_batch(dst, kWho), r->dst_w, any_layout, r->bits);
+    kPair.in_kind(s, t);
     const int es = s.es, il = s.interleaved;
     const bool planes = !il && !s.shift;                                               // planar LSB: the planar kernels, as before
     if (il && !r->pair_cpw)
         refuse("the interleaved chroma window of " + std::to_string(r->prog[1][0].K) + " pairs does not fit a wave's staging region (" +
                std::to_string((kResizeRegionBytes - kResizePairSlack) / (2 * es)) + " pairs): the ratio is too small for interleaved surfaces");
-    // the planes of a frame: Y, U, V -- or Y and the one UV plane, whose rows are as many containers as luma rows
-    const int nplanes = il ? 2 : 3;
-    struct Geometry { int w, h; };
-    const Geometry sg[2] = {{r->src_w, r->src_h}, {il ? r->src_w : r->src_w / 2, r->src_h / 2}};
-    const Geometry dg[2] = {{r->dst_w, r->dst_h}, {il ? r->dst_w : r->dst_w / 2, r->dst_h / 2}};
-    const long long s_stride[2] = {s.strideY, s.strideUV}, t_stride[2] = {t.strideY, t.strideUV};
-    const long long s_pitch[2] = {(long long)s.pitchY * es, (long long)s.pitchUV * es}, t_pitch[2] = {(long long)t.pitchY * es, (long long)t.pitchUV * es};
-    if (s_pitch[0] > INT32_MAX || s_pitch[1] > INT32_MAX || t_pitch[0] > INT32_MAX || t_pitch[1] > INT32_MAX) refuse("pitch above 2 GiB");
-    const void* const sp[3] = {s.Y, s.U, s.V};
-    const void* const tp[3] = {t.Y, t.U, t.V};
-    // destination frames must not overlap each other, and no destination plane's span may touch a source plane's
-    for (int k = 0; k < 2; ++k)
-        if (nframes > 1 && t_stride[k] < (long long)(dg[k].h - 1) * t_pitch[k] + (long long)dg[k].w * es) refuse("destination frames overlap each other");
-    Span sspan[3], dspan[3];
-    for (int p = 0; p < nplanes; ++p) {
-        const int k = p ? 1 : 0;
-        sspan[p] = plane_span(sp[p], s_stride[k], s_pitch[k], sg[k].w * es, sg[k].h, nframes);
-        dspan[p] = plane_span(tp[p], t_stride[k], t_pitch[k], dg[k].w * es, dg[k].h, nframes);
-    }
-    for (int i = 0; i < nplanes; ++i)
-        for (int j = 0; j < nplanes; ++j)
-            if (const Span &x = sspan[i], &y = dspan[j]; x.lo < y.hi && y.lo < x.hi) refuse("the destination's byte range overlaps the source's (no in-place resize)");
+    const PlaneBytes sb = kPair.bytes(s, r->src_w, r->src_h), tb = kPair.bytes(t, r->dst_w, r->dst_h);
+    kPair.disjoint(sb, nframes, tb, nframes);
 
     c->bind();
     const int round = std::min(r->round_frames, nframes);
@@ -151,25 +113,23 @@ void resize_run(AmtGpuResize* r, const AmtGpuSurfaces* src, const AmtGpuSurfaces
     const int mid_pitch[2] = {r->mid_pitch[0], il ? r->mid_pitch[0] : r->mid_pitch[1]};
     const size_t mid_plane[2] = {r->mid_plane[0], il ? (size_t)r->mid_pitch[0] * (size_t)(r->src_h / 2) : r->mid_plane[1]};
     uint8_t* const mid[3] = {r->dMid.get(), r->dMid.get() + mid_plane[0] * round, il ? nullptr : r->dMid.get() + (mid_plane[0] + mid_plane[1]) * round};
-    const RowsAt srcY{lane_addr(s.Y), 0, s_stride[0], s_pitch[0]}, srcUV{lane_addr(s.U), lane_addr(s.V), s_stride[1], s_pitch[1]};
-    const RowsAt dstY{lane_addr(t.Y), 0, t_stride[0], t_pitch[0]}, dstUV{lane_addr(t.U), lane_addr(t.V), t_stride[1], t_pitch[1]};
     const RowsAt midY{lane_addr(mid[0]), 0, (long long)mid_plane[0], mid_pitch[0]}, midUV{lane_addr(mid[1]), lane_addr(mid[2]), (long long)mid_plane[1], mid_pitch[1]};
     ResizeStageArgs h{}, v{};
     h.es = v.es = es;
     h.maxv = v.maxv = (1 << r->bits) - 1;
-    // (an interleaved batch has null V planes, which count as aligned: surface_batch drops whatever the descriptor holds there)
-    h.vec = v.vec = planes ? resize_vec16(srcY, srcUV, midY, midUV, dstY, dstUV) : resize_surface_vec16(srcY, srcUV, midY, midUV, dstY, dstUV);
+    h.vec = v.vec = planes ? resize_vec16(sb.luma(), sb.chroma(), midY, midUV, tb.luma(), tb.chroma())
+                           : resize_surface_vec16(sb.luma(), sb.chroma(), midY, midUV, tb.luma(), tb.chroma());
     for (int k = 0; k < 2; ++k) {
         h.prog[k] = r->dprog[k][0]; v.prog[k] = r->dprog[k][1];
-        h.lines[k] = sg[k].h; v.lines[k] = dg[k].w;
+        h.lines[k] = sb.rows[k]; v.lines[k] = tb.row[k] / es;
         h.cpw[k] = k && il ? r->pair_cpw : r->cpw[k]; v.cpw[k] = 0;
     }
     for (int first = 0; first < nframes; first += round) {
         const int n = std::min(round, nframes - first);
-        for (int p = 0; p < nplanes; ++p) {
+        for (int p = 0; p < sb.nplanes; ++p) {
             const int k = p ? 1 : 0;
-            h.plane[p] = ResizePlaneArgs{(const uint8_t*)sp[p] + (long long)first * s_stride[k], mid[p], s_stride[k], (long long)mid_plane[k], (int)s_pitch[k], mid_pitch[k]};
-            v.plane[p] = ResizePlaneArgs{mid[p], (uint8_t*)tp[p] + (long long)first * t_stride[k], (long long)mid_plane[k], t_stride[k], mid_pitch[k], (int)t_pitch[k]};
+            h.plane[p] = ResizePlaneArgs{(const uint8_t*)sb.p[p] + first * sb.stride[k], mid[p], sb.stride[k], (long long)mid_plane[k], sb.pitch[k], mid_pitch[k]};
+            v.plane[p] = ResizePlaneArgs{mid[p], (uint8_t*)tb.p[p] + first * tb.stride[k], (long long)mid_plane[k], tb.stride[k], mid_pitch[k], tb.pitch[k]};
         }
         const int s1 = c->prof_begin(planes ? "resize_h_kernel" : "resize_surface_h_kernel");
         AMT_HIP(planes ? launch_resize_h(c->stream, h, n) : launch_resize_surfaces_h(c->stream, h, il, s.shift, n));

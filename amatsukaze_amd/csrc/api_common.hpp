@@ -82,7 +82,7 @@ inline int scan_sample_bytes(int bits, int thy = 0)
 
 // The ABI's description of a batch of planes (byte strides, sample pitches) as the launchers take it: the same units, planar and LSB.
 // Nothing is converted here or anywhere else in the host code; this is the one place that checks that the sample size divides the byte
-// strides, so that a launcher whose kernel counts in samples may divide (kernels.hpp, FrameBatch).  ScanLogo's entry points also refuse
+// strides, so that a launcher whose kernel counts in samples may divide (frame_batch.h, FrameBatch).  ScanLogo's entry points also refuse
 // the depth and a plane base off the sample size, in their own words; a caller that reads the luma plane alone passes null chroma planes
 // and a zero chroma stride.
 enum class PlaneRules { Plain, ScanLogo };

@@ -645,6 +645,24 @@ typedef struct AmtGpuRenderFrame { int32_t kind, top, bottom, ticks; } AmtGpuRen
  * a 60i frame n -> BOB_TOP(n) 1, BOB_BOTTOM(n) 1; anything else (30p, 24p outside a complete cycle) -> WEAVE(n, n) 2, the frame as it is.
  * *nout = the entries needed; returns 0 when cap is smaller (nothing is written then), 1 otherwise; nframes == 0 returns 1, *nout = 0 */
 int  amtgpu_kfm_render_plan(const uint8_t* cadence, const uint8_t* phase, int nframes, AmtGpuRenderFrame* out, int cap, int* nout);
+/* ---- source and destination: the one rule of the chain's entry points below -- amtgpu_kfm_render[_deint[_surfaces]], amtgpu_resize_run
+ *      [_surfaces], amtgpu_temporal_nr[_surfaces], amtgpu_deband_run -- which all read frames through one AmtGpuSurfaces and write frames
+ *      through another.  Each returns 0 with a message on ctx, and launches nothing, unless:
+ *   - each descriptor is well formed (not NULL, bits 8..16, MSB-aligned only above 8 bits, reserved 0, no plane NULL but an interleaved
+ *     V, strides and plane bases multiples of the container size);
+ *   - each is of a layout the call takes: any, or planar LSB-aligned only (interleaved and MSB-aligned descriptors are refused);
+ *   - each has the bits the object was created for, where the call has an object (resize, deband);
+ *   - no frame stride is negative;
+ *   - rows fit their pitch: pitchY >= width, pitchUV >= width / 2 planar and >= width interleaved, where a UV row is `width` containers;
+ *   - the two are IN KIND: equal bits, equal interleaved, and an equal shift s = msb_aligned ? 16 - bits : 0.  No call converts layouts;
+ *   - a row pitch in bytes fits an int: "pitch above 2 GiB" otherwise, from every one of these calls;
+ *   - with more than one destination frame, they do not overlap each other in a plane: each stride is at least (rows - 1) * pitch + row
+ *     bytes, luma and chroma;
+ *   - no destination plane's byte range (first byte of frame 0 .. last byte of the last frame written) overlaps a source plane's (first
+ *     byte of frame 0 .. last byte of the last frame of the batch), over the planes there are: Y and UV when interleaved (V is not
+ *     looked at, and may be anything), Y, U and V otherwise.  So no call works in place.
+ *      Source and destination may differ in pitch, stride, size (resize) and frame count (render, temporal NR).  The comments below
+ *      name only what is particular to each call. ---- */
 /* Renders plan[0 .. nout) into dst's frames 0 .. nout - 1.  src holds source frames [src_first, src_first + nsrc) of a clip of clip_frames
  * frames; width x height is the luma size (both even, height >= 4; chroma planes are width / 2 x height / 2); plan is a HOST array.
  * src and dst must be IN KIND: equal bits (8 or 9..16), equal interleaved, and an equal shift s = msb_aligned ? 16 - bits : 0.  Planes in,
@@ -664,12 +682,10 @@ int  amtgpu_kfm_render_plan(const uint8_t* cadence, const uint8_t* phase, int nf
  * Interleaved chroma: U is one UV plane of height / 2 rows of `width` containers, pitchUV >= width; V is ignored and may be NULL.  The
  * rule is vertical and temporal only, so each U and each V container meets its own plane's column: the result is the interleave of the
  * planar result.  Y and UV of one allocation (strideY == strideUV == the surface size) is the normal case.
- * Returns 0 with a message on ctx, and launches nothing: descriptors not in kind; width or height odd, height < 4; a pitch below the row
- * (pitchUV < width when interleaved, < width / 2 when planar); kind outside 0..2; a BOB entry with top != bottom; a frame number outside
- * the batch; thresh >= 0 and a temporal neighbour (n - 1 for BOB_TOP with n >= 1, n + 1 for BOB_BOTTOM with n + 1 < clip_frames) outside
- * the batch; destination frames that overlap each other in a plane; a destination plane whose byte range (first byte of frame 0 .. last
- * byte of frame nout - 1) overlaps a source plane's -- over the planes there are: Y and UV (rows of width containers) when interleaved,
- * Y, U and V otherwise.  nout == 0 returns 1.
+ * Returns 0 with a message on ctx, and launches nothing: what the source and destination rule above refuses (every layout is taken;
+ * nsrc source frames, nout destination frames); width or height odd, height < 4; kind outside 0..2; a BOB entry with top != bottom; a
+ * frame number outside the batch; thresh >= 0 and a temporal neighbour (n - 1 for BOB_TOP with n >= 1, n + 1 for BOB_BOTTOM with
+ * n + 1 < clip_frames) outside the batch.  nout == 0 returns 1.
  * The bytes written depend on the clip and the plan alone: a clip rendered in several calls, each batch with its one-frame halo, gives
  * the bytes of one call.  Reads nothing outside a row's width (width / 2 in planar chroma) containers of a source row, writes nothing
  * outside them in a destination row.  Synchronises: the plan is copied to the device for the one launch and the copy is freed before the
@@ -738,10 +754,9 @@ int  amtgpu_kfm_render_deint_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* 
  * The bytes depend on the clip and the parameters alone: a clip filtered in batches, each with d frames of halo wherever the clip has
  * them, gives the bytes of one call.
  * Returns 0 with a message on ctx, and launches nothing: temporal_distance outside 0..63; threshold outside 0..32767; bits outside 8..16;
- * src and dst of different bits; a descriptor that is interleaved or MSB-aligned (planar LSB only); width or height odd; interlaced with
- * height % 4 != 0 (the reference reads chroma row height / 2 there); a pitch below the row; a negative frame stride; a window frame
- * outside the batch; an output frame outside the clip; destination frames that overlap each other in a plane; a destination plane whose
- * byte range (first byte of frame 0 .. last byte of frame nout - 1) overlaps a source plane's.  nout == 0 returns 1.
+ * what the source and destination rule above refuses (planar LSB only; nsrc source frames, nout destination frames); width or height
+ * odd; interlaced with height % 4 != 0 (the reference reads chroma row height / 2 there); a window frame outside the batch; an output
+ * frame outside the clip.  nout == 0 returns 1.
  * Reads nothing outside a row's width (width / 2 in chroma) containers of a source row, writes nothing outside them in a destination row.
  * Synchronises, as amtgpu_kfm_render does: dst is complete when the call returns */
 int  amtgpu_temporal_nr(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
@@ -755,8 +770,7 @@ int  amtgpu_temporal_nr(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_f
  * source's low bits never survive.  So dst >> s, de-interleaved, equals amtgpu_temporal_nr of src >> s, de-interleaved, byte for byte,
  * whatever sits in the source's low bits and however the clip is cut into batches with temporal_distance frames of halo.
  * Every refusal of amtgpu_temporal_nr is kept, with its wording, but "planar LSB only": a mixed pair is refused instead ("not in kind
- * ... converts no layouts"); an interleaved descriptor needs pitchUV >= width, and the overlap checks cover its two planes with UV rows
- * of width containers.  Synchronises */
+ * ... converts no layouts"), as the source and destination rule has it for every layout.  Synchronises */
 int  amtgpu_temporal_nr_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* src, int src_first, int nsrc, int clip_frames, int width, int height,
                                  int out_first, int nout, int temporal_distance, int threshold, int interlaced, const AmtGpuSurfaces* dst);
 
@@ -784,10 +798,9 @@ int  amtgpu_temporal_nr_surfaces(AmtGpuContext* ctx, const AmtGpuSurfaces* src, 
  *   chroma planes'); a program whose largest sum of positive coefficients times maxv plus 8192, or likewise of negative ones, leaves
  *   int32; a horizontal window (K samples) that does not fit the kernel's staging region (2000 bytes).
  * amtgpu_resize_run: frames 0 .. nframes - 1 of src (src_w x src_h) into frames 0 .. nframes - 1 of dst (dst_w x dst_h), planar LSB planes
- *   of the resizer's bits.  Returns 0 with a message on ctx, and launches nothing: an interleaved or MSB-aligned descriptor; bits that
- *   are not the resizer's (so unequal bits); a pitch smaller than the row; a negative frame stride; destination frames that overlap each
- *   other in a plane; a destination plane whose byte range (first byte of frame 0 .. last byte of frame nframes - 1) overlaps a source
- *   plane's.  nframes == 0 returns 1.  Reads nothing outside a row's width of a source row, writes nothing outside it in a destination
+ *   of the resizer's bits.  Returns 0 with a message on ctx, and launches nothing: what the source and destination rule above refuses
+ *   (planar LSB only; the resizer's bits, so unequal bits too; each side by its own size; nframes frames on either side).
+ *   nframes == 0 returns 1.  Reads nothing outside a row's width of a source row, writes nothing outside it in a destination
  *   row; the source is never written.  All rounds run in the context's stream.  Synchronises, as amtgpu_temporal_nr does.
  * amtgpu_resize_run_surfaces: the same object, rounds, scratch bound and checks on decoder surfaces where they lie, source and
  *   destination IN KIND: equal bits (the resizer's), interleaved and msb_aligned -- NV12, interleaved LSB, P010 / P012 / P016, planar MSB.
@@ -839,10 +852,9 @@ int  amtgpu_resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int
  *   non-positive size, or one above 65534 (the hash key packs y << 16 | x); bits outside 8..16; radius outside 1..31; threshold outside
  *   0..32767; sample outside 0..2.
  * amtgpu_deband_run: frames 0 .. nframes - 1 of src into frames 0 .. nframes - 1 of dst, planar LSB planes of the object's size and
- *   bits, in one launch.  Returns 0 with a message on ctx, and launches nothing: an interleaved or MSB-aligned descriptor (planar LSB
- *   only); bits that are not the object's; a pitch below the row; a negative frame stride; destination frames that overlap each other
- *   in a plane; a destination plane whose byte range (first byte of frame 0 .. last byte of frame nframes - 1) overlaps a source
- *   plane's -- in-place is impossible here, the filter reads neighbours.  nframes == 0 returns 1.  Reads nothing outside the first Wp
+ *   bits, in one launch.  Returns 0 with a message on ctx, and launches nothing: what the source and destination rule above refuses
+ *   (planar LSB only; the object's bits; nframes frames on either side) -- in-place is impossible here, the filter reads neighbours.
+ *   nframes == 0 returns 1.  Reads nothing outside the first Wp
  *   containers of a source row and writes nothing outside them in a destination row; every container of the output frames is written;
  *   the source is never written.  Synchronises, as amtgpu_resize_run does.
  * amtgpu_deband_get_offsets: plane p's table, Wp * Hp int8 each, row-major (either pointer may be NULL).

@@ -254,27 +254,28 @@ def test_refusals_write_nothing(gpu):
 
     # run
     cases = {
-        "interleaved source": (db, changed(s, interleaved=1), t, N),
-        "interleaved destination": (db, s, changed(t, interleaved=1), N),
-        "MSB-aligned source": (db10, changed(s, bits=10, msb_aligned=1), changed(t, bits=10), N),
-        "MSB-aligned destination": (db10, changed(s, bits=10), changed(t, bits=10, msb_aligned=1), N),
-        "bits that are not the object's": (db10, s, t, N),
-        "source of other bits": (db, changed(s, bits=10), t, N),
-        "destination of other bits": (db, s, changed(t, bits=10), N),
-        "source pitch below the row": (db, changed(s, pitchY=w - 2), t, N),
-        "destination chroma pitch below the row": (db, s, changed(t, pitchUV=w // 2 - 1), N),
-        "negative source stride": (db, changed(s, strideY=-s.strideY), t, N),
-        "negative destination chroma stride": (db, s, changed(t, strideUV=-t.strideUV), N),
-        "negative frame count": (db, s, t, -1),
-        "overlapping destination frames": (db, s, changed(t, strideY=(h - 1) * t.pitchY + w - 1), 2),
-        "destination is the source": (db, s, s, N),
-        "destination luma inside the source's chroma": (db, s, changed(t, Y=s.U), 1),
-        "destination one byte into the source": (db, s, changed(t, V=s.Y + s.strideY * (N - 1) + (h - 1) * s.pitchY + w - 1), N),
-        "null source plane": (db, changed(s, V=None), t, N),
+        # name: (arguments..., words the message must hold)
+        "interleaved source": (db, changed(s, interleaved=1), t, N, "source: planar, LSB-aligned planes only"),
+        "interleaved destination": (db, s, changed(t, interleaved=1), N, "destination: planar, LSB-aligned planes only"),
+        "MSB-aligned source": (db10, changed(s, bits=10, msb_aligned=1), changed(t, bits=10), N, "source: planar, LSB-aligned planes only"),
+        "MSB-aligned destination": (db10, changed(s, bits=10), changed(t, bits=10, msb_aligned=1), N, "destination: planar, LSB-aligned planes only"),
+        "bits that are not the object's": (db10, s, t, N, "source: 8 bits, the debander was created for 10"),
+        "source of other bits": (db, changed(s, bits=10), t, N, "source: 10 bits, the debander was created for 8"),
+        "destination of other bits": (db, s, changed(t, bits=10), N, "destination: 10 bits, the debander was created for 8"),
+        "source pitch below the row": (db, changed(s, pitchY=w - 2), t, N, "source: pitch smaller than the row"),
+        "destination chroma pitch below the row": (db, s, changed(t, pitchUV=w // 2 - 1), N, "destination: pitch smaller than the row"),
+        "negative source stride": (db, changed(s, strideY=-s.strideY), t, N, "source: negative frame stride"),
+        "negative destination chroma stride": (db, s, changed(t, strideUV=-t.strideUV), N, "destination: negative frame stride"),
+        "negative frame count": (db, s, t, -1, "negative frame count"),
+        "overlapping destination frames": (db, s, changed(t, strideY=(h - 1) * t.pitchY + w - 1), 2, "destination frames overlap each other"),
+        "destination is the source": (db, s, s, N, "overlaps the source's"),
+        "destination luma inside the source's chroma": (db, s, changed(t, Y=s.U), 1, "overlaps the source's"),
+        "destination one byte into the source": (db, s, changed(t, V=s.Y + s.strideY * (N - 1) + (h - 1) * s.pitchY + w - 1), N, "overlaps the source's"),
+        "null source plane": (db, changed(s, V=None), t, N, "null surface plane"),
     }
-    for what, args in cases.items():
+    for what, (*args, words) in cases.items():
         r, msg = call(*args)
-        assert r == 0 and "[Deband]" in msg, (what, msg)
+        assert r == 0 and "[Deband]" in msg and words in msg, (what, msg)
     assert call(db, s, t, 0)[0] == 1                                    # nothing to filter: 1
     with pytest.raises(AmtError):
         db.run(src, cut(dst, 0, 2))                                     # more frames than dst holds

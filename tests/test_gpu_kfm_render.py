@@ -266,39 +266,43 @@ def test_refusals_launch_nothing(gpu):
 
     mid = DeviceSurfaces(src.Y[2:5], src.U[2:5], src.V[2:5], W, H, 8).ref()            # frames 2..4 of a clip of 8
     cases = {
-        "odd width": (s, 0, N, N, W - 1, H, ok, -1, d),
-        "odd height": (s, 0, N, N, W, H - 1, ok, -1, d),
-        "height below 4": (s, 0, N, N, W, 2, ok, -1, d),
-        "kind 3": (s, 0, N, N, W, H, plan((3, 0, 0, 2)), -1, d),
-        "kind -1": (s, 0, N, N, W, H, plan((W_, 0, 0, 2), (-1, 0, 0, 2)), -1, d),
-        "BOB_TOP with top != bottom": (s, 0, N, N, W, H, plan((T_, 1, 2, 1)), -1, d),
-        "BOB_BOTTOM with top != bottom": (s, 0, N, N, W, H, plan((B_, 2, 1, 1)), -1, d),
-        "top behind the batch": (s, 0, N, N, W, H, plan((W_, N, 0, 2)), -1, d),
-        "bottom negative": (s, 0, N, N, W, H, plan((W_, 0, -1, 2)), -1, d),
-        "top before src_first": (mid, 2, 3, 8, W, H, plan((W_, 1, 2, 2)), -1, d),
-        "bottom behind src_first + nsrc": (mid, 2, 3, 8, W, H, plan((W_, 2, 5, 2)), -1, d),
-        "BOB_TOP without frame n - 1": (mid, 2, 3, 8, W, H, plan((T_, 2, 2, 1)), 0, d),
-        "BOB_BOTTOM without frame n + 1": (mid, 2, 3, 8, W, H, plan((B_, 4, 4, 1)), 5, d),
-        "batch outside the clip": (s, 3, N, N, W, H, plan((W_, 3, 3, 2)), -1, d),
-        "destination is the source": (s, 0, N, N, W, H, ok, -1, s),
-        "destination luma inside the source's chroma": (s, 0, N, N, W, H, ok, -1, changed(d, Y=s.U)),
-        "destination one byte into the source": (s, 0, N, N, W, H, ok, -1, changed(d, V=s.Y + s.strideY * N - 1)),
-        "NV12 source": (changed(s, interleaved=1), 0, N, N, W, H, ok, -1, d),
-        "NV12 destination": (s, 0, N, N, W, H, ok, -1, changed(d, interleaved=1)),
-        "MSB-aligned source": (changed(s, bits=10, msb_aligned=1), 0, N, N, W, H, ok, -1, changed(d, bits=10)),
-        "different depths": (s, 0, N, N, W, H, ok, -1, changed(d, bits=10)),
-        "source pitch below the row": (changed(s, pitchY=W - 2), 0, N, N, W, H, ok, -1, d),
-        "destination chroma pitch below the row": (s, 0, N, N, W, H, ok, -1, changed(d, pitchUV=W // 2 - 1)),
-        "overlapping destination frames": (s, 0, N, N, W, H, plan((W_, 0, 0, 2), (W_, 1, 1, 2)), -1, changed(d, strideY=H * 96 - 1)),
+        # name: (arguments, words the message must hold: the shared source/destination rule's refusals by their phrase)
+        "odd width": ((s, 0, N, N, W - 1, H, ok, -1, d), "even"),
+        "odd height": ((s, 0, N, N, W, H - 1, ok, -1, d), "even"),
+        "height below 4": ((s, 0, N, N, W, 2, ok, -1, d), "at least 4"),
+        "kind 3": ((s, 0, N, N, W, H, plan((3, 0, 0, 2)), -1, d), "kind outside 0..2"),
+        "kind -1": ((s, 0, N, N, W, H, plan((W_, 0, 0, 2), (-1, 0, 0, 2)), -1, d), "plan entry 1: kind outside 0..2"),
+        "BOB_TOP with top != bottom": ((s, 0, N, N, W, H, plan((T_, 1, 2, 1)), -1, d), "top == bottom"),
+        "BOB_BOTTOM with top != bottom": ((s, 0, N, N, W, H, plan((B_, 2, 1, 1)), -1, d), "top == bottom"),
+        "top behind the batch": ((s, 0, N, N, W, H, plan((W_, N, 0, 2)), -1, d), "top frame 6 is outside the batch"),
+        "bottom negative": ((s, 0, N, N, W, H, plan((W_, 0, -1, 2)), -1, d), "bottom frame -1 is outside the batch"),
+        "top before src_first": ((mid, 2, 3, 8, W, H, plan((W_, 1, 2, 2)), -1, d), "top frame 1 is outside the batch"),
+        "bottom behind src_first + nsrc": ((mid, 2, 3, 8, W, H, plan((W_, 2, 5, 2)), -1, d), "bottom frame 5 is outside the batch"),
+        "BOB_TOP without frame n - 1": ((mid, 2, 3, 8, W, H, plan((T_, 2, 2, 1)), 0, d), "the temporal neighbour 1 "),
+        "BOB_BOTTOM without frame n + 1": ((mid, 2, 3, 8, W, H, plan((B_, 4, 4, 1)), 5, d), "the temporal neighbour 5 "),
+        "batch outside the clip": ((s, 3, N, N, W, H, plan((W_, 3, 3, 2)), -1, d), "does not lie inside the clip"),
+        "destination is the source": ((s, 0, N, N, W, H, ok, -1, s), "overlaps the source's"),
+        "destination luma inside the source's chroma": ((s, 0, N, N, W, H, ok, -1, changed(d, Y=s.U)), "overlaps the source's"),
+        "destination one byte into the source": ((s, 0, N, N, W, H, ok, -1, changed(d, V=s.Y + s.strideY * N - 1)), "overlaps the source's"),
+        "NV12 source": ((changed(s, interleaved=1, pitchUV=W), 0, N, N, W, H, ok, -1, d), "not in kind"),
+        "NV12 destination": ((s, 0, N, N, W, H, ok, -1, changed(d, interleaved=1, pitchUV=W)), "not in kind"),
+        "MSB-aligned source": ((changed(s, bits=10, msb_aligned=1), 0, N, N, W, H, ok, -1, changed(d, bits=10)), "not in kind"),
+        "different depths": ((s, 0, N, N, W, H, ok, -1, changed(d, bits=10)), "differ in bits"),
+        "source pitch below the row": ((changed(s, pitchY=W - 2), 0, N, N, W, H, ok, -1, d), "source: pitch smaller than the row"),
+        "destination chroma pitch below the row": ((s, 0, N, N, W, H, ok, -1, changed(d, pitchUV=W // 2 - 1)), "destination: pitch smaller than the row"),
+        "overlapping destination frames": ((s, 0, N, N, W, H, plan((W_, 0, 0, 2), (W_, 1, 1, 2)), -1, changed(d, strideY=H * 96 - 1)), "destination frames overlap each other"),
         "null plan": None,
+        "negative source stride": ((changed(s, strideY=-s.strideY), 0, N, N, W, H, ok, -1, d), "source: negative frame stride"),
+        "negative destination chroma stride": ((s, 0, N, N, W, H, ok, -1, changed(d, strideUV=-d.strideUV)), "destination: negative frame stride"),
     }
-    for what, args in cases.items():
-        if args is None:
+    for what, case in cases.items():
+        if case is None:
             r = ctx.lib.amtgpu_kfm_render(ctx.h, C.byref(s), 0, N, N, W, H, None, 1, -1, C.byref(d))
-            msg = ctx.lib.amtgpu_last_error(ctx.h).decode(errors="replace")
+            msg, words = ctx.lib.amtgpu_last_error(ctx.h).decode(errors="replace"), "null plan"
         else:
-            r, msg = raw_render(ctx, *args)
-        assert r == 0 and msg.strip(), what
+            r, msg = raw_render(ctx, *case[0])
+            words = case[1]
+        assert r == 0 and "[KFMRender]" in msg and words in msg, (what, msg)
     assert raw_render(ctx, s, 0, N, N, W, H, ok, -1, d, nout=-1)[0] == 0
     assert raw_render(ctx, s, 0, N, N, W, H, ok, 0, d, nout=0)[0] == 1                                # nothing to render: 1
     with pytest.raises(AmtError, match="KFMRender"):

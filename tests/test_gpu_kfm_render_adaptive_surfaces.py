@@ -292,11 +292,15 @@ def test_refusals_launch_nothing_and_python_takes_surfaces(gpu):
         "BOB_BOTTOM without frame n + 1": ((mid, 2, 3, 8, W, H, plan((B_, 4, 4, 1)), ADAPTIVE, -1, nv12_d), "plan entry 0: the neighbour frame 5 "),
         "NV12 into planes": ((nv12_s, 0, N, N, W, H, ok, ADAPTIVE, -1, pl8_d), "not in kind"),
         "planes into NV12": ((pl8_s, 0, N, N, W, H, ok, ADAPTIVE, -1, nv12_d), "not in kind"),
-        "P010 into NV12": ((p010_s, 0, N, N, W, H, ok, ADAPTIVE, -1, nv12_d), "bits"),
+        "P010 into NV12": ((p010_s, 0, N, N, W, H, ok, ADAPTIVE, -1, nv12_d), "differ in bits"),
         "P010 into P012": ((p010_s, 0, N, N, W, H, ok, ADAPTIVE, -1, p012_d), "bits"),
         "P010 into a descriptor that says P012": ((p010_s, 0, N, N, W, H, ok, ADAPTIVE, -1, GS.changed(p010_d, bits=12)), "bits"),
-        "destination is the source": ((nv12_s, 0, N, N, W, H, ok, ADAPTIVE, -1, nv12_s), ""),
-        "odd width": ((nv12_s, 0, N, N, W - 1, H, ok, ADAPTIVE, -1, nv12_d), ""),
+        "destination is the source": ((nv12_s, 0, N, N, W, H, ok, ADAPTIVE, -1, nv12_s), "overlaps the source's"),
+        "odd width": ((nv12_s, 0, N, N, W - 1, H, ok, ADAPTIVE, -1, nv12_d), "even"),
+        "source pitchUV below width": ((GS.changed(nv12_s, pitchUV=W - 2), 0, N, N, W, H, ok, ADAPTIVE, -1, nv12_d), "source: pitch smaller than the row"),
+        "negative destination stride": ((p010_s, 0, N, N, W, H, ok, ADAPTIVE, -1, GS.changed(p010_d, strideY=-p010_d.strideY)), "destination: negative frame stride"),
+        "overlapping destination UV frames": ((nv12_s, 0, N, N, W, H, plan((T_, 2, 2, 1), (B_, 2, 2, 1)), ADAPTIVE, -1, GS.changed(nv12_d, strideUV=(H // 2) * nv12_d.pitchUV - 1)),
+                                              "destination frames overlap each other"),
     }
     for what, (args, word) in cases.items():
         r, msg = raw_deint_surfaces(ctx, *args)

@@ -302,26 +302,29 @@ def test_refusals_launch_nothing_and_null_v_is_accepted(gpu):
     pm10_s, pm10_d = pair("planar-msb-10", (W, H, 10, False, True, 96, 48, 0, 0, False))
     assert nv12_s.strideY == nv12_s.strideUV == W * H * 3 // 2 and nv12_s.U == nv12_s.Y + W * H and not nv12_s.V and not nv12_d.V
     cases = {
+        # name: (source, destination, words the message must hold)
         # not in kind
-        "NV12 into planes": (nv12_s, pl8_d),
-        "planes into NV12": (pl8_s, nv12_d),
-        "P010 into planar MSB": (p010_s, pm10_d),
-        "planar MSB into P010": (pm10_s, p010_d),
-        "P010 into interleaved LSB (shift 6 against 0)": (p010_s, il10_d),
-        "interleaved LSB into P010": (il10_s, p010_d),
-        "P010 into P012 (bits, and shift 6 against 4)": (p010_s, p012_d),
-        "P012 into P010": (p012_s, p010_d),
-        "P010 into a descriptor that says P012 of the same planes' layout": (p010_s, changed(p010_d, bits=12)),
+        "NV12 into planes": (nv12_s, pl8_d, "not in kind"),
+        "planes into NV12": (pl8_s, nv12_d, "not in kind"),
+        "P010 into planar MSB": (p010_s, pm10_d, "not in kind"),
+        "planar MSB into P010": (pm10_s, p010_d, "not in kind"),
+        "P010 into interleaved LSB (shift 6 against 0)": (p010_s, il10_d, "converts no layouts"),
+        "interleaved LSB into P010": (il10_s, p010_d, "converts no layouts"),
+        "P010 into P012 (bits, and shift 6 against 4)": (p010_s, p012_d, "differ in bits"),
+        "P012 into P010": (p012_s, p010_d, "differ in bits"),
+        "P010 into a descriptor that says P012 of the same planes' layout": (p010_s, changed(p010_d, bits=12), "differ in bits"),
         # in kind, and refused all the same
-        "interleaved source pitchUV below width": (changed(nv12_s, pitchUV=W - 2), nv12_d),
-        "interleaved destination pitchUV below width": (nv12_s, changed(nv12_d, pitchUV=W - 2)),
-        "destination Y inside the source's UV plane": (nv12_s, changed(nv12_d, Y=nv12_s.U)),
-        "destination UV over the source's Y plane": (nv12_s, changed(nv12_d, U=nv12_s.Y)),
-        "overlapping destination frames on the UV plane": (nv12_s, changed(nv12_d, strideUV=(H // 2) * 96 - 1)),
+        "interleaved source pitchUV below width": (changed(nv12_s, pitchUV=W - 2), nv12_d, "source: pitch smaller than the row"),
+        "interleaved destination pitchUV below width": (nv12_s, changed(nv12_d, pitchUV=W - 2), "destination: pitch smaller than the row"),
+        "destination Y inside the source's UV plane": (nv12_s, changed(nv12_d, Y=nv12_s.U), "overlaps the source's"),
+        "destination UV over the source's Y plane": (nv12_s, changed(nv12_d, U=nv12_s.Y), "overlaps the source's"),
+        "overlapping destination frames on the UV plane": (nv12_s, changed(nv12_d, strideUV=(H // 2) * 96 - 1), "destination frames overlap each other"),
+        "negative source stride": (changed(p010_s, strideY=-p010_s.strideY), p010_d, "source: negative frame stride"),
+        "negative destination UV stride": (nv12_s, changed(nv12_d, strideUV=-nv12_d.strideUV), "destination: negative frame stride"),
     }
-    for what, (s, d) in cases.items():
+    for what, (s, d, words) in cases.items():
         r, msg = raw_render(ctx, s, 0, N, N, W, H, ok, 0, d)
-        assert r == 0 and msg.strip() and "KFMRender" in msg, (what, r, msg)
+        assert r == 0 and "[KFMRender]" in msg and words in msg, (what, r, msg)
     torch.cuda.synchronize()
     for name, both in clips.items():
         for host, _, flat_t in both:

@@ -357,37 +357,40 @@ def test_refusals_launch_nothing(gpu):
 
     es_pitchY = t.pitchY
     cases = {
-        "temporal_distance -1": (s, 0, N, N, w, h, 0, N, -1, 1, 0, t),
-        "temporal_distance 64": (s, 0, N, N, w, h, 0, N, 64, 1, 0, t),
-        "threshold -1": (s, 0, N, N, w, h, 0, N, 3, -1, 0, t),
-        "threshold 32768": (s, 0, N, N, w, h, 0, N, 3, 32768, 0, t),
-        "bits 7": (changed(s, bits=7), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=7)),
-        "bits 17": (changed(s, bits=17), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=17)),
-        "different depths": (s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=10)),
-        "interleaved source": (changed(s, interleaved=1), 0, N, N, w, h, 0, N, 3, 1, 0, t),
-        "interleaved destination": (s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, interleaved=1)),
-        "MSB-aligned source": (changed(s, bits=10, msb_aligned=1), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=10)),
-        "MSB-aligned destination": (changed(s, bits=10), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=10, msb_aligned=1)),
-        "odd width": (s, 0, N, N, w - 1, h, 0, N, 3, 1, 0, t),
-        "odd height": (s, 0, N, N, w, h - 1, 0, N, 3, 1, 0, t),
-        "interlaced with height % 4 == 2": (s, 0, N, N, w, h - 2, 0, N, 3, 1, 1, t),
-        "source pitch below the row": (changed(s, pitchY=w - 2), 0, N, N, w, h, 0, N, 3, 1, 0, t),
-        "destination chroma pitch below the row": (s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, pitchUV=w // 2 - 1)),
-        "window frame before the batch": (mid, 2, 4, N, w, h, 4, 1, 3, 1, 0, t),
-        "window frame behind the batch": (mid, 2, 4, N, w, h, 5, 1, 1, 1, 0, t),
-        "batch outside the clip": (s, 3, N, N, w, h, 3, 1, 0, 1, 0, t),
-        "output frame behind the clip": (s, 0, N, N, w, h, N - 1, 2, 0, 1, 0, t),
-        "output frame before the clip": (s, 0, N, N, w, h, -1, 2, 0, 1, 0, t),
-        "negative output count": (s, 0, N, N, w, h, 0, -1, 3, 1, 0, t),
-        "overlapping destination frames": (s, 0, N, N, w, h, 0, 2, 3, 1, 0, changed(t, strideY=(h - 1) * es_pitchY + w - 1)),
-        "destination is the source": (s, 0, N, N, w, h, 0, N, 3, 1, 0, s),
-        "destination luma inside the source's chroma": (s, 0, N, N, w, h, 0, 1, 3, 1, 0, changed(t, Y=s.U)),
-        "destination one byte into the source": (s, 0, N, N, w, h, 0, 1, 3, 1, 0, changed(t, V=s.Y + s.strideY * (N - 1) + (h - 1) * s.pitchY + w - 1)),
+        # name: (arguments, words the message must hold: the shared source/destination rule's refusals by their phrase)
+        "temporal_distance -1": ((s, 0, N, N, w, h, 0, N, -1, 1, 0, t), "temporal_distance"),
+        "temporal_distance 64": ((s, 0, N, N, w, h, 0, N, 64, 1, 0, t), "temporal_distance"),
+        "threshold -1": ((s, 0, N, N, w, h, 0, N, 3, -1, 0, t), "threshold"),
+        "threshold 32768": ((s, 0, N, N, w, h, 0, N, 3, 32768, 0, t), "threshold"),
+        "bits 7": ((changed(s, bits=7), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=7)), "bits"),
+        "bits 17": ((changed(s, bits=17), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=17)), "bits"),
+        "different depths": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=10)), "differ in bits"),
+        "interleaved source": ((changed(s, interleaved=1), 0, N, N, w, h, 0, N, 3, 1, 0, t), "source: planar, LSB-aligned planes only"),
+        "interleaved destination": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, interleaved=1)), "destination: planar, LSB-aligned planes only"),
+        "MSB-aligned source": ((changed(s, bits=10, msb_aligned=1), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=10)), "source: planar, LSB-aligned planes only"),
+        "MSB-aligned destination": ((changed(s, bits=10), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=10, msb_aligned=1)), "destination: planar, LSB-aligned planes only"),
+        "odd width": ((s, 0, N, N, w - 1, h, 0, N, 3, 1, 0, t), "even"),
+        "odd height": ((s, 0, N, N, w, h - 1, 0, N, 3, 1, 0, t), "even"),
+        "interlaced with height % 4 == 2": ((s, 0, N, N, w, h - 2, 0, N, 3, 1, 1, t), "multiple of 4"),
+        "source pitch below the row": ((changed(s, pitchY=w - 2), 0, N, N, w, h, 0, N, 3, 1, 0, t), "source: pitch smaller than the row"),
+        "destination chroma pitch below the row": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, pitchUV=w // 2 - 1)), "destination: pitch smaller than the row"),
+        "window frame before the batch": ((mid, 2, 4, N, w, h, 4, 1, 3, 1, 0, t), "window frame 1 "),
+        "window frame behind the batch": ((mid, 2, 4, N, w, h, 5, 1, 1, 1, 0, t), "window frame 6 "),
+        "batch outside the clip": ((s, 3, N, N, w, h, 3, 1, 0, 1, 0, t), "does not lie inside the clip"),
+        "output frame behind the clip": ((s, 0, N, N, w, h, N - 1, 2, 0, 1, 0, t), "outside the clip"),
+        "output frame before the clip": ((s, 0, N, N, w, h, -1, 2, 0, 1, 0, t), "outside the clip"),
+        "negative output count": ((s, 0, N, N, w, h, 0, -1, 3, 1, 0, t), "negative"),
+        "overlapping destination frames": ((s, 0, N, N, w, h, 0, 2, 3, 1, 0, changed(t, strideY=(h - 1) * es_pitchY + w - 1)), "destination frames overlap each other"),
+        "destination is the source": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, s), "overlaps the source's"),
+        "destination luma inside the source's chroma": ((s, 0, N, N, w, h, 0, 1, 3, 1, 0, changed(t, Y=s.U)), "overlaps the source's"),
+        "destination one byte into the source": ((s, 0, N, N, w, h, 0, 1, 3, 1, 0, changed(t, V=s.Y + s.strideY * (N - 1) + (h - 1) * s.pitchY + w - 1)), "overlaps the source's"),
+        "negative source stride": ((changed(s, strideY=-s.strideY), 0, N, N, w, h, 0, N, 3, 1, 0, t), "source: negative frame stride"),
+        "negative destination chroma stride": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, strideUV=-t.strideUV)), "destination: negative frame stride"),
     }
-    for what, args in cases.items():
+    for what, (args, words) in cases.items():
         r, msg = call(*args)
         assert r == 0 and msg.strip(), what
-        assert "TemporalNR" in msg, (what, msg)
+        assert "TemporalNR" in msg and words in msg, (what, msg)
     assert call(s, 0, N, N, w, h, 0, 0, 3, 1, 0, t)[0] == 1                                          # nothing to filter: 1
     with pytest.raises(AmtError, match="TemporalNR"):
         temporal_nr(ctx, src, dst, distance=64)

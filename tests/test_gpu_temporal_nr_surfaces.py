@@ -435,19 +435,21 @@ def test_refusals_launch_nothing(gpu):
         "planar LSB into planar MSB": ((pl10_s, 0, N, N, w, h, 0, N, 3, 1, 0, pmsb_d), "converts no layouts"),
         "P010 into NV12": ((p010_s, 0, N, N, w, h, 0, N, 3, 1, 0, t), "bits"),
         "P010 into a descriptor that says P012": ((p010_s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(p010_d, bits=12)), "bits"),
-        "interleaved source pitchUV below width": ((changed(s, pitchUV=w - 2), 0, N, N, w, h, 0, N, 3, 1, 0, t), "pitch smaller than the row"),
-        "interleaved destination pitchUV below width": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, pitchUV=w - 1)), "pitch smaller than the row"),
-        "destination is the source": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, s), "overlaps"),
-        "destination UV inside the source's luma": ((s, 0, N, N, w, h, 0, 1, 3, 1, 0, changed(t, U=s.Y)), "overlaps"),
-        "destination luma on the last byte of the source's UV rows": ((s, 0, N, N, w, h, 0, 1, 3, 1, 0, changed(t, Y=last_uv_byte)), "overlaps"),
-        "overlapping destination UV frames": ((s, 0, N, N, w, h, 0, 2, 3, 1, 0, changed(t, strideUV=(hUV - 1) * t.pitchUV + w - 1)), "overlap each other"),
+        "interleaved source pitchUV below width": ((changed(s, pitchUV=w - 2), 0, N, N, w, h, 0, N, 3, 1, 0, t), "source: pitch smaller than the row"),
+        "interleaved destination pitchUV below width": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, pitchUV=w - 1)), "destination: pitch smaller than the row"),
+        "destination is the source": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, s), "overlaps the source's"),
+        "destination UV inside the source's luma": ((s, 0, N, N, w, h, 0, 1, 3, 1, 0, changed(t, U=s.Y)), "overlaps the source's"),
+        "destination luma on the last byte of the source's UV rows": ((s, 0, N, N, w, h, 0, 1, 3, 1, 0, changed(t, Y=last_uv_byte)), "overlaps the source's"),
+        "overlapping destination UV frames": ((s, 0, N, N, w, h, 0, 2, 3, 1, 0, changed(t, strideUV=(hUV - 1) * t.pitchUV + w - 1)), "destination frames overlap each other"),
+        "negative source stride": ((changed(p010_s, strideY=-p010_s.strideY), 0, N, N, w, h, 0, N, 3, 1, 0, p010_d), "source: negative frame stride"),
+        "negative destination UV stride": ((s, 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, strideUV=-t.strideUV)), "destination: negative frame stride"),
         "temporal_distance 64": ((s, 0, N, N, w, h, 0, N, 64, 1, 0, t), "temporal_distance"),
         "threshold -1": ((p010_s, 0, N, N, w, h, 0, N, 3, -1, 0, p010_d), "threshold"),
         "bits 7": ((changed(s, bits=7), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, bits=7)), "bits"),
         "MSB-aligned at 8 bits": ((changed(s, msb_aligned=1), 0, N, N, w, h, 0, N, 3, 1, 0, changed(t, msb_aligned=1)), "MSB"),
         "odd width": ((s, 0, N, N, w - 1, h, 0, N, 3, 1, 0, t), "even"),
         "interlaced with height % 4 == 2": ((p010_s, 0, N, N, w, h - 2, 0, N, 3, 1, 1, p010_d), "multiple of 4"),
-        "source luma pitch below the row": ((changed(s, pitchY=w - 2), 0, N, N, w, h, 0, N, 3, 1, 0, t), "pitch smaller than the row"),
+        "source luma pitch below the row": ((changed(s, pitchY=w - 2), 0, N, N, w, h, 0, N, 3, 1, 0, t), "source: pitch smaller than the row"),
         "null UV plane": ((changed(s, U=None), 0, N, N, w, h, 0, N, 3, 1, 0, t), "null"),
         "window frame before the batch": ((mid, 2, 4, N, w, h, 4, 1, 3, 1, 0, t), "window frame 1 "),
         "window frame behind the batch": ((mid, 2, 4, N, w, h, 5, 1, 1, 1, 0, t), "window frame 6 "),
