@@ -1168,7 +1168,7 @@ class Resizer:
 
 
 class Debander:
-    """Deband of clips in HBM, planar LSB planes (amtgpu_deband_*): the KDeband(25, 1, 2, true) behind KTemporalNR
+    """Deband of clips in HBM, planar or decoder surfaces in kind (amtgpu_deband_*): the KDeband(25, 1, 2, true) behind KTemporalNR
     in the server's chain, integer and exact.  Per pixel up to four references at the offsets of a table that is static over frames
     (a hash of the position, the plane and `seed`; |dx|, |dy| <= min(radius, distance to the plane's edge), chroma at radius >> 1):
     sample 0 takes the first reference, 1 the mean of a pair, 2 the mean of two pairs at right angles; blur_first compares the mean with
@@ -1183,8 +1183,11 @@ class Debander:
         ctx.check(self.h, "Debander")
 
     def run(self, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSurfaces | DeviceClip"):
-        """frames 0 .. src.num_frames - 1 of src into the same frames of dst, planar LSB planes of the debander's size and bits; dst
-        must not overlap src.  Synchronises.  Returns the number of frames"""
+        """frames 0 .. src.num_frames - 1 of src into the same frames of dst, both of the debander's size and bits; dst must not overlap
+        src.  Planar LSB planes go to amtgpu_deband_run; where either is interleaved or MSB-aligned (NV12, P010 / P012 / P016,
+        interleaved LSB, planar MSB) the pair goes to amtgpu_deband_run_surfaces and must be in kind: the rule runs on container >>
+        shift, U and V each on its own with its own table, and every destination container is result << shift with zero low bits.
+        Synchronises.  Returns the number of frames"""
         n = src.num_frames
         if n > dst.num_frames:
             raise AmtError(f"Debander: {n} frames, dst holds {dst.num_frames}")
@@ -1192,7 +1195,9 @@ class Debander:
             if (int(c.width), int(c.height)) != (self.width, self.height):
                 raise AmtError(f"Debander: made for {self.width}x{self.height}, got {c.width}x{c.height}")
         s, t = _surfaces_ref(src), _surfaces_ref(dst)
-        self.ctx.check(self.ctx.lib.amtgpu_deband_run(self.h, C.byref(s), C.byref(t), n), "Debander")
+        in_kind = s.interleaved or s.msb_aligned or t.interleaved or t.msb_aligned
+        run = self.ctx.lib.amtgpu_deband_run_surfaces if in_kind else self.ctx.lib.amtgpu_deband_run
+        self.ctx.check(run(self.h, C.byref(s), C.byref(t), n), "Debander")
         return n
 
     def _plane_shape(self, plane):

@@ -190,6 +190,7 @@ SIGNATURES = {
     "amtgpu_deband_create": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, C.c_uint32]),
     "amtgpu_deband_destroy": (None, [c_p]),
     "amtgpu_deband_run": (c_i, [c_p, c_p, c_p, c_i]),
+    "amtgpu_deband_run_surfaces": (c_i, [c_p, c_p, c_p, c_i]),
     "amtgpu_deband_get_offsets": (c_i, [c_p, c_i, c_p, c_p]),
     "amtgpu_deband_set_offsets": (c_i, [c_p, c_i, c_p, c_p]),
     "amtgpu_cm_write_chapter_exe": (c_i, [c_p, c_i, c_i, c_s]),

@@ -48,6 +48,7 @@ SOURCES = [
     "resize_plan.cpp",
     "amt_gpu_deband.hip",
     "deband_kernels.hip",
+    "deband_surface_kernels.hip",
     "deband_plan.cpp",
     "logo_model.cpp",
     "logo_fit.cpp",

@@ -38,4 +38,17 @@ long long deband_first_offset_outside(const int8_t* dx, const int8_t* dy, int W,
     return -1;
 }
 
+std::vector<int8_t> deband_interleave(const std::vector<int8_t>& u, const std::vector<int8_t>& v, int W, int H, int pitch)
+{
+    if (W < 1 || H < 1 || pitch < 2 * W || u.size() != (size_t)W * H || v.size() != u.size())
+        throw std::invalid_argument("deband_interleave: two tables of W x H entries and a pitch of at least 2 W");
+    std::vector<int8_t> out((size_t)pitch * H, 0);
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            out[(size_t)y * pitch + 2 * x] = u[(size_t)y * W + x];
+            out[(size_t)y * pitch + 2 * x + 1] = v[(size_t)y * W + x];
+        }
+    return out;
+}
+
 } // namespace amt

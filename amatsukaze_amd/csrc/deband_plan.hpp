@@ -42,5 +42,9 @@ struct DebandTable {
 DebandTable deband_table(int plane, int W, int H, int R, uint32_t seed);
 // The first entry (row-major index) of a caller's table whose |dx| or |dy| exceeds lim(x, y), or -1 where every entry is inside
 long long deband_first_offset_outside(const int8_t* dx, const int8_t* dy, int W, int H, int R);
+// One of dx / dy of the interleaved UV plane of a decoder surface, which the surface kernels walk as one plane of 2 W containers by H
+// rows: u's entry at 2x and v's at 2x + 1 of rows `pitch` entries apart (pitch >= 2 W; the entries behind 2 W are zero).  u and v are
+// W x H, row-major.  Throws std::invalid_argument otherwise
+std::vector<int8_t> deband_interleave(const std::vector<int8_t>& u, const std::vector<int8_t>& v, int W, int H, int pitch);
 
 } // namespace amt

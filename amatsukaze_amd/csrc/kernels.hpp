@@ -232,6 +232,55 @@ inline bool deband_grid(const DebandArgs& a, int nframes, DebandGrid& g)
 // One launch for all planes and frames; none when nframes <= 0
 hipError_t launch_deband(hipStream_t st, const DebandArgs& a, int nframes);
 
+// ---- deband_surface_kernels.hip ----
+// The same rule on decoder surfaces in kind (NV12, interleaved 16-bit LSB, P010 / P012 / P016, planar 16-bit MSB), the planar kernel's
+// shape: the same tile, LDS pitch and bytes.  nplanes 3: Y, U, V each a plane of its own.  nplanes 2 (interleaved): Y and the UV plane,
+// which is walked as ONE plane of `width` containers by height / 2 rows whose table holds U's entry at 2x and V's at 2x + 1 and whose
+// cell steps 2 containers per unit of a horizontal offset; it stages RX = 2 * (radius >> 1) columns and RY = radius >> 1 rows of halo
+// where a plane of its own has RX = RY = its radius.  shift = 16 - bits where MSB-aligned: LDS holds container >> shift, the rule runs
+// on those samples (thresh counts them), and every destination container is result << shift
+static_assert(2 * (kDebandHalo >> 1) <= kDebandHalo, "the interleaved UV plane's column halo fits the planar kernel's LDS pitch");
+struct DebandSurfacePlaneArgs {
+    const uint8_t* src; uint8_t* dst;
+    const int8_t *dx, *dy;                     // as DebandPlaneArgs; the interleaved UV plane's: the object's interleaved table
+    long long src_stride, dst_stride;          // bytes between frames
+    int src_pitch, dst_pitch;                  // bytes between rows
+    int W, H;                                  // the plane's size in containers (the UV plane: width x height / 2)
+    int RX, RY;                                // columns and rows of halo (0..kDebandHalo)
+    int table_pitch;                           // a multiple of 16, at least W rounded up to 16
+};
+struct DebandSurfaceArgs {
+    DebandSurfacePlaneArgs plane[3];           // Y, U, V or Y, UV (plane[2] is unused then)
+    int nplanes;                               // 3, or 2: interleaved
+    int es, vec;                               // vec: deband_vec16 (lane_rule.h) on both sides' planes
+    int shift;                                 // 0, or 16 - bits of an MSB-aligned 16-bit surface
+    int thresh;                                // threshold << (bits - 8), in samples
+    int sample, blur_first;
+};
+// The grid, as deband_grid: x walks a frame's tiles, luma first, then the chroma plane's or planes'.  False where an argument or the grid
+// is out of range
+inline bool deband_surface_grid(const DebandSurfaceArgs& a, int nframes, DebandGrid& g)
+{
+    if ((a.es != 1 && a.es != 2) || a.sample < 0 || a.sample > 2 || a.thresh < 0 || nframes <= 0) return false;
+    if ((a.nplanes != 2 && a.nplanes != 3) || a.shift < 0 || a.shift > 8 || (a.shift && a.es != 2)) return false;
+    for (int p = 0; p < a.nplanes; ++p) {
+        const DebandSurfacePlaneArgs& q = a.plane[p];
+        if (!q.src || !q.dst || !q.dx || !q.dy || q.W <= 0 || q.H <= 0 || q.W > 65534 || q.H > 65534) return false;
+        if (q.RX < 0 || q.RX > kDebandHalo || q.RY < 0 || q.RY > kDebandHalo) return false;
+        if (q.src_pitch < q.W * a.es || q.dst_pitch < q.W * a.es || q.table_pitch % 16 || q.table_pitch < ((q.W + 15) & ~15)) return false;
+        if (p && (q.W != a.plane[1].W || q.H != a.plane[1].H)) return false;
+    }
+    if (a.nplanes == 2 && (a.plane[1].W & 1)) return false;
+    for (int k = 0; k < 2; ++k) {
+        g.tiles_x[k] = (a.plane[k].W + kDebandTileW - 1) / kDebandTileW;
+        g.tiles[k] = g.tiles_x[k] * ((a.plane[k].H + kDebandTileH - 1) / kDebandTileH);
+    }
+    g.grid = dim3((unsigned)(g.tiles[0] + (a.nplanes - 1) * g.tiles[1]), (unsigned)(nframes < 65535 ? nframes : 65535));
+    return true;
+}
+// One launch for all planes and frames; none when nframes <= 0.  Planar LSB planes are not this launcher's: hipErrorInvalidValue
+hipError_t launch_deband_surfaces(hipStream_t st, const DebandSurfaceArgs& a, int nframes);
+
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 // Both take a luma batch of either alignment: b.shift != 0 (16-bit containers, shift = 16 - bits) runs the same sums on container >> shift,
 // `bits` then being the depth of the shifted samples (9..15 metrics, 9..16 finder): the instantiations of stats_msb_ / logofind_msb_kernels.hip.

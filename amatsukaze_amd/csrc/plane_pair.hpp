@@ -106,7 +106,7 @@ struct PlanePairRule {
     }
 };
 
-// the chain's entry points (deband takes one layout and never asks in_kind)
+// the chain's entry points (each has a planar-LSB-only form and one that takes every pair in kind; all ask in_kind)
 inline constexpr PlanePairRule kRenderPair{"[KFMRender]", "renderer", "(no in-place rendering)", nullptr};
 inline constexpr PlanePairRule kResizePair{"[Resize]", "resizer", "(no in-place resize)", "resizer"};
 inline constexpr PlanePairRule kTemporalNRPair{"[TemporalNR]", "filter", "(no in-place filtering)", nullptr};

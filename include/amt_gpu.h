@@ -646,7 +646,7 @@ typedef struct AmtGpuRenderFrame { int32_t kind, top, bottom, ticks; } AmtGpuRen
  * *nout = the entries needed; returns 0 when cap is smaller (nothing is written then), 1 otherwise; nframes == 0 returns 1, *nout = 0 */
 int  amtgpu_kfm_render_plan(const uint8_t* cadence, const uint8_t* phase, int nframes, AmtGpuRenderFrame* out, int cap, int* nout);
 /* ---- source and destination: the one rule of the chain's entry points below -- amtgpu_kfm_render[_deint[_surfaces]], amtgpu_resize_run
- *      [_surfaces], amtgpu_temporal_nr[_surfaces], amtgpu_deband_run -- which all read frames through one AmtGpuSurfaces and write frames
+ *      [_surfaces], amtgpu_temporal_nr[_surfaces], amtgpu_deband_run[_surfaces] -- which all read frames through one AmtGpuSurfaces and write frames
  *      through another.  Each returns 0 with a message on ctx, and launches nothing, unless:
  *   - each descriptor is well formed (not NULL, bits 8..16, MSB-aligned only above 8 bits, reserved 0, no plane NULL but an interleaved
  *     V, strides and plane bases multiples of the container size);
@@ -828,7 +828,8 @@ int  amtgpu_resize_run_surfaces(AmtGpuResize* r, const AmtGpuSurfaces* src, cons
 int  amtgpu_resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int* start, int* coeff);
 
 /* ---- deband: the KDeband(25, 1, 2, true) behind KTemporalNR in the server's chain (Misc.cs:1431; the GUI's "banding reduction"
- *      checkbox, which the reference's README pairs with the temporal NR), on planar LSB planes in HBM.  Self-specified, "parity
+ *      checkbox, which the reference's README pairs with the temporal NR), on planar LSB planes (amtgpu_deband_run) or decoder surfaces
+ *      in kind (amtgpu_deband_run_surfaces) in HBM.  Self-specified, "parity
  *      unpinned" (KDeband belongs to AviSynthCUDAFilters; its source is not in the reference tree): integer and
  *      exact, so the bytes are those of the rule below wherever it runs and depend on the clip and the parameters alone.  The argument
  *      order (range, threshold, sample, blur_first) and the defaults 25, 1, 2, true are the server's call.  An addition; the ABI
@@ -857,6 +858,17 @@ int  amtgpu_resize_get_program(AmtGpuResize* r, int plane, int axis, int* K, int
  *   nframes == 0 returns 1.  Reads nothing outside the first Wp
  *   containers of a source row and writes nothing outside them in a destination row; every container of the output frames is written;
  *   the source is never written.  Synchronises, as amtgpu_resize_run does.
+ * amtgpu_deband_run_surfaces: the same call on decoder surfaces IN KIND -- NV12, interleaved 16-bit LSB, P010 / P012 / P016, planar
+ *   16-bit MSB -- where they lie; a P010 chain needs no planar copy in front of the deband and none behind it.  The rule is the rule
+ *   above, on samples.  With s = 16 - bits where the pair is MSB-aligned, else 0: a sample is container >> s, whatever the low bits
+ *   hold; thresh = threshold << (bits - 8) counts samples; in an interleaved UV row U is the even container and V the odd one, and the
+ *   two stay as independent as planes: U is filtered with plane 1's table and V with plane 2's, each with radius >> 1 and lim(x, y) of
+ *   the W/2 x H/2 component plane, and a reference of a U container is a U container.  Every container of every row is written and no
+ *   row is copied, so every destination container is result << s, its low bits zero, as in the resize.  The contract: dst >> s,
+ *   de-interleaved, is byte for byte what amtgpu_deband_run gives for src >> s, de-interleaved, for the same object.  The checks are
+ *   amtgpu_deband_run's with every layout taken, and the pair must be in kind ("the filter converts no layouts").  A planar LSB pair
+ *   launches amtgpu_deband_run's kernel and gives its bytes.  The object keeps, besides the three tables, U's and V's interleaved (U's
+ *   entry at 2x, V's at 2x + 1); amtgpu_deband_set_offsets on plane 1 or 2 rebuilds it.  An addition; the ABI version stays 5.
  * amtgpu_deband_get_offsets: plane p's table, Wp * Hp int8 each, row-major (either pointer may be NULL).
  * amtgpu_deband_set_offsets: replaces one plane's table with the caller's -- a pattern of the caller's own, or a test's planted one.
  *   Refused, the table staying as it was, if any |dx| or |dy| exceeds lim(x, y).  Synchronises */
@@ -865,6 +877,7 @@ AmtGpuDeband* amtgpu_deband_create(AmtGpuContext* ctx, int width, int height, in
                                    uint32_t seed);
 void amtgpu_deband_destroy(AmtGpuDeband* d);
 int  amtgpu_deband_run(AmtGpuDeband* d, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes);
+int  amtgpu_deband_run_surfaces(AmtGpuDeband* d, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes);
 int  amtgpu_deband_get_offsets(AmtGpuDeband* d, int plane, int8_t* dx, int8_t* dy);          /* Wp * Hp each, row-major */
 int  amtgpu_deband_set_offsets(AmtGpuDeband* d, int plane, const int8_t* dx, const int8_t* dy);
 
