@@ -1228,3 +1228,24 @@ class Debander:
             self.close()
         except Exception:
             pass
+
+
+def edge_level(ctx: Context, src: "DeviceSurfaces | DeviceClip", dst: "DeviceSurfaces | DeviceClip", strength=16, threshold=10, repair=2):
+    """Edge level of clips in HBM (amtgpu_edgelevel): the KEdgeLevel(16, 10, 2) behind KDeband in the server's chain,
+    integer and exact.  Self-specified ("parity unpinned"): the rule is this project's, its constants are the specification's own, and no
+    real footage has been judged.  Per interior luma pixel the line of five -- the column where its range exceeds the row's, else the row
+    -- is levelled towards its nearer end, e = c + (((c - (max + min >> 1)) * strength) >> 4) clamped into [min, max], unless the line is
+    flat (range <= threshold << (bits - 8)), sharp already (4 step >= 3 range) or too blurred (8 step <= 3 range); repair r > 0 then
+    clamps e between the r-th smallest and the r-th largest of the 3 x 3 around the pixel.  The two outermost rows and columns and
+    both chroma planes are copied.  Frames 0 .. src.num_frames - 1 of src go into the same frames of dst; both are planar LSB clips of
+    one size and depth and must not overlap.  The arguments' order and defaults are the server's call.  Synchronises.  Returns the
+    number of frames"""
+    n = src.num_frames
+    if n > dst.num_frames:
+        raise AmtError(f"edge_level: {n} frames, dst holds {dst.num_frames}")
+    if (int(src.width), int(src.height)) != (int(dst.width), int(dst.height)):
+        raise AmtError(f"edge_level: src is {src.width}x{src.height}, dst {dst.width}x{dst.height}")
+    s, t = _surfaces_ref(src), _surfaces_ref(dst)
+    ctx.check(ctx.lib.amtgpu_edgelevel(ctx.h, C.byref(s), C.byref(t), int(src.width), int(src.height), n, int(strength), int(threshold), int(repair)),
+              "edge_level")
+    return n

@@ -193,6 +193,7 @@ SIGNATURES = {
     "amtgpu_deband_run_surfaces": (c_i, [c_p, c_p, c_p, c_i]),
     "amtgpu_deband_get_offsets": (c_i, [c_p, c_i, c_p, c_p]),
     "amtgpu_deband_set_offsets": (c_i, [c_p, c_i, c_p, c_p]),
+    "amtgpu_edgelevel": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i]),
     "amtgpu_cm_write_chapter_exe": (c_i, [c_p, c_i, c_i, c_s]),
     "amtgpu_audiolevels_create": (c_p, [c_p, c_i, c_i, c_i, c_i, c_i64]),
     "amtgpu_audiolevels_destroy": (None, [c_p]),

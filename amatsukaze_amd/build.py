@@ -50,6 +50,8 @@ SOURCES = [
     "deband_kernels.hip",
     "deband_surface_kernels.hip",
     "deband_plan.cpp",
+    "amt_gpu_edgelevel.hip",
+    "edgelevel_kernels.hip",
     "logo_model.cpp",
     "logo_fit.cpp",
     "decisions.cpp",

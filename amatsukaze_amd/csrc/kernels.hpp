@@ -281,6 +281,39 @@ inline bool deband_surface_grid(const DebandSurfaceArgs& a, int nframes, DebandG
 // One launch for all planes and frames; none when nframes <= 0.  Planar LSB planes are not this launcher's: hipErrorInvalidValue
 hipError_t launch_deband_surfaces(hipStream_t st, const DebandSurfaceArgs& a, int nframes);
 
+// ---- edgelevel_kernels.hip ----
+// The edge level of DESIGN.md section 6g on planar LSB planes: a luma stencil of five rows by five columns, chroma copied, every frame
+// on its own.  A wave owns a strip of kEdgeStripRows output rows of one span of kEdgeSpanBytes bytes of the luma plane (a lane 16 of
+// them) and slides a window of five rows down it; a block is four such waves, or four waves that each copy one chroma row.
+constexpr int kEdgeStripRows = 32;
+constexpr int kEdgeSpanBytes = 64 * 16;
+struct EdgeLevelArgs {
+    const uint8_t *srcY, *srcU, *srcV; uint8_t *dstY, *dstU, *dstV;
+    long long src_strideY, src_strideUV, dst_strideY, dst_strideUV;  // bytes between frames
+    int src_pitchY, src_pitchUV, dst_pitchY, dst_pitchUV;            // bytes between rows
+    int W, H;                                                        // luma size in containers; both even
+    int es, vec;                                                     // vec: edgelevel_vec16 (lane_rule.h)
+    int strength, thresh, repair;                                    // 0..255; threshold << (bits - 8); 0..4
+};
+// The grid of the launcher below: x walks a frame's luma units (strip by strip, a strip's spans side by side), four to a block, then its
+// chroma rows (U's, then V's), four to a block; y the frames, a block taking every gridDim.y-th where there are more than 65 535.  False
+// where an argument or the grid is out of range
+struct EdgeLevelGrid { int spans, units, luma_blocks; dim3 grid; };
+inline bool edgelevel_grid(const EdgeLevelArgs& a, int nframes, EdgeLevelGrid& g)
+{
+    if ((a.es != 1 && a.es != 2) || a.W <= 0 || a.H <= 0 || (a.W & 1) || (a.H & 1) || nframes <= 0) return false;
+    if (a.strength < 0 || a.strength > 255 || a.thresh < 0 || a.repair < 0 || a.repair > 4) return false;
+    if (!a.srcY || !a.srcU || !a.srcV || !a.dstY || !a.dstU || !a.dstV) return false;
+    if (a.src_pitchY < a.W * a.es || a.dst_pitchY < a.W * a.es || a.src_pitchUV < a.W / 2 * a.es || a.dst_pitchUV < a.W / 2 * a.es) return false;
+    const long long spans = ((long long)a.W * a.es + kEdgeSpanBytes - 1) / kEdgeSpanBytes, strips = (a.H + kEdgeStripRows - 1) / kEdgeStripRows;
+    const long long units = spans * strips, luma_blocks = (units + 3) / 4, chroma_blocks = (a.H + 3) / 4;    // H / 2 rows of U and of V
+    if (units > 0x7FFFFFF0LL || luma_blocks + chroma_blocks > 0x7FFFFFFFLL) return false;
+    g = EdgeLevelGrid{(int)spans, (int)units, (int)luma_blocks, dim3((unsigned)(luma_blocks + chroma_blocks), (unsigned)(nframes < 65535 ? nframes : 65535))};
+    return true;
+}
+// One launch for all planes and frames; none when nframes <= 0.  The cell is edgelevel_body.h's
+hipError_t launch_edgelevel(hipStream_t st, const EdgeLevelArgs& a, int nframes);
+
 // ---- stats_kernels.hip, logofind_kernels.hip ----
 // Both take a luma batch of either alignment: b.shift != 0 (16-bit containers, shift = 16 - bits) runs the same sums on container >> shift,
 // `bits` then being the depth of the shifted samples (9..15 metrics, 9..16 finder): the instantiations of stats_msb_ / logofind_msb_kernels.hip.

@@ -112,4 +112,17 @@ inline int deband_vec16(const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& d
     return lane_divides(16, srcY.bits() | srcUV.bits() | dstY.bits() | dstUV.bits()) ? 1 : 0;
 }
 
+// edgelevel_kernel: a lane loads 16 bytes of each luma row of its window and stores 16 bytes of an output row, and a chroma row is
+// copied 16 bytes per lane, where every row of every plane of the source and of the destination starts 16-byte aligned.  `rowY` /
+// `rowUV`: the BYTES of a luma / chroma row, the same on both sides.  A row's last containers go container by container, but the two
+// containers beside a wave's span are loaded as one pair (lanes 0 and 63), which lies inside the row, and is aligned, only where the
+// luma row is a whole number of pairs; a chroma row need only be whole containers.  Otherwise everything goes container by container
+inline int edgelevel_vec16(int es, const RowsAt& srcY, const RowsAt& srcUV, const RowsAt& dstY, const RowsAt& dstUV, long long rowY, long long rowUV)
+{
+    return lane_divides(16, srcY.bits() | srcUV.bits() | dstY.bits() | dstUV.bits()) && lane_divides(2 * (uint64_t)es, (uint64_t)rowY) &&
+                   lane_divides((uint64_t)es, (uint64_t)rowUV)
+               ? 1
+               : 0;
+}
+
 } // namespace amt

@@ -1,4 +1,4 @@
-// plane_pair.hpp -- the source/destination rule of the resident post-process chain (render, resize, temporal NR, deband; include/amt_gpu.h,
+// plane_pair.hpp -- the source/destination rule of the resident post-process chain (render, resize, temporal NR, deband, edge level; include/amt_gpu.h,
 // "source and destination"): the only code between a caller's two descriptors and a kernel that writes HBM through them, so it is written
 // once, here.  An entry point calls, in this order and with its own checks in between: side() on the source and on the destination,
 // in_kind(), bytes() for either side, disjoint().  Every refusal is a std::runtime_error in the entry point's own words (PlanePairRule).
@@ -111,5 +111,7 @@ inline constexpr PlanePairRule kRenderPair{"[KFMRender]", "renderer", "(no in-pl
 inline constexpr PlanePairRule kResizePair{"[Resize]", "resizer", "(no in-place resize)", "resizer"};
 inline constexpr PlanePairRule kTemporalNRPair{"[TemporalNR]", "filter", "(no in-place filtering)", nullptr};
 inline constexpr PlanePairRule kDebandPair{"[Deband]", "filter", "(no in-place filtering: the filter reads neighbours)", "debander"};
+// (planar LSB only so far)
+inline constexpr PlanePairRule kEdgeLevelPair{"[EdgeLevel]", "filter", "(no in-place filtering: the filter reads neighbours)", nullptr};
 
 } // namespace amt

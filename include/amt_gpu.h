@@ -646,7 +646,7 @@ typedef struct AmtGpuRenderFrame { int32_t kind, top, bottom, ticks; } AmtGpuRen
  * *nout = the entries needed; returns 0 when cap is smaller (nothing is written then), 1 otherwise; nframes == 0 returns 1, *nout = 0 */
 int  amtgpu_kfm_render_plan(const uint8_t* cadence, const uint8_t* phase, int nframes, AmtGpuRenderFrame* out, int cap, int* nout);
 /* ---- source and destination: the one rule of the chain's entry points below -- amtgpu_kfm_render[_deint[_surfaces]], amtgpu_resize_run
- *      [_surfaces], amtgpu_temporal_nr[_surfaces], amtgpu_deband_run[_surfaces] -- which all read frames through one AmtGpuSurfaces and write frames
+ *      [_surfaces], amtgpu_temporal_nr[_surfaces], amtgpu_deband_run[_surfaces], amtgpu_edgelevel -- which all read frames through one AmtGpuSurfaces and write frames
  *      through another.  Each returns 0 with a message on ctx, and launches nothing, unless:
  *   - each descriptor is well formed (not NULL, bits 8..16, MSB-aligned only above 8 bits, reserved 0, no plane NULL but an interleaved
  *     V, strides and plane bases multiples of the container size);
@@ -880,6 +880,42 @@ int  amtgpu_deband_run(AmtGpuDeband* d, const AmtGpuSurfaces* src, const AmtGpuS
 int  amtgpu_deband_run_surfaces(AmtGpuDeband* d, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int nframes);
 int  amtgpu_deband_get_offsets(AmtGpuDeband* d, int plane, int8_t* dx, int8_t* dy);          /* Wp * Hp each, row-major */
 int  amtgpu_deband_set_offsets(AmtGpuDeband* d, int plane, const int8_t* dx, const int8_t* dy);
+
+/* ---- edge level: the KEdgeLevel(16, 10, 2) behind KDeband in the server's chain (Misc.cs:1435; the GUI's "edge enhancement (for
+ *      anime)" checkbox), on planar LSB planes in HBM.  Self-specified, "parity unpinned" (KEdgeLevel belongs to AviSynthCUDAFilters; its
+ *      source is not in the reference tree; the reference's README describes it as a port of AviUtl's edge-level filter that leaves out
+ *      edges that are already sharp and areas that are too blurred and applies its result through a step like RgTools' Repair; DESIGN.md
+ *      section 6g): integer and exact, so the bytes are those of the rule below wherever it runs and depend on the clip and the
+ *      parameters alone.  The rule is this project's; its constants are the specification's own, and no real footage has been judged.
+ *      The argument order (str, thrs, repair) and the defaults 16, 10, 2 are the server's call.  An addition; the ABI version stays 5. ----
+ * - Input is planar LSB planes of 8..16 bits, 4:2:0, `width` and `height` even and positive.
+ * - Frames are independent: there is no halo in time, and a clip cut into calls gives the bytes of one call.
+ * - Chroma is copied.  Every container of U and V goes to the destination as stored.  AviUtl's filter is luma only, and KEdgeLevel's
+ *   call passes no chroma argument.
+ * - Containers are taken as stored, with no masking to `bits`, as in the temporal NR and the deband.
+ * Parameters, in the server's order (str, thrs, repair): strength 0..255; threshold 0..32767, with T = threshold << (bits - 8);
+ * repair 0..4.  For the luma sample c = s[y][x]:
+ * 1. Border.  Where x < 2, x >= W - 2, y < 2 or y >= H - 2: out = c.  No reference ever lies outside the plane, so there is no edge
+ *    rule.  A plane narrower or lower than 5 is copied.
+ * 2. Direction.  H5 = s[y][x-2 .. x+2], V5 = s[y-2 .. y+2][x].  rh = max(H5) - min(H5), rv = max(V5) - min(V5).  The line L is V5
+ *    where rh < rv, else H5.  A tie takes the horizontal line.  mx = max(L), mn = min(L), rng = mx - mn.
+ * 3. Flat.  rng <= T: out = c.
+ * 4. Step.  step = max |L[i+1] - L[i]|, i = 0..3.  Sharp already: 4 * step >= 3 * rng: out = c.  Too blurred: 8 * step <= 3 * rng:
+ *    out = c.  A linear ramp has 4 * step = rng.
+ * 5. Level.  avg = (mx + mn) >> 1.  e = c + (((c - avg) * strength) >> 4), the shift arithmetic (floor).  e is clamped into [mn, mx].
+ *    |c - avg| <= 32768 and strength <= 255, so the product is below 2^23 in magnitude: a signed 24-bit multiply holds it.
+ * 6. Repair.  With repair = r > 0: sort the nine source samples s[y-1..y+1][x-1..x+1] ascending as n[0..8].
+ *    out = min(max(e, n[r - 1]), n[9 - r]).  These are RgTools' Repair modes 1..4, the source as its own reference.  With r = 0:
+ *    out = e.  Repair is applied only where step 5 was reached.  It can move a pixel that step 5 left at c.
+ * amtgpu_edgelevel: frames 0 .. nframes - 1 of src into frames 0 .. nframes - 1 of dst, in one launch for all three planes.  Stateless,
+ *   like amtgpu_temporal_nr: there is no table, so no object.  Returns 0 with a message on ctx, and launches nothing: strength,
+ *   threshold or repair out of range; a negative frame count; an odd or non-positive size; what the source and destination rule above
+ *   refuses (planar LSB only: decoder surfaces in kind are not built; bits that differ between the sides; nframes frames on either
+ *   side) -- in-place is impossible here, the filter reads neighbours.  nframes == 0 returns 1.  Reads nothing outside the first
+ *   `width` (`width / 2`) containers of a source row and writes nothing outside them in a destination row; every container of the
+ *   output frames is written; the source is never written.  Synchronises: dst is complete when the call returns */
+int  amtgpu_edgelevel(AmtGpuContext* ctx, const AmtGpuSurfaces* src, const AmtGpuSurfaces* dst, int width, int height, int nframes, int strength,
+                      int threshold, int repair);
 
 /* chapter_exe output contract (CMAnalyze::readSceneChanges, CMAnalyze.hpp:411-439): header, a "----" line, "SCPos: <frame>"
  * lines.  This call writes no "mute" lines: amtgpu_cm_write_chapter_exe_mute below writes the file with them */
