@@ -23,6 +23,7 @@ SOURCES = [
     "eval_linear_kernels.hip",
     "eval_pair_kernels.hip",
     "eval_pair1_kernels.hip",
+    "eval_pair1_duo_kernels.hip",
     "erase_scan_kernels.hip",
     "erase_surface_kernels.hip",
     "stats_kernels.hip",

@@ -213,6 +213,7 @@ private:
     bool tiles_stage4_ = false;                    // the taps carry the 0.25; otherwise the pair kernel's ldexp form runs on plain taps
     std::vector<DevBuf<float2>> d_tkp_, d_tsc_, d_tpq_;
     bool tiles_units_ = false;                     // the scan's plans are single-pass ones and its pair kernel the one-unit form (ensure_tiles)
+    PairShape pair_shape_{kTileWaves, kTileMaxFrames, false};   // ... in which of its two shapes (eval_tiles.hpp tile_pair_shape; ensure_tiles)
     std::vector<DevBuf<uint32_t>> d_tinfo_, d_tpos_, d_tunits_;
     std::vector<DevBuf<char>> d_tlin_;
     int lin_queue_ = 256;

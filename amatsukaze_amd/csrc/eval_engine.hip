@@ -200,12 +200,14 @@ void EvalEngine::run(const FrameBatch& luma, int bits, int nframes, float* dout,
         // fades {0, 1}: the window of s and the window of bg are the two blends themselves
         const size_t dot = prof_name_.find('.');
         const std::string suffix = dot == std::string::npos ? std::string() : prof_name_.substr(dot);
-        const int Gp = group_frames_ > 0 ? group_frames_ : (int)std::max(1LL, std::min((long long)kTileMaxFrames, (long long)nframes * nl / 2048));
+        const bool duo = pair_shape_.duo;     // (ensure_tiles; then tiles_units_ is set)
+        const int Gw = group_frames_ > 0 ? group_frames_ : (int)std::max(1LL, std::min((long long)kTileMaxFrames, (long long)nframes * nl / 2048));
+        const int Gp = duo ? std::min(Gw, pair_shape_.frames) : Gw;    // (two workgroups' LDS share a CU up to kPairDuoFrames)
         // (tables that carry DeintY's 0.25 -- every engine, in practice -- or the kernel's ldexp form on unscaled ones: ensure_tiles)
         // (single-pass plans for every logo -- the bench's and most drawn logos -- run the one-unit form: ensure_tiles)
         // (the profile names the pass, whichever of its two staging forms runs: bench.py and tools read it by this name)
         const int sp = ctx_->prof_begin(((tiles_stage4_ ? "logo_eval_pair_kernel" : "logo_eval_pair_ldexp_kernel") + suffix).c_str());
-        AMT_HIP((tiles_units_ ? launch_logo_eval_pair1 : launch_logo_eval_pair)(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, luma, dframe_map, nframes, Gp, dout, out_frame_stride_,
+        AMT_HIP((duo ? launch_logo_eval_pair1_duo : tiles_units_ ? launch_logo_eval_pair1 : launch_logo_eval_pair)(ctx_->stream, bits, d_logos_.get(), d_tls_.get(), nl, luma, dframe_map, nframes, Gp, dout, out_frame_stride_,
                                       take_abs_ ? 1 : 0, tiles_stage4_ ? 0 : 1));
         ctx_->prof_end(sp);
         return;
@@ -330,7 +332,17 @@ void EvalEngine::ensure_tiles()
         for (int i = 0; i < nl; ++i)
             single[i] = build_tile_plan(specs_[i].tables.pos, specs_[i].tables.count, specs_[i].planes.w, specs_[i].planes.h, kTileCutUnits);
         tiles_units_ = tile_plans_single_pass(plans, single);
-        if (tiles_units_) plans.swap(single);
+        // ... and the one-unit form in a second shape, 7 + 1 waves and two workgroups per CU, on plans of seven tiles per band: taken
+        // when no logo's plan is modelled dearer for it and a workgroup's LDS fits this device (tile_pair_shape)
+        std::vector<TilePlan> duo(nl);
+        for (int i = 0; i < nl; ++i)
+            duo[i] = build_tile_plan(specs_[i].tables.pos, specs_[i].tables.count, specs_[i].planes.w, specs_[i].planes.h, kTileCutUnits, kPairDuoWaves);
+        int dev = 0, lds_limit = 0;
+        AMT_HIP(hipGetDevice(&dev));
+        AMT_HIP(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        pair_shape_ = tile_pair_shape(plans, single, duo, (size_t)std::max(0, lds_limit), kEvalScorePad);
+        if (pair_shape_.duo) { tiles_units_ = true; plans.swap(duo); }
+        else if (tiles_units_) plans.swap(single);
     }
     d_tunits_.resize(nl);
     d_tkp_.resize(nl); d_tsc_.resize(nl); d_tpq_.resize(nl); d_tinfo_.resize(nl); d_tpos_.resize(nl); d_tlin_.resize(nl); d_tiles_.resize(nl); d_tbands_.resize(nl); d_tlist_.resize(nl);

@@ -20,8 +20,9 @@ namespace amt {
 using namespace lin;
 using namespace tile;
 
-constexpr int kPairThreads = (kTileWaves + 1) * 64;              // the evaluation waves + the summing wave
-constexpr int kPairRowPitch = kTileBandPix + kEvalScorePad;      // floats; the sum reads ahead of the row's end
+constexpr int pair_threads(int nw) { return (nw + 1) * 64; }                          // the evaluation waves + the summing wave
+constexpr int pair_row_pitch(int nw) { return nw * kTileLanes + kEvalScorePad; }      // floats; the sum reads ahead of the row's end
+constexpr int kPairThreads = pair_threads(kTileWaves);
 
 // {corr(k, s), corr(k, bg)} around the window means M = window_means(W) in the reference's order (exact_math.h corr5x5_strided),
 // both halves at once
@@ -79,12 +80,16 @@ struct PairLaunch {
 // depend on, so it is fetched a band ahead, at a band's end where the next band's pixel and taps are requested, and made a plain
 // value there (the terms' flush has just waited for everything older, the word is the first load behind it): the loop carries a
 // register, no load crosses the back edge, and no wait stands between the next tile's coefficient loads and its raw request.
-template <typename pix_t, bool STAGE4, bool ONE_UNIT = false>
+//
+// NW: the evaluation waves of the instance = the tiles per band of the plans it walks (TilePlan::waves; the shapes: eval_tiles.hpp
+// tile_pair_shape)
+template <typename pix_t, bool STAGE4, bool ONE_UNIT = false, int NW = kTileWaves>
 __device__ __forceinline__ void logo_eval_pair_body(const PairLaunch& A)
 {
+    constexpr int kPairRowPitch = pair_row_pitch(NW);
     extern __shared__ float lds[];
-    f2* const planes = reinterpret_cast<f2*>(lds);                       // [kTileWaves][kTileCap] {s, bg}: a wave's own tile
-    float* const rows = lds + kTileWaves * kTileCap * 2;                 // [2][2 G][kPairRowPitch] per-pixel terms of a band
+    f2* const planes = reinterpret_cast<f2*>(lds);                       // [NW][kTileCap] {s, bg}: a wave's own tile
+    float* const rows = lds + NW * kTileCap * 2;                         // [2][2 G][kPairRowPitch] per-pixel terms of a band
 
     const int G = A.G;
     const WgMap wm = wg_map_shared_rows((int)blockIdx.x, A.nlogos, A.ngroups);
@@ -98,7 +103,7 @@ __device__ __forceinline__ void logo_eval_pair_body(const PairLaunch& A)
     const TileLogoDev* const Xp = A.tls + logo;
     const int nbands = Xp->nbands;
 
-    if (wave == kTileWaves) {
+    if (wave == NW) {
         // ---------------- the summing wave: after the barrier that ends band b it adds band b's rows ----------------
         // Its chain of dependent adds is short on instructions but long on latency: with the issue priority raised it gets its
         // slot as soon as an add's operand is ready instead of queueing behind the SIMD's evaluation waves for every element
@@ -147,7 +152,7 @@ __device__ __forceinline__ void logo_eval_pair_body(const PairLaunch& A)
     //  compiler places at the loop head for them is the merge of this path and the back edge -- with the raw loads sunk below the 14
     //  pixel / tap loads it became vmcnt(0) in every iteration, which also waits for the scale gathers issued just before)
     asm volatile("" ::: "memory");
-    if constexpr (ONE_UNIT) unext = gld<unsigned>(gUnits, ((unsigned)((nbands > 1 ? kTileWaves : 0) + wave) * 64u + (unsigned)lane) * 4u);
+    if constexpr (ONE_UNIT) unext = gld<unsigned>(gUnits, ((unsigned)((nbands > 1 ? NW : 0) + wave) * 64u + (unsigned)lane) * 4u);
     px.load(gK, gInfo, nslots8, (unsigned)wave * 64u + (unsigned)lane, T, plane_base);
     if constexpr (ONE_UNIT) asm volatile("" : "+v"(unext));
     st.coefs_landed();
@@ -172,7 +177,7 @@ __device__ __forceinline__ void logo_eval_pair_body(const PairLaunch& A)
         st.convert();
         // ---- 2. the next iteration's raw samples travel during the evaluation (past the last iteration: a repeat nobody reads) ----
         if (band_end && b + 1 < nbands) {
-            fetch_tile(T, tiles + (b + 1) * kTileWaves);
+            fetch_tile(T, tiles + (b + 1) * NW);
             if constexpr (ONE_UNIT) st.setup_units(T, unext);
             else st.setup_units(T, lane);
         }
@@ -203,8 +208,8 @@ __device__ __forceinline__ void logo_eval_pair_body(const PairLaunch& A)
             ++b; g = 0;
             if (b < nbands) {
                 st.coefs_landed();
-                if constexpr (ONE_UNIT) unext = gld<unsigned>(gUnits, ((unsigned)((b + 1 < nbands ? b + 1 : b) * kTileWaves + wave) * 64u + (unsigned)lane) * 4u);
-                px.load(gK, gInfo, nslots8, (unsigned)(b * kTileWaves + wave) * 64u + (unsigned)lane, T, plane_base);
+                if constexpr (ONE_UNIT) unext = gld<unsigned>(gUnits, ((unsigned)((b + 1 < nbands ? b + 1 : b) * NW + wave) * 64u + (unsigned)lane) * 4u);
+                px.load(gK, gInfo, nslots8, (unsigned)(b * NW + wave) * 64u + (unsigned)lane, T, plane_base);
                 if constexpr (ONE_UNIT) asm volatile("" : "+v"(unext));
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -216,7 +221,8 @@ __device__ __forceinline__ void logo_eval_pair_body(const PairLaunch& A)
 
 // the launch arguments both forms share; hipSuccess with *grid == 0: nothing to launch
 inline hipError_t pair_launch_args(PairLaunch& A, size_t* lds, unsigned* grid, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
-                                   const FrameBatch& luma, const int* dframe_map, int nframes, int G, float* dout, int out_frame_stride, int take_abs)
+                                   const FrameBatch& luma, const int* dframe_map, int nframes, int G, float* dout, int out_frame_stride, int take_abs,
+                                   int nw = kTileWaves)
 {
     *grid = 0; *lds = 0;
     if (nframes <= 0 || nlogos <= 0) return hipSuccess;
@@ -225,7 +231,7 @@ inline hipError_t pair_launch_args(PairLaunch& A, size_t* lds, unsigned* grid, i
     A.maxv = (float)((1 << bits) - 1);
     A.nframes = nframes; A.G = G; A.ngroups = (nframes + G - 1) / G; A.nlogos = nlogos;
     A.out = dout; A.out_frame_stride = out_frame_stride; A.take_abs = take_abs;
-    *lds = ((size_t)kTileWaves * kTileCap * 2 + (size_t)2 * 2 * G * kPairRowPitch) * sizeof(float);
+    *lds = tile_pair_lds_bytes(nw, G, kEvalScorePad);
     if (G < 1 || 2 * G > 64 || *lds > 160 * 1024) return hipErrorInvalidValue;
     *grid = (unsigned)wg_grid_shared_rows(A.ngroups, nlogos);
     return hipSuccess;

@@ -125,10 +125,12 @@ inline uint32_t tile_slot_info(int woff, int ridx, bool valid) { return (uint32_
 
 struct TilePlan {
     std::vector<TileBandDesc> bands;
-    std::vector<TileDesc> tiles;          // bands.size() * kTileWaves
+    int waves = kTileWaves;               // tiles per band: slot = (band * waves + wave) * 64 + lane
+    std::vector<TileDesc> tiles;          // bands.size() * waves
     std::vector<uint32_t> sinfo;          // per slot: window offset in the tile (pairs, bits 0-11), index in the band's score row (bits 12-23), valid (bit 31)
     std::vector<int> slot_pixel;          // per slot: mask pixel m, -1 for an idle lane
     long long model_cost = 0;             // modelled critical path: per band the busiest SIMD's sum of its tiles' 131 + 31 * passes
+    long long work_cost = 0;              // the same costs added over every tile: the vector work of a frame, wherever it runs
     int nslots() const { return (int)sinfo.size(); }
     // kTileCutUnits only: per tile the units some window of a valid slot reads, in raster order -- kTileLanes words (tile_unit_word)
     // per tile, entries from nunits[tile] on repeat the last needed unit (a tile without pixels: unit 0 throughout, nunits 0)
@@ -249,19 +251,20 @@ inline std::vector<std::vector<Px>> deal_band(const std::vector<uint32_t>& pos, 
     return groups;
 }
 // pixels per band
-inline std::vector<int> cut_bands(const std::vector<uint32_t>& pos, int count, bool fine, bool units = false)
+inline std::vector<int> cut_bands(const std::vector<uint32_t>& pos, int count, bool fine, bool units = false, int nw = kTileWaves)
 {
     std::vector<int> cuts;
+    const int band_pix = nw * kTileLanes;
     for (int m = 0; m < count;) {
-        int n = std::min(kTileBandPix, count - m);
-        while ((int)deal_band(pos, m, n, units).size() > kTileWaves)          // sparse stretch: a shorter band
+        int n = std::min(band_pix, count - m);
+        while ((int)deal_band(pos, m, n, units).size() > nw)          // sparse stretch: a shorter band
             n = fine ? std::max(1, n - 4) : std::max(1, n - std::max(1, n / 8));
         cuts.push_back(n);
         m += n;
     }
     if (fine && cuts.size() >= 2 && cuts.back() < kTileLanes) {
         const int n = cuts[cuts.size() - 2] + cuts.back();
-        if (n <= kTileBandPix && (int)deal_band(pos, count - n, n, units).size() <= kTileWaves) { cuts.pop_back(); cuts.back() = n; }
+        if (n <= band_pix && (int)deal_band(pos, count - n, n, units).size() <= nw) { cuts.pop_back(); cuts.back() = n; }
     }
     return cuts;
 }
@@ -269,20 +272,24 @@ inline std::vector<int> cut_bands(const std::vector<uint32_t>& pos, int count, b
 } // namespace tiles_detail
 
 // pos[m] = (y << 16) | x of mask pixel m in raster order (MaskTables::pos); every pixel has 2 <= x < w-2, 2 <= y < h-2, w >= 5
-inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int w, int h, TileCut cut = kTileCutCoarse)
+// nw: tiles per band = evaluation waves of the kernel instance that walks the plan (the slot strides follow it)
+inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int w, int h, TileCut cut = kTileCutCoarse, int nw = kTileWaves)
 {
     using namespace tiles_detail;
     (void)h;
     if (w < 5) throw std::runtime_error("logo too narrow for the tile kernel");
     if (cut == kTileCutBest) {
-        TilePlan coarse = build_tile_plan(pos, count, w, h, kTileCutCoarse), fine = build_tile_plan(pos, count, w, h, kTileCutFine);
+        TilePlan coarse = build_tile_plan(pos, count, w, h, kTileCutCoarse, nw), fine = build_tile_plan(pos, count, w, h, kTileCutFine, nw);
         return fine.model_cost < coarse.model_cost ? fine : coarse;
     }
     TilePlan P;
     const bool units = cut == kTileCutUnits;
     P.single_pass = units;
+    P.waves = nw;
+    if (nw < 1 || nw > 15) throw std::runtime_error("tile plan: waves per band");
+    const int band_pix = nw * kTileLanes;
     int m = 0;
-    for (const int n : cut_bands(pos, count, cut == kTileCutFine || units, units)) {
+    for (const int n : cut_bands(pos, count, cut == kTileCutFine || units, units, nw)) {
         std::vector<std::vector<Px>> groups = deal_band(pos, m, n, units);
         // Which wave takes which tile is free.  Waves are dealt to the CU's four SIMDs round-robin (wave w on SIMD w % 4: with eleven
         // evaluation waves three each on SIMDs 0-2, two and the summing wave on SIMD 3), a SIMD issues for one wave at a time, and a
@@ -294,26 +301,27 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
             auto cost = [&](size_t i) { const Geometry G = bbox(groups[i], 0, groups[i].size()); return 131 + 31 * (!units && G.nrows * G.ncol4 > kTileLanes ? 2 : 1); };   // (units: at most kTileLanes NEEDED units, by deal_band's rule)
             std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return cost(a) > cost(b); });
             int load[4] = {0, 0, 0, 0}, used[4] = {0, 0, 0, 0}, cap[4] = {0, 0, 0, 0};
-            for (int w = 0; w < kTileWaves; ++w) ++cap[w % 4];
-            std::vector<std::vector<Px>> placed(kTileWaves);
+            for (int w = 0; w < nw; ++w) ++cap[w % 4];
+            std::vector<std::vector<Px>> placed(nw);
             for (size_t i : order) {
                 int best = -1;
                 for (int k = 0; k < 4; ++k)
                     if (used[k] < cap[k] && (best < 0 || load[k] < load[best])) best = k;
                 placed[best + 4 * used[best]] = groups[i];
                 load[best] += cost(i); ++used[best];
+                P.work_cost += cost(i);
             }
             P.model_cost += *std::max_element(load, load + 4);
             groups.swap(placed);                                  // (a wave without a tile keeps an empty group: npix 0, it idles through the band)
         }
         const int band = (int)P.bands.size();
         P.bands.push_back(TileBandDesc{m, n});
-        P.tiles.resize((size_t)(band + 1) * kTileWaves, TileDesc{0, 0, 0, 1, 4, 0, 65536, 0});
-        P.sinfo.resize((size_t)(band + 1) * kTileBandPix, tile_slot_info(0, 0, false));
-        P.slot_pixel.resize((size_t)(band + 1) * kTileBandPix, -1);
+        P.tiles.resize((size_t)(band + 1) * nw, TileDesc{0, 0, 0, 1, 4, 0, 65536, 0});
+        P.sinfo.resize((size_t)(band + 1) * band_pix, tile_slot_info(0, 0, false));
+        P.slot_pixel.resize((size_t)(band + 1) * band_pix, -1);
         if (units) {
-            P.units.resize((size_t)(band + 1) * kTileBandPix, tile_unit_word(0, 0));
-            P.nunits.resize((size_t)(band + 1) * kTileWaves, 0);
+            P.units.resize((size_t)(band + 1) * band_pix, tile_unit_word(0, 0));
+            P.nunits.resize((size_t)(band + 1) * nw, 0);
         }
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             const std::vector<Px>& g = groups[gi];
@@ -327,7 +335,7 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
             }
             std::vector<uint8_t> half;
             split_lanes(g, G.x0, G.y0, best_tp, &half);
-            TileDesc& T = P.tiles[(size_t)band * kTileWaves + gi];
+            TileDesc& T = P.tiles[(size_t)band * nw + gi];
             T.x0 = G.x0; T.y0 = G.y0; T.nrows = G.nrows; T.ncol4 = G.ncol4; T.tp = best_tp; T.npix = (int)g.size();
             T.rcp = (65536 + G.ncol4 - 1) / G.ncol4;
             for (int u = 0; u < kTileLanes * kTileUnits; ++u)
@@ -337,7 +345,7 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
             int next[2] = {0, kTileLanes / 2}, filler[2] = {-1, -1};
             for (size_t i = 0; i < g.size(); ++i) {
                 const int l = next[half[i]]++;
-                const size_t slot = ((size_t)band * kTileWaves + gi) * kTileLanes + l;
+                const size_t slot = ((size_t)band * nw + gi) * kTileLanes + l;
                 const int woff = (g[i].y - 2 - G.y0) * best_tp + (g[i].x - 2 - G.x0);
                 if (l >= kTileLanes / 2 * (half[i] + 1)) throw std::runtime_error("tile plan: more than 32 pixels in half a wave");
                 if (woff < 0 || woff + 4 * best_tp + 4 > G.nrows * best_tp - 1 || G.nrows * best_tp > kTileCap) throw std::runtime_error("tile plan: window outside its tile");
@@ -348,7 +356,7 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
             for (int hf = 0; hf < 2; ++hf) {
                 const int woff = filler[hf] >= 0 ? filler[hf] : filler[1 - hf];
                 for (int l = next[hf]; l < kTileLanes / 2 * (hf + 1); ++l)
-                    P.sinfo[((size_t)band * kTileWaves + gi) * kTileLanes + l] = tile_slot_info(woff, 0, false);
+                    P.sinfo[((size_t)band * nw + gi) * kTileLanes + l] = tile_slot_info(woff, 0, false);
             }
             if (units) {
                 // (lanes without a pixel read a valid pixel's window: they need no unit of their own)
@@ -357,7 +365,7 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
                 if (keys.empty() || keys.size() > (size_t)kTileLanes) throw std::runtime_error("tile plan: needed units");
                 for (uint32_t& k : keys) k = tile_unit_word((int)(k >> 8) - G.y0, (int)(k & 0xFFu));     // row-major: sorts in raster order
                 std::sort(keys.begin(), keys.end());
-                const size_t tile = (size_t)band * kTileWaves + gi;
+                const size_t tile = (size_t)band * nw + gi;
                 P.nunits[tile] = (int)keys.size();
                 for (int l = 0; l < kTileLanes; ++l) P.units[tile * kTileLanes + l] = keys[std::min((size_t)l, keys.size() - 1)];
             }
@@ -369,12 +377,48 @@ inline TilePlan build_tile_plan(const std::vector<uint32_t>& pos, int count, int
 
 // The scan engine's choice between its logos' best two-unit plans and their single-pass plans: one kernel per launch, so the single-pass
 // form runs when EVERY logo has a single-pass plan whose modelled cost is not above that of its best existing plan.
-inline bool tile_plans_single_pass(const std::vector<TilePlan>& best, const std::vector<TilePlan>& units)
+inline bool tile_plans_single_pass(const std::vector<TilePlan>& best, const std::vector<TilePlan>& units, int nw = kTileWaves)
 {
     if (best.empty() || best.size() != units.size()) return false;
     for (size_t i = 0; i < best.size(); ++i)
-        if (!units[i].single_pass || units[i].model_cost > best[i].model_cost || !tile_slots_ok(units[i].nslots())) return false;
+        if (!units[i].single_pass || units[i].waves != nw || best[i].waves != nw || units[i].model_cost > best[i].model_cost || !tile_slots_ok(units[i].nslots())) return false;
     return true;
+}
+
+// LDS of one workgroup of the scan's pair kernel: a tile plane per evaluation wave, and two sets (double buffer) of 2 G score rows of a
+// band's pixels plus the read-ahead of the sum (row_pad floats: kEvalScorePad)
+inline size_t tile_pair_lds_bytes(int nw, int G, int row_pad)
+{
+    return ((size_t)nw * kTileCap * 2 + (size_t)2 * 2 * G * (nw * kTileLanes + row_pad)) * sizeof(float);
+}
+
+// The one-unit scan kernel's second shape: 7 evaluation waves + the summing wave and at most 6 frames per workgroup, compiled for four
+// waves per SIMD, so that TWO workgroups share a CU (2 x 75 136 B of LDS, 2 x 8 waves).  While the last waves of one workgroup run into
+// a band's barrier the other workgroup's waves take the SIMDs' issue slots, which the 11 + 1 shape leaves idle for a fifth of its waves'
+// cycles (profiles/pair_waves_notes.md: 2.36 against 2.50 ms per 10 000 frames).
+constexpr int kPairDuoWaves = 7;
+constexpr int kPairDuoFrames = 6;
+struct PairShape { int waves, frames; bool duo; };   // evaluation waves = tiles per band; most frames per workgroup; the second shape's kernels
+                                                      // (said outright: in a fenced variant build kTileWaves may equal kPairDuoWaves)
+
+// Which shape an engine's scan runs -- a pure function of the logos' plans and the device's LDS per workgroup, so that a host program
+// can replay it (tests/cpp/pair_shape_replay.cpp).  best / units: every logo's kTileCutBest and kTileCutUnits plan at kTileWaves, what
+// tile_plans_single_pass chooses between; duo: its kTileCutUnits plan at kPairDuoWaves.  The duo shape is taken when every logo's
+// duo plan is modelled no dearer than the cheapest of its plans at kTileWaves, and a workgroup's LDS fits.  The model of the duo
+// shape: its two resident workgroups are at different places of their bands, so a SIMD is not idle while one of them waits at a barrier
+// and what counts is the frame's vector work spread over the CU's four SIMDs (work_cost / 4), not the busiest SIMD of every band.
+// Otherwise {kTileWaves, kTileMaxFrames}: the engine runs what tile_plans_single_pass says.
+inline PairShape tile_pair_shape(const std::vector<TilePlan>& best, const std::vector<TilePlan>& units, const std::vector<TilePlan>& duo,
+                                 size_t lds_per_workgroup, int row_pad)
+{
+    const PairShape keep{kTileWaves, kTileMaxFrames, false};
+    if (best.empty() || best.size() != units.size() || best.size() != duo.size()) return keep;
+    if (tile_pair_lds_bytes(kPairDuoWaves, kPairDuoFrames, row_pad) > lds_per_workgroup) return keep;
+    for (size_t i = 0; i < best.size(); ++i) {
+        const long long existing = units[i].single_pass ? std::min(best[i].model_cost, units[i].model_cost) : best[i].model_cost;
+        if (!duo[i].single_pass || duo[i].waves != kPairDuoWaves || !tile_slots_ok(duo[i].nslots()) || (duo[i].work_cost + 3) / 4 > existing) return keep;
+    }
+    return PairShape{kPairDuoWaves, kPairDuoFrames, true};
 }
 
 } // namespace amt

@@ -378,6 +378,10 @@ hipError_t launch_logo_eval_pair(hipStream_t st, int bits, const EvalLogoDev* dl
 hipError_t launch_logo_eval_pair1(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
                                   const FrameBatch& luma, const int* dframe_map, int nframes, int G, float* dout, int out_frame_stride, int take_abs,
                                   int ldexp_form);
+// eval_pair1_duo_kernels.hip: the same on single-pass plans of kPairDuoWaves tiles per band (eval_tiles.hpp tile_pair_shape), G <= kPairDuoFrames
+hipError_t launch_logo_eval_pair1_duo(hipStream_t st, int bits, const EvalLogoDev* dlogos, const TileLogoDev* dtls, int nlogos,
+                                      const FrameBatch& luma, const int* dframe_map, int nframes, int G, float* dout, int out_frame_stride, int take_abs,
+                                      int ldexp_form);
 // Sentinel monitor of AMTGPU_ANALYZE_LINEAR_MONITORED: persistent per-analyzer device state.  max_abs_bits: the largest |linear - exact| over
 // every compared score as float bits (non-negative floats order like unsigned ints; NaN counts as +inf); tripped: a comparison failed (sticky
 // until re-armed); frames_checked: sentinel frames compared; batches_tripped: batches in which a comparison failed

@@ -5,9 +5,13 @@ box: python tools/tile_bench.py"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+# the pair kernel's shapes at four waves per SIMD (profiles/pair_waves_notes.md); AMT_TILE_WAVES is shared with the linear kernel's plans, so a
+# variant's linear figure says nothing
 VARIANTS = {
+    "w15_g6_occ4": ["AMT_PAIR_OCC=4", "AMT_TILE_WAVES=15", "AMT_TILE_G=6"],
     "w15_g5_occ4": ["AMT_PAIR_OCC=4", "AMT_TILE_WAVES=15", "AMT_TILE_G=5"],
-    "w7_g6_occ4": ["AMT_PAIR_OCC=4", "AMT_TILE_WAVES=7", "AMT_TILE_G=6"],
+    "w7_g6_occ4": ["AMT_PAIR_OCC=4", "AMT_TILE_WAVES=7", "AMT_TILE_G=6"],  # two workgroups per CU
+    "w7_g5_occ4": ["AMT_PAIR_OCC=4", "AMT_TILE_WAVES=7", "AMT_TILE_G=5"],
     "w7_g8": ["AMT_TILE_WAVES=7", "AMT_TILE_G=8"],
     # the 16-bit linear kernel runs two workgroups per CU: room for more frames per workgroup
     "lin16_g8": ["AMT_LIN_G16=8"], "lin16_g8_1k": ["AMT_LIN_G16=8", "AMT_LIN_WGS_MIN16=1024"],
@@ -16,8 +20,8 @@ VARIANTS = {
     # listed re-evaluation of the linear mode's guard: fades per workgroup (0 = all eleven in one workgroup)
     "listed0": ["AMT_LISTED_FADE_CHUNK=0"], "listed2": ["AMT_LISTED_FADE_CHUNK=2"], "listed4": ["AMT_LISTED_FADE_CHUNK=4"],
 }
-ONLY = [a for a in sys.argv[1:] if not a.startswith("--")]
-if ONLY:
+ONLY = [a for a in sys.argv[1:] if a in VARIANTS]
+if ONLY or "--lib" in sys.argv:
     VARIANTS = {k: v for k, v in VARIANTS.items() if k in ONLY}
 if "--build" in sys.argv:
     from amatsukaze_amd import build as B
@@ -51,18 +55,35 @@ if "--child" in sys.argv:
         out[tag] = r
         del Y
     print(json.dumps(out)); sys.exit(0)
-res = {}
-names = ["default"] + list(VARIANTS)
-for name in names:
+# --lib NAME (repeatable): amatsukaze_amd/libamt_gpu_tile_NAME.so built elsewhere, e.g. the parent commit's library beside this one's
+names = ["default"] + list(VARIANTS) + [sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a == "--lib"]
+
+
+def child(name):
     env = dict(os.environ)
     if name != "default":
         so = os.path.join(ROOT, "amatsukaze_amd", f"libamt_gpu_tile_{name}.so")
         if not os.path.exists(so):
-            continue
+            return None
         env["AMTGPU_LIB"] = so
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True, timeout=600)
-    try:
-        res[name] = json.loads(r.stdout.strip().splitlines()[-1])
-    except Exception:
-        res[name] = {"error": (r.stderr or r.stdout)[-400:]}
-    print(name, json.dumps(res[name]), flush=True)
+    # (a child that runs out of time raises: the job ends there)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True, timeout=300)
+    if r.returncode != 0:
+        print(name, json.dumps({"error": (r.stderr or r.stdout)[-400:], "returncode": r.returncode}), flush=True)
+        sys.exit(1)  # a fault or an abort: start nothing more on the device
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+# --reps N [--out FILE]: the A/B protocol -- every library once per repetition, alternated, a fresh process each; all figures kept
+REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 1
+res = {n: [] for n in names}
+for rep in range(REPS):
+    for name in names:
+        r = child(name)
+        if r is None:
+            continue
+        res[name].append(r)
+        print(rep, name, json.dumps(r), flush=True)
+        if "--out" in sys.argv:
+            with open(sys.argv[sys.argv.index("--out") + 1], "w") as f:
+                json.dump(res, f, indent=1)
